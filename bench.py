@@ -49,6 +49,7 @@ L1_SWEEP_ISSUES_PER_ELEMENT = 2.0
 L1_SWEEP_MICROBENCH_TELEMS = 32.9                       # register-resident ceiling of the same mix (tools/valu_bench.hip)
 REPEATS = 7                                             # timed regions per run (train) / timed passes (eval): the MEDIAN is reported
 MIN_WARM_SECONDS = 0.05                                 # warm until >= 50 ms of GPU work has run, whatever --warmup says
+DUMP_LIMIT_BYTES = 64 << 20                             # --dump-outputs: at most 64 MB of arrays
 
 
 class _KG:
@@ -143,8 +144,11 @@ def setup_headline(batch, eval_triples, device, world=1, rank=0):
 def reset_headline(H):
     """Back to the freshly initialised tables and optimiser state.  The hinge kernel skips the backward of pairs whose
     margin is already satisfied, so a step gets cheaper as training progresses: every measurement starts
-    from the same (initial, all-margins-violated) state, whatever the warm-up length."""
-    tr = H.tr
+    from the same (initial, all-margins-violated) state, whatever the warm-up length.  The batch stream is rewound too (epoch
+    order from batch 0, Philox offset 0) and the loss accumulators cleared, so every measurement steps the same batches with the
+    same negatives and computes the same outputs (--dump-outputs)."""
+    from pykg2vec_amd import kernels as K
+    tr, gen = H.tr, H.gen
     ps = getattr(tr, "_pull", None)
     if ps is not None:
         ps.cur = 0
@@ -154,8 +158,43 @@ def reset_headline(H):
         if st is not None:
             st.zero_()
     tr.flat.step = 0
+    tr.loss_buf.zero_()
+    gen.stop()
+    gen._batch_idx, gen._draws = 0, 0
     if ps is not None:
         ps.sync_in()   # row norms of the restored tables
+        if not ps.grad_only:
+            # the negatives of batch 0 at offset 0, as the previous step's ride-along sampler leaves them: the first timed step
+            # finds its list set ready, as every later one does
+            idx = gen.pull_index()
+            for ls in ps.lists:
+                ls.clear()
+            ps.cur_list = 0
+            K.pull_sample(idx.batch(0)[0], idx.inv(0), E, gen.bern, gen.slots, gen.seed, 0, ps.lists[0])
+            ps.ready = (0, 0)
+
+
+def dump_outputs(H, out_dir, world=1, rank=0):
+    """What the timed path hands its caller after its last step -> out_dir/<name>.npy: the tables the model's parameters hold
+    (float32, 6.5 MB at the headline shape) and the loss summed over the steps of the last timed region (float64, over all
+    ranks).  Every rank takes part (the loss is all-reduced); rank 0 writes.  Returns the names written."""
+    import torch.distributed as dist
+    from pykg2vec_amd import kernels as K
+    H.tr.sync_model()
+    loss = K.read_loss(H.tr.loss_buf).double().reshape(1)
+    if world > 1:
+        dist.all_reduce(loss)
+    if rank != 0:
+        return None
+    arrays = {name: getattr(H.model, name).weight.detach().float().cpu().numpy() for name in ("ent_embeddings", "rel_embeddings")}
+    arrays["loss"] = loss.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def run_headline_steps(H, n, events=None):
@@ -360,8 +399,12 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the C2 / C3 / C4 `extra` records (N=1 only)")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not run the rocprofv3 counter passes (use the committed ones)")
     ap.add_argument("--full-line", action="store_true", help="also print the complete record (tens of KB) as an earlier stdout line; it is always written to gpurun_out/bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (tables, loss of the last timed region) as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.pmc_child:
         from tools import bench_pmc
@@ -475,6 +518,8 @@ def main():
         regions.append((float(t.item()), ev_t0.elapsed_time(ev_t1) / args.steps))
     by_wall = sorted(regions)
     dt, region_ms_per_step = by_wall[len(by_wall) // 2]   # the median region: its wall clock and its HIP-event time per step
+    # ---- the outputs of the timed path: the tables and loss the LAST timed region left (every region computes the same)
+    dumped = dump_outputs(H, args.dump_outputs, world, rank) if args.dump_outputs else None
     region_spread = {"repeats": REPEATS, "ms_per_step_min": by_wall[0][0] / args.steps * 1e3, "ms_per_step_max": by_wall[-1][0] / args.steps * 1e3,
                      "ms_per_step_all": [r[0] / args.steps * 1e3 for r in regions]}
     # ---- N > 1: where a step's time goes.  A separate, untimed pass of 16 steps with an event at every phase boundary of the
@@ -741,6 +786,8 @@ def main():
             out["setup"] = setup
         if small is not None:
             out["train_reference_default_batch"] = small
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         out["live_pmc"] = live_meta if not isinstance(live_meta, str) else {"unavailable": live_meta}
     if world == 1 and not args.no_extra_configs:
         extra = {}

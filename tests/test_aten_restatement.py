@@ -1,8 +1,15 @@
 """oracle/aten_step.py (the ATen-op-for-op restatement bench.py times as `cpu_baseline.kind = "aten-restatement"` where the reference
 tree is absent) must be BIT-EQUAL to the live reference: same loss, same gradients, same weights after several optimiser steps, same
 raw and filtered ranks.  Live comparison in the build container; the frozen fixture (tests/golden/ref_aten_step.npz, written from the
-live reference by oracle/make_golden_aten.py) keeps the check alive where the tree is absent."""
+live reference by oracle/make_golden_aten.py) keeps the check alive where the tree is absent.
+
+The optimisers' elementwise arithmetic goes through MKL, which picks its code path by CPU vendor and generation: the same torch build
+computes different last bits on different hosts.  MKL's reproducible branch (MKL_CBWR=COMPATIBLE, read when MKL initialises) gives the
+same bits on every x86 host, so the fixture is frozen under it and the frozen comparisons run the restatement in a child process
+under it too."""
 import os
+import subprocess
+import sys
 import types
 
 import numpy as np
@@ -96,21 +103,57 @@ def run_reference(l1, opt_name, steps=3):
 CASES = [(True, "adam"), (False, "adam"), (True, "sgd"), (True, "adagrad"), (False, "rms")]
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="reference tree not present")
+PINNED_ENV = {"MKL_CBWR": "COMPATIBLE"}   # (oracle/make_golden_aten.py freezes under the same setting)
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _tag(l1, opt_name):
+    return "%s_%s_" % ("l1" if l1 else "l2", opt_name)
+
+
+def dump_restatement(path):
+    """Every case of run_restatement -> one .npz, keys <tag><name> (the child process of `pinned_restatement`)."""
+    np.savez(path, **{_tag(l1, o) + k: v for l1, o in CASES for k, v in run_restatement(l1, o).items()})
+
+
+@pytest.fixture(scope="module")
+def pinned_restatement(tmp_path_factory):
+    """run_restatement of every case in a fresh process with MKL on its reproducible branch."""
+    path = str(tmp_path_factory.mktemp("aten") / "restatement.npz")
+    code = "import sys; sys.path[:0] = %r; import test_aten_restatement as T; T.dump_restatement(%r)" % (
+        [HERE, os.path.join(os.path.dirname(HERE), "oracle")], path)
+    subprocess.run([sys.executable, "-s", "-c", code], env=dict(os.environ, **PINNED_ENV), check=True, timeout=600)
+    z = np.load(path)
+    return lambda l1, opt_name: {k[len(_tag(l1, opt_name)):]: z[k] for k in z.files if k.startswith(_tag(l1, opt_name))}
+
+
+def _frozen_reference(golden_dir, l1, opt_name):
+    """The reference's outputs of the same run as frozen by oracle/make_golden_aten.py (bit equality holds on that torch build only)."""
+    z = np.load(os.path.join(golden_dir, "ref_aten_step.npz"))
+    if str(z["torch_version"]) != torch.__version__:
+        pytest.skip("fixture frozen on torch %s, running %s: bit equality is only promised on the same build" % (z["torch_version"], torch.__version__))
+    assert str(z["mkl_cbwr"]) == PINNED_ENV["MKL_CBWR"]
+    return {k[len(_tag(l1, opt_name)):]: z[k] for k in z.files if k.startswith(_tag(l1, opt_name))}
+
+
 @pytest.mark.parametrize("l1,opt_name", CASES)
-def test_bit_equal_to_live_reference(l1, opt_name):
-    got, ref = run_restatement(l1, opt_name), run_reference(l1, opt_name)
+def test_bit_equal_to_live_reference(golden_dir, pinned_restatement, l1, opt_name):
+    """Live where the reference tree is importable (both runs in this process); elsewhere the pinned run against the same run's
+    frozen reference outputs."""
+    if ref_shim.reference_available():
+        ref, got = run_reference(l1, opt_name), run_restatement(l1, opt_name)
+    else:
+        ref, got = _frozen_reference(golden_dir, l1, opt_name), pinned_restatement(l1, opt_name)
+    assert set(got) == set(ref), set(got) ^ set(ref)
     for k in ref:
         assert got[k].dtype == ref[k].dtype and got[k].shape == ref[k].shape, k
         assert np.array_equal(got[k], ref[k]), (k, np.abs(got[k].astype(np.float64) - ref[k]).max())
 
 
 @pytest.mark.parametrize("l1,opt_name", CASES)
-def test_bit_equal_to_frozen_reference_outputs(golden_dir, l1, opt_name):
-    z = np.load(os.path.join(golden_dir, "ref_aten_step.npz"))
-    if str(z["torch_version"]) != torch.__version__:
-        pytest.skip("fixture frozen on torch %s, running %s: bit equality is only promised on the same build" % (z["torch_version"], torch.__version__))
-    got = run_restatement(l1, opt_name)
-    tag = "%s_%s_" % ("l1" if l1 else "l2", opt_name)
+def test_bit_equal_to_frozen_reference_outputs(golden_dir, pinned_restatement, l1, opt_name):
+    ref = _frozen_reference(golden_dir, l1, opt_name)
+    got = pinned_restatement(l1, opt_name)
+    assert set(got) == set(ref), set(got) ^ set(ref)
     for k, v in got.items():
-        assert np.array_equal(v, z[tag + k]), (tag + k)
+        assert np.array_equal(v, ref[k]), (_tag(l1, opt_name) + k)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,3 +100,28 @@ def test_rccl_setup_summary_reads_an_init_log(tmp_path, monkeypatch):
         assert bench.rccl_setup_summary() is None
     finally:
         os.remove(log)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_do_not_depend_on_the_warm_up(tmp_path):
+    """--dump-outputs DIR: what the timed path left after its last step, as DIR/<name>.npy.  Two runs whose warm-ups differ in
+    length step the same batches with the same negatives from the same tables, so they must dump the same tables (the
+    owner-computes step sums in a fixed order: bit-identical) and the same loss; the line reports --steps timed steps."""
+    runs = []
+    for warm in (2, 9):
+        d = tmp_path / ("warm%d" % warm)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", str(warm), "--eval-triples",
+               "256", "--no-cpu-baseline", "--no-extra-configs", "--no-live-pmc", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.splitlines()[-1])
+        assert line["steps"] == 5 and line["warmup"] == warm and line["ms_per_step"] > 0
+        assert line["ms_per_step"] == pytest.approx(line["timed_region_s"] / 5 * 1e3, rel=1e-3)   # (the line rounds both)
+        assert sorted(os.listdir(d)) == ["ent_embeddings.npy", "loss.npy", "rel_embeddings.npy"]
+        runs.append({n: np.load(str(d / (n + ".npy"))) for n in ("ent_embeddings", "rel_embeddings", "loss")})
+    a, b = runs
+    assert a["ent_embeddings"].shape == (bench.E, bench.DIM) and a["rel_embeddings"].shape == (bench.R, bench.DIM)
+    assert a["ent_embeddings"].dtype == np.float32 and a["loss"].dtype == np.float64 and a["loss"][0] > 0
+    for n in ("ent_embeddings", "rel_embeddings"):
+        assert np.all(np.isfinite(a[n])) and np.array_equal(a[n], b[n]), n
+    assert a["loss"][0] == pytest.approx(b["loss"][0], rel=1e-5)

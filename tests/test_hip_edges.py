@@ -182,8 +182,12 @@ def test_bench_eight_ranks_share_one_gpu(env_extra, label):
     GPU: eight processes (gloo, all on device 0) shard the batch and the Philox stream eight ways, exchange the flat gradient, and must
     end with bit-identical tables; the test split (59 071 triples, not a multiple of 8) is sharded over the ranks for the eval leg; rank
     0 prints the one JSON line with the per-phase times and the collective description.  Nothing here needs RCCL: what is rehearsed
-    is every line of bench.py's and the Trainer's N = 8 path except the transport."""
+    is every line of bench.py's and the Trainer's N = 8 path except the transport.  At most six processes may hold one GPU at a
+    time, so the eight ranks need eight GPUs (KGE_BENCH_SHARE_GPU then gives each rank a device of its own)."""
     import json, os, subprocess, sys
+    n_dev = torch.cuda.device_count()
+    if n_dev < 8:
+        pytest.skip("needs 8 GPUs (one per rank: eight ranks are more processes than one GPU may hold), found %d" % n_dev)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KGE_BENCH_SHARE_GPU="1", KGE_BENCH_CHECK_REPLICAS="1", **env_extra)
     port = {"all-reduce": "29531", "sharded": "29533", "owner-computes": "29535"}[label]

@@ -203,26 +203,33 @@ def test_stand_alone_trainer_stops_early_checkpoints_the_best_and_keeps_referenc
     tr3.load_model()
 
 
-def test_patience_rule_equals_the_reference_early_stopper():
+PATIENCE_MONITORS, PATIENCE_VALUES, PATIENCE_TRIALS = ("mr", "fmr", "mrr", "fmrr"), (-1, 0, 1, 3), 20
+
+
+def patience_sequences():
+    """The metric sequences the stopper rule is pinned on: [monitor, patience, trial, epoch], plenty of equal and worse
+    neighbours (also the input of oracle/make_golden_stopper.py)."""
+    rng = np.random.default_rng(0)
+    return rng.integers(0, 4, size=(len(PATIENCE_MONITORS), len(PATIENCE_VALUES), PATIENCE_TRIALS, 25)).astype(float)
+
+
+def test_patience_rule_equals_the_reference_early_stopper(golden_dir):
     """PatienceStopper.should_stop == the reference's EarlyStopper.should_stop on the same metric sequences, for every monitor and
-    for zero / positive / negative patience (utils/trainer.py:22-68).  Needs the reference tree (build container only)."""
-    import ref_shim
-    if not ref_shim.reference_available():
-        pytest.skip("reference tree not present")
-    ref_shim.install()
-    from pykg2vec.utils.trainer import EarlyStopper
-    from pykg2vec.common import Monitor as RefMonitor
+    for zero / positive / negative patience (utils/trainer.py:22-68): the reference's decisions are frozen in
+    tests/golden/ref_early_stopper.npz (oracle/make_golden_stopper.py)."""
     from pykg2vec_amd.trainer import PatienceStopper
     from pykg2vec_amd.common import Monitor
-    rng = np.random.default_rng(0)
-    for mon in ("mr", "fmr", "mrr", "fmrr"):
-        for patience in (-1, 0, 1, 3):
-            for trial in range(20):
-                ours, ref = PatienceStopper(patience, Monitor(mon)), EarlyStopper(patience, RefMonitor(mon))
-                seq = rng.integers(0, 4, size=25).astype(float)          # plenty of equal and worse neighbours
-                for v in seq:
+    z = np.load(os.path.join(golden_dir, "ref_early_stopper.npz"))
+    seqs, ref = z["sequences"], z["should_stop"]
+    assert np.array_equal(seqs, patience_sequences()) and ref.shape == seqs.shape
+    assert ref.any() and not ref.all()   # the fixture holds both answers
+    for i, mon in enumerate(PATIENCE_MONITORS):
+        for j, patience in enumerate(PATIENCE_VALUES):
+            for trial in range(PATIENCE_TRIALS):
+                ours = PatienceStopper(patience, Monitor(mon))
+                for k, v in enumerate(seqs[i, j, trial]):
                     metrics = {"mr": v, "fmr": v, "mrr": v, "fmrr": v}
-                    assert ours.should_stop(metrics) == ref.should_stop(metrics), (mon, patience, trial)
+                    assert ours.should_stop(metrics) == bool(ref[i, j, trial, k]), (mon, patience, trial, k)
 
 
 def test_relation_property_matches_reference_rule():
