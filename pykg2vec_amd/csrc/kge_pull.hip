@@ -61,7 +61,8 @@ struct PullArgs {
     const float* theta;        // TransM (pairwise.py:341-347): fixed per-relation weight of both energies; NULL = TransE
     // two-phase ("staged direction") form: k_pull_eval leaves one record per pair, the owners of k_pull_step<..., DIR> sum them
     float4* recs;              // [n_pairs] (coef * theta, energy(+), energy(-), tail as 0 / 1)
-    void* codes;               // [n_pairs][2][G * NV] one byte per lane = the signs of its four residual elements (2 bits each)
+    void* codes;               // [n_pairs][G * NV] 16 bits per lane: the signs of its four elements of the positive residual (2 bits each,
+                               // low byte) and of the negative residual (high byte) -- one 16-bit load per visit
     int64_t n_pairs;
 };
 
@@ -164,12 +165,14 @@ struct PullRows {
 // ---- phase 1 of the two-phase form: every pair of the batch is evaluated ONCE by one lane group -- the same four gathers, the
 // same arithmetic in the same order as a visit of k_pull_step -- and leaves a record: the hinge coefficient, and the signed
 // direction of both residuals (two bits per element).  L1 only (see launch_pull_step).  No sampling here: the draw was
-// registered by the sampler riding in the previous step's launch.
+// registered by the sampler riding in the previous step's launch.  (Moving the next batch's sampler here was measured slower: its
+// ~10 us chain of dependent loads and atomics outlives the evaluation's 5 us workgroups; profiles/r07_eval_sampler_ab.txt.)
 // kEvalPP pairs per lane group, their descriptors and then their four rows requested together (independent chains): half the
 // workgroups -- 2 048 at B = 32 768, ONE residency round of 8 x 256 workgroups instead of two -- and half the workgroup launches
 // (per-workgroup timestamps: the dispatcher needs 1.8 us to start 2 048 workgroups; profiles/r04_experiments.md section 7).
 constexpr int kEvalPP = 2;
 constexpr bool kHatCompactDefault = true;   // hat rows: padded to 4 * G * NV floats (rounds 2-5) or compact (KGE_HAT_COMPACT=1)
+// (C1, NV = 1: 62 VGPRs -- 8 waves per SIMD, the launch's 2 048 workgroups are one residency round; tests/test_pull_occupancy.py checks it)
 template <bool L1, int G, int NV>
 __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restrict__ loss) {
     constexpr int GPB = kBlock / G, PP = kEvalPP;
@@ -241,7 +244,7 @@ __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restr
         if (gl == 0) a.recs[i] = make_float4(tail ? -coef : coef, sp, sn, 0.f);   // (coef >= 0: its sign carries `tail`)
         if (coef != 0.f) {
             if constexpr (L1) {
-                unsigned char* cp = reinterpret_cast<unsigned char*>(a.codes) + i * (int64_t)(2 * G * NV);
+                unsigned short* cp = reinterpret_cast<unsigned short*>(a.codes) + i * (int64_t)(G * NV);
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
                     // the sign k_pull_step uses: clamp(x * 2^100, -1, 1); code 0 = zero, 1 = positive, 3 = negative: the two bits ARE the
@@ -254,8 +257,7 @@ __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restr
                       bn |= (s2 > 0.f ? 1u : (s2 < 0.f ? 3u : 0u)) << sh; }
                     KGE_CODE(x, 0) KGE_CODE(y, 2) KGE_CODE(z, 4) KGE_CODE(w, 6)
 #undef KGE_CODE
-                    cp[v * G + gl] = (unsigned char)bp;
-                    cp[G * NV + v * G + gl] = (unsigned char)bn;
+                    cp[v * G + gl] = (unsigned short)(bp | bn << 8);
                 }
             }
         }
@@ -264,8 +266,11 @@ __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restr
     KGE_TS_END(1, 1)
 }
 
+// (two-phase form with NV = 1: 8 waves per SIMD, 2 048 workgroup slots instead of 1 792 for the C1 launch's 2 045 owner and 128 sampler
+//  workgroups.  The attribute is a guard: the code fits without it; an edit that needs more registers now spills, which
+//  tests/test_pull_occupancy.py reports)
 template <int OPT, bool L1, int G, int NV, bool DIR = false>
-__global__ __launch_bounds__(kBlock) void k_pull_step(PullArgs a, PullSampleArgs sa, float* __restrict__ loss) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIR && NV == 1 ? 8 : 1))) void k_pull_step(PullArgs a, PullSampleArgs sa, float* __restrict__ loss) {
     static_assert(!DIR || L1, "the two-phase form exists for L1 only");
     constexpr int GPB = kBlock / G;
     KGE_TS_BEGIN(0)
@@ -338,7 +343,7 @@ __global__ __launch_bounds__(kBlock) void k_pull_step(PullArgs a, PullSampleArgs
             int4 gi[NV];
 #pragma unroll
             for (int v = 0; v < NV; ++v) gi[v] = make_int4(0, 0, 0, 0);
-            auto visit_dir = [&](int e, const RecT rec, const auto& cpv, const auto& cnv) {
+            auto visit_dir = [&](auto unit_c, int e, const RecT rec, const auto& cv) {   // (unit_c: std::bool_constant<unit>)
                 const int role = e & 3;
                 const unsigned rbits = __float_as_uint(rec_x(rec));
                 const float coef = fabsf(rec_x(rec));
@@ -347,66 +352,75 @@ __global__ __launch_bounds__(kBlock) void k_pull_step(PullArgs a, PullSampleArgs
                 const int lu = __builtin_amdgcn_sbfe(0x05F5, sh2, 2u), lv = __builtin_amdgcn_sbfe(0x7F1C, sh2, 2u);
                 float su = (float)lu * coef, sv = (float)lv * coef;
                 if constexpr (L1) {
-                    if (unit) {
+                    if constexpr (decltype(unit_c)::value) {
                         const int c2 = coef == 1.f ? 2 : 1;
                         const int iu = __mul24(lu, c2), iv = __mul24(lv, c2);
 #pragma unroll
                         for (int v2 = 0; v2 < NV; ++v2) {
-                            const unsigned bp = cpv[v2], bn = cnv[v2];
+                            const unsigned b = cv[v2];   // (positive residual: bits 0..7, negative: bits 8..15)
 #define KGE_DECI(b, sh) (((int)((unsigned)(b) << (30 - (sh)))) >> 30)
-                            gi[v2].x = mad_i24(iv, KGE_DECI(bn, 0), mad_i24(iu, KGE_DECI(bp, 0), gi[v2].x));
-                            gi[v2].y = mad_i24(iv, KGE_DECI(bn, 2), mad_i24(iu, KGE_DECI(bp, 2), gi[v2].y));
-                            gi[v2].z = mad_i24(iv, KGE_DECI(bn, 4), mad_i24(iu, KGE_DECI(bp, 4), gi[v2].z));
-                            gi[v2].w = mad_i24(iv, KGE_DECI(bn, 6), mad_i24(iu, KGE_DECI(bp, 6), gi[v2].w));
+                            gi[v2].x = mad_i24(iv, KGE_DECI(b, 8), mad_i24(iu, KGE_DECI(b, 0), gi[v2].x));
+                            gi[v2].y = mad_i24(iv, KGE_DECI(b, 10), mad_i24(iu, KGE_DECI(b, 2), gi[v2].y));
+                            gi[v2].z = mad_i24(iv, KGE_DECI(b, 12), mad_i24(iu, KGE_DECI(b, 4), gi[v2].z));
+                            gi[v2].w = mad_i24(iv, KGE_DECI(b, 14), mad_i24(iu, KGE_DECI(b, 6), gi[v2].w));
 #undef KGE_DECI
                         }
                         return;
                     }
 #pragma unroll
                     for (int v2 = 0; v2 < NV; ++v2) {
-                        const unsigned bp = cpv[v2], bn = cnv[v2];
+                        const unsigned b = cv[v2];
 #define KGE_DEC(b, sh) ((float)(((int)((b) << (30 - (sh)))) >> 30))   /* 2-bit two's complement: 01 -> +1, 11 -> -1, 00 -> 0 */
-                        gs[v2].x = fmaf(sv, KGE_DEC(bn, 0), fmaf(su, KGE_DEC(bp, 0), gs[v2].x));
-                        gs[v2].y = fmaf(sv, KGE_DEC(bn, 2), fmaf(su, KGE_DEC(bp, 2), gs[v2].y));
-                        gs[v2].z = fmaf(sv, KGE_DEC(bn, 4), fmaf(su, KGE_DEC(bp, 4), gs[v2].z));
-                        gs[v2].w = fmaf(sv, KGE_DEC(bn, 6), fmaf(su, KGE_DEC(bp, 6), gs[v2].w));
+                        gs[v2].x = fmaf(sv, KGE_DEC(b, 8), fmaf(su, KGE_DEC(b, 0), gs[v2].x));
+                        gs[v2].y = fmaf(sv, KGE_DEC(b, 10), fmaf(su, KGE_DEC(b, 2), gs[v2].y));
+                        gs[v2].z = fmaf(sv, KGE_DEC(b, 12), fmaf(su, KGE_DEC(b, 4), gs[v2].z));
+                        gs[v2].w = fmaf(sv, KGE_DEC(b, 14), fmaf(su, KGE_DEC(b, 6), gs[v2].w));
 #undef KGE_DEC
                     }
                 }
             };
             using CodeT = unsigned;
-            auto load_codes = [&](int pair, CodeT (&cpv)[NV], CodeT (&cnv)[NV]) {
+            auto load_codes = [&](int pair, CodeT (&cv)[NV]) {
                 if constexpr (L1) {
                     // (32-bit byte offsets from the uniform base: one shift-add per visit instead of 64-bit address arithmetic per load;
-                    //  n_pairs * 2 G NV bytes < 4 GiB is checked where the buffers are sized)
-                    const unsigned char* __restrict__ cbase = reinterpret_cast<const unsigned char*>(a.codes);
-                    const unsigned off = (unsigned)pair * (unsigned)(2 * G * NV) + (unsigned)gl;
+                    //  n_pairs * 2 G NV bytes < 4 GiB is checked where the buffers are sized).  One 16-bit load per lane and chunk: the
+                    //  positive residual's code in the low byte, the negative's in the high byte -- one register for both
+                    const char* __restrict__ cbase = reinterpret_cast<const char*>(a.codes);
+                    const unsigned off = ((unsigned)pair * (unsigned)(G * NV) + (unsigned)gl) * 2u;
 #pragma unroll
-                    for (int v2 = 0; v2 < NV; ++v2) { cpv[v2] = cbase[off + (unsigned)(v2 * G)]; cnv[v2] = cbase[off + (unsigned)(G * NV + v2 * G)]; }
+                    for (int v2 = 0; v2 < NV; ++v2) cv[v2] = *reinterpret_cast<const unsigned short*>(cbase + off + (unsigned)(2 * v2 * G));
                 }
             };
 #ifndef KGE_DIR_BATCH
 #define KGE_DIR_BATCH 4
 #endif
-            constexpr int kDirBatch = KGE_DIR_BATCH;     // visits whose records and codes are requested before the first is summed
+            // visits whose records and codes are requested before the first is summed: 4 on the integer path; 2 on the float path
+            // (theta != NULL), whose decoded signs are converted to float ahead of the sums -- at 4 that path alone set the kernel's
+            // register peak (69 VGPRs, 7 waves per SIMD)
+            constexpr int kDirBatch = KGE_DIR_BATCH, kDirBatchF = KGE_DIR_BATCH < 2 ? KGE_DIR_BATCH : 2;
 #ifdef KGE_DIR_NOVISIT   /* timing experiment only: how long is phase 2 without its visits? */
             nvis = 0;
 #endif
-            for (int v0 = 0; v0 < nvis; v0 += kDirBatch) {
-                int e[kDirBatch];
-                RecT rec[kDirBatch];
-                CodeT cpv[kDirBatch][NV], cnv[kDirBatch][NV];
+            auto visit_all = [&](auto unit_c, auto batch_c) {
+                constexpr int kB = decltype(batch_c)::value;
+                for (int v0 = 0; v0 < nvis; v0 += kB) {
+                    int e[kB];
+                    RecT rec[kB];
+                    CodeT cv[kB][NV];
 #pragma unroll
-                for (int q = 0; q < kDirBatch; ++q) {
-                    e[q] = v0 + q < nvis ? vis[v0 + q] : -1;
-                    const int pair = e[q] >= 0 ? (e[q] >> 2) : 0;
-                    rec[q] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.recs) + (unsigned)pair * 16u);
-                    load_codes(pair, cpv[q], cnv[q]);
+                    for (int q = 0; q < kB; ++q) {
+                        e[q] = v0 + q < nvis ? vis[v0 + q] : -1;
+                        const int pair = e[q] >= 0 ? (e[q] >> 2) : 0;
+                        rec[q] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.recs) + (unsigned)pair * 16u);
+                        load_codes(pair, cv[q]);
+                    }
+#pragma unroll
+                    for (int q = 0; q < kB; ++q)
+                        if (e[q] >= 0) visit_dir(unit_c, e[q], rec[q], cv[q]);
                 }
-#pragma unroll
-                for (int q = 0; q < kDirBatch; ++q)
-                    if (e[q] >= 0) visit_dir(e[q], rec[q], cpv[q], cnv[q]);
-            }
+            };
+            if (unit) visit_all(std::true_type{}, std::integral_constant<int, kDirBatch>{});
+            else visit_all(std::false_type{}, std::integral_constant<int, kDirBatchF>{});
             if (cnt > 0 && !fast_c) {   // more drawers than the bucket / lane group holds: pair-ordered walk over bucket + chain
                 const int nb = cnt < kPullCap ? cnt : kPullCap;
                 int last = -1;
@@ -415,11 +429,12 @@ __global__ __launch_bounds__(kBlock) void k_pull_step(PullArgs a, PullSampleArgs
                     for (int m = 0; m < nb; ++m) { const int j = a.lists.bucket[(int64_t)g * kPullCap + m]; if (j > last && j < best) best = j; }
                     for (int j = a.lists.head[g]; j >= 0; j = a.lists.next[j]) if (j > last && j < best) best = j;
                     if (best == 0x7FFFFFFF) break;
-                    CodeT c1[NV], c2[NV];
-                    load_codes(best, c1, c2);
+                    CodeT c1[NV];
+                    load_codes(best, c1);
                     RecT rb;
                     rb = reinterpret_cast<const float*>(a.recs)[4 * (int64_t)best];
-                    visit_dir((best << 2) | kRoleC, rb, c1, c2);
+                    if (unit) visit_dir(std::true_type{}, (best << 2) | kRoleC, rb, c1);
+                    else visit_dir(std::false_type{}, (best << 2) | kRoleC, rb, c1);
                     last = best;
                 }
             }
