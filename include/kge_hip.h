@@ -46,7 +46,10 @@ enum kge_model {
     KGE_SIMPLE = 11,  /* pointwise.py:461-546 ent_head, ent_tail, rel, rel_inv; energy = -clamp(<h,r,t> + <t,r_inv,h>/2, +-20) */
     KGE_SIMPLE_IGNR = 12, /* pointwise.py:549-592 same tables; energy = -clamp(<h,r,t> + <t,r_inv,h>, +-20) */
     KGE_QUATE = 13,   /* pointwise.py:595-768 ent_s, ent_x, ent_y, ent_z, rel_s, rel_x, rel_y, rel_z (rel_w is unused by forward) */
-    KGE_TRANSR = 14   /* pairwise.py:367-470  ent_embeddings[E,dim], rel_embeddings[R,rel_dim], rel_matrix[R, dim*rel_dim] */
+    KGE_TRANSR = 14,  /* pairwise.py:367-470  ent_embeddings[E,dim], rel_embeddings[R,rel_dim], rel_matrix[R, dim*rel_dim] */
+    KGE_SLM = 15,     /* pairwise.py:473-541  ent_embeddings[E,dim], rel_embeddings[R,rel_dim], mr1[dim,rel_dim], mr2[dim,rel_dim] */
+    KGE_SME = 16,     /* pairwise.py:544-657  ent, rel, mu1[d,d], mu2[d,d], bu[d,1], mv1[d,d], mv2[d,d], bv[d,1] (rel_dim == dim) */
+    KGE_SME_BL = 17   /* pairwise.py:660-724  same tables as SME; bilinear hidden layer, energy = +gu.gv */
 };
 
 #define KGE_FLAG_L1 1u /* l1_flag of TransE/TransH/TransD (pairwise.py:72-76) */
@@ -115,7 +118,8 @@ int kge_debug_marker(int32_t tag, void* stream);
  * 0 for the gather-type models; RESCAL and TransR group the batch by relation on the device (about 5R + n + n/32 ints per side),
  * TransR's large-batch pairwise step (negatives that keep their positives' relations: nr == pr) keeps
  * 2n*(rel_dim + 1) floats per side between its two launches (dL/d(h^ M), dL/d(t^ M) and the rows' inverse norms),
- * NTN keeps n*(4d + 3k_r + 6) floats of intermediates per side; the hinge step adds 2n floats. */
+ * NTN keeps n*(4d + 3k_r + 6) floats of intermediates per side; SME / SME_BL n*(6d + 3), SLM n*(2k_r + 3), plus 128 partials
+ * of the shared-matrix gradients (4d^2 + 2d / 2 d k_r floats each); the hinge step adds 2n floats. */
 size_t kge_workspace_bytes(const kge_model_desc* m, int64_t n);
 
 /* Model.forward(h, r, t) -> energies[n]   (pairwise.py:56-76,166-174,270-278,786-791,855-860,955-960;

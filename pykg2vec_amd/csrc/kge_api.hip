@@ -47,7 +47,8 @@ static int table_count(int model) {
         case KGE_NTN: case KGE_ANALOGY: return 6;
         case KGE_TRANSM: case KGE_CP: case KGE_TRANSR: return 3;
         case KGE_SIMPLE: case KGE_SIMPLE_IGNR: return 4;
-        case KGE_QUATE: return 8;
+        case KGE_QUATE: case KGE_SME: case KGE_SME_BL: return 8;
+        case KGE_SLM: return 4;
     }
     return -1;
 }
@@ -127,6 +128,7 @@ int kge_score_forward(const kge_model_desc* m, const int64_t* h, const int64_t* 
     if (m->model == KGE_RESCAL) return launch_rescal_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     if (m->model == KGE_NTN) return launch_ntn_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     if (m->model == KGE_TRANSR) return launch_transr_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
+    if (is_semantic_model(m->model)) return launch_semantic_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     return launch_score_forward(m, h, r, t, n, scores, s);
 }
 
@@ -140,6 +142,7 @@ int kge_score_backward(const kge_model_desc* m, const int64_t* h, const int64_t*
     if (m->model == KGE_RESCAL) return launch_rescal_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
     if (m->model == KGE_NTN) return launch_ntn_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
     if (m->model == KGE_TRANSR) return launch_transr_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
+    if (is_semantic_model(m->model)) return launch_semantic_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, s);
     return launch_score_backward(m, h, r, t, n, dscore, s);
 }
 
@@ -204,6 +207,11 @@ int kge_train_pairwise_hinge(const kge_model_desc* m, const int64_t* ph, const i
         if ((rc = launch_transr_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
         if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
         return launch_transr_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
+    }
+    if (is_semantic_model(m->model)) {   // SLM / SME / SME_BL (kge_semantic.hip): the NTN route
+        if ((rc = launch_semantic_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
+        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
+        return launch_semantic_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
     }
     set_error("kge_train_pairwise_hinge: unsupported model %d", m->model);
     return -1;

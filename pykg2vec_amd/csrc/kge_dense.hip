@@ -472,6 +472,7 @@ size_t dense_workspace_bytes(const kge_model_desc* m, int64_t n) {
     if (m->model == KGE_RESCAL) return group_ws_bytes(m->tot_relation, n);
     if (m->model == KGE_NTN) return ntn_workspace_bytes(m, n);
     if (m->model == KGE_TRANSR) return transr_workspace_bytes(m, n);
+    if (is_semantic_model(m->model)) return semantic_workspace_bytes(m, n);
     return 0;
 }
 

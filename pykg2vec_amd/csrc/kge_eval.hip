@@ -90,7 +90,7 @@ static bool make_plan(const kge_model_desc* m, int64_t n, void* ws, EvalPlan* p,
             p->form = (m->flags & KGE_FLAG_L1) ? F_L1 : F_L2; break;
         case KGE_ROTATE: p->form = F_SQM; break;
         case KGE_DISTMULT: case KGE_COMPLEX: case KGE_ANALOGY: case KGE_RESCAL:
-        case KGE_CP: case KGE_SIMPLE: case KGE_SIMPLE_IGNR: case KGE_QUATE: case KGE_HEAD_1N_INTERNAL: p->form = F_NEGDOT; break;
+        case KGE_CP: case KGE_SIMPLE: case KGE_SIMPLE_IGNR: case KGE_QUATE: case KGE_HEAD_1N_INTERNAL: case KGE_DOT_INTERNAL: p->form = F_NEGDOT; break;
         default: return false;
     }
     p->post = m->model == KGE_TRANSM ? P_SCALE : (m->model == KGE_SIMPLE || m->model == KGE_SIMPLE_IGNR) ? P_CLAMP
@@ -121,6 +121,7 @@ static bool make_plan(const kge_model_desc* m, int64_t n, void* ws, EvalPlan* p,
 
 size_t eval_workspace_bytes(const kge_model_desc* m, int64_t n, int64_t tables) {
     if (m->model == KGE_NTN) return ntn_eval_workspace_bytes(m, n);
+    if (is_semantic_model(m->model)) return semantic_eval_workspace_bytes(m, n);
     EvalPlan p;
     if (!make_plan(m, n, nullptr, &p, tables)) return 0;
     return p.bytes;
@@ -499,6 +500,10 @@ __global__ __launch_bounds__(256) void k_eval_queries(DeviceModel m, const int64
         const float* x = m.tab[2] + i * d;
         for (int k = lane; k < d; k += TPT) { qt[k] = x[k]; qh[k] = 0.f; }
         if (lane == 0 && m.tab[1] != nullptr) { qt[d] = 1.0f; qh[d] = 0.f; }
+    } else if constexpr (M == KGE_DOT_INTERNAL) {
+        // caller-built query rows: x [n, 2, K], row 2i = the tail sweep of triple i, 2i + 1 = its head sweep
+        const float* x = m.tab[2] + 2 * i * d;
+        for (int k = lane; k < d; k += TPT) { qt[k] = x[k]; qh[k] = x[d + k]; }
     } else if constexpr (M == KGE_DISTMULT) {
         const float* eh = m.tab[0] + h * d; const float* er = m.tab[1] + r * d; const float* et = m.tab[0] + t * d;
         for (int k = lane; k < d; k += TPT) { qt[k] = eh[k] * er[k]; qh[k] = er[k] * et[k]; }
@@ -1724,7 +1729,7 @@ static int run_pipeline(const kge_model_desc* m, const int64_t* triples, int64_t
     switch (m->model) {
         KGE_Q(KGE_TRANSE) KGE_Q(KGE_TRANSH) KGE_Q(KGE_TRANSD) KGE_Q(KGE_ROTATE) KGE_Q(KGE_DISTMULT)
         KGE_Q(KGE_COMPLEX) KGE_Q(KGE_ANALOGY) KGE_Q(KGE_RESCAL)
-        KGE_Q(KGE_TRANSM) KGE_Q(KGE_CP) KGE_Q(KGE_SIMPLE) KGE_Q(KGE_SIMPLE_IGNR) KGE_Q(KGE_QUATE) KGE_Q(KGE_HEAD_1N_INTERNAL)
+        KGE_Q(KGE_TRANSM) KGE_Q(KGE_CP) KGE_Q(KGE_SIMPLE) KGE_Q(KGE_SIMPLE_IGNR) KGE_Q(KGE_QUATE) KGE_Q(KGE_HEAD_1N_INTERNAL) KGE_Q(KGE_DOT_INTERNAL)
         default: set_error("kge_eval: unsupported model %d", m->model); return -1;
     }
 #undef KGE_Q
@@ -1765,6 +1770,8 @@ int launch_eval_ranks(const kge_model_desc* m, const int64_t* triples, int64_t n
         if (ties) (void)hipMemsetAsync(ties, 0xFF, (size_t)2 * n * sizeof(int32_t), s);
         return launch_ntn_eval_ranks(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, s);
     }
+    if (is_semantic_model(m->model))
+        return launch_semantic_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
     return run_pipeline(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s);
 }
 
@@ -1822,7 +1829,31 @@ int launch_eval_sweep_scores(const kge_model_desc* m, const int64_t* triples, in
         if (side != 2) { set_error("kge_eval_sweep_scores_side: the NTN sweep computes both sides per call"); return -1; }
         return launch_ntn_eval_scores(m, triples, n, ws, ws_bytes, scores, s);
     }
+    if (is_semantic_model(m->model))
+        return launch_semantic_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
     return run_pipeline(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
+}
+
+static kge_model_desc dot_desc(const float* cand, const float* q, int K, int64_t E) {
+    kge_model_desc m;
+    memset(&m, 0, sizeof(m));
+    m.model = KGE_DOT_INTERNAL;
+    m.tot_entity = E; m.tot_relation = 1; m.dim = K; m.rel_dim = K;
+    m.tables[0] = const_cast<float*>(cand); m.tables[2] = const_cast<float*>(q);
+    return m;
+}
+
+size_t dot_eval_workspace_bytes(int64_t n, int K, int64_t E) {
+    const kge_model_desc m = dot_desc(nullptr, nullptr, K, E);
+    EvalPlan p;
+    return make_plan(&m, n, nullptr, &p) ? p.bytes : 0;
+}
+
+int launch_dot_eval(const float* cand, const float* q, int K, int64_t E, const int64_t* triples, int64_t n, const int64_t* tail_off,
+                    const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes,
+                    int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side) {
+    const kge_model_desc m = dot_desc(cand, q, K, E);
+    return run_pipeline(&m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, scores, s, side);
 }
 
 static kge_model_desc head_rank_desc(const float* x, int dim, const float* ent, int64_t E, const float* bias) {

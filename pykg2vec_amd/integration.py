@@ -10,7 +10,7 @@ drop-in models, generator and evaluator.
 """
 import types
 
-PAIRWISE = ("TransE", "TransH", "TransD", "TransM", "TransR", "RotatE", "Rescal", "NTN")
+PAIRWISE = ("TransE", "TransH", "TransD", "TransM", "TransR", "RotatE", "Rescal", "NTN", "SLM", "SME", "SME_BL")
 POINTWISE = ("DistMult", "Complex", "ComplexN3", "ANALOGY", "CP", "SimplE", "SimplE_ignr", "QuatE")
 
 

@@ -14,7 +14,7 @@ from . import _lib as L
 MODEL_IDS = {"transe": L.TRANSE, "transh": L.TRANSH, "transd": L.TRANSD, "rotate": L.ROTATE, "rescal": L.RESCAL,
              "ntn": L.NTN, "distmult": L.DISTMULT, "complex": L.COMPLEX, "complexn3": L.COMPLEX, "analogy": L.ANALOGY,
              "transm": L.TRANSM, "cp": L.CP, "simple": L.SIMPLE, "simple_ignr": L.SIMPLE_IGNR, "quate": L.QUATE,
-             "transr": L.TRANSR}
+             "transr": L.TRANSR, "slm": L.SLM, "sme": L.SME, "sme_bl": L.SME_BL}
 OPTIMIZER_IDS = {"sgd": L.OPT_SGD, "adam": L.OPT_ADAM, "adagrad": L.OPT_ADAGRAD, "rms": L.OPT_RMSPROP,
                  "gradient": 4}   # KGE_OPT_GRADIENT: kge_pull_step writes the dense gradient instead of updating
 
@@ -51,6 +51,9 @@ _TABLE_SHAPES = {
     "rescal": [("E", "d"), ("R", "d*d")],
     "ntn": [("E", "d"), ("R", "k"), ("d", "k"), ("d", "k"), (1, "k"), ("k", "d*d")],
     "transr": [("E", "d"), ("R", "k"), ("R", "d*k")],
+    "slm": [("E", "d"), ("R", "k"), ("d", "k"), ("d", "k")],
+    "sme": [("E", "d"), ("R", "d"), ("d", "d"), ("d", "d"), ("d", 1), ("d", "d"), ("d", "d"), ("d", 1)],
+    "sme_bl": [("E", "d"), ("R", "d"), ("d", "d"), ("d", "d"), ("d", 1), ("d", "d"), ("d", "d"), ("d", 1)],
     "distmult": [("E", "d"), ("R", "d")],
     "complex": [("E", "d"), ("E", "d"), ("R", "d"), ("R", "d")],
     "complexn3": [("E", "d"), ("E", "d"), ("R", "d"), ("R", "d")],
@@ -678,8 +681,8 @@ def eval_sweep_scores(desc, triples, workspace=None):
 
 def eval_sweep_scores_side(desc, triples, side, workspace=None):
     """float32 [n, E]: side 0 = energies of (h_i, r_i, e) for all e, side 1 = energies of (e, r_i, t_i); the other side's query
-    is never swept (kge_eval_sweep_scores_side).  TransR / NTN compute both sides per call: the full sweep, sliced."""
-    if desc.model in (MODEL_IDS["transr"], MODEL_IDS["ntn"]):
+    is never swept (kge_eval_sweep_scores_side).  TransR / NTN / SLM compute both sides per call: the full sweep, sliced."""
+    if desc.model in (MODEL_IDS["transr"], MODEL_IDS["ntn"], MODEL_IDS["slm"]):
         return eval_sweep_scores(desc, triples, workspace)[int(side)::2]
     n = triples.shape[0]
     if workspace is None:

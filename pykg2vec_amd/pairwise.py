@@ -230,3 +230,65 @@ class NTN(PairwiseModel):
 
     def get_reg(self, h, r, t):
         return self.lmbda * torch.sqrt(sum(torch.sum(p.weight ** 2) for p in self.parameter_list))
+
+
+class SLM(PairwiseModel):
+    """pairwise.py:473-541.  energy = -r^ . tanh(h^ M1 + t^ M2): NTN without the bilinear tensor and the bias."""
+    kernel_name = "slm"
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "rel_hidden_size", "ent_hidden_size"], kwargs))
+        d, k = self.ent_hidden_size, self.rel_hidden_size
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, d)
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation, k)
+        self.mr1 = NamedEmbedding("mr1", d, k)
+        self.mr2 = NamedEmbedding("mr2", d, k)
+        _xavier(self.ent_embeddings, self.rel_embeddings, self.mr1, self.mr2)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings, self.mr1, self.mr2]
+        self.loss = Criterion.pairwise_hinge
+
+    def desc_kwargs(self):
+        return dict(dim=self.ent_hidden_size, rel_dim=self.rel_hidden_size)
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+
+class SME(PairwiseModel):
+    """pairwise.py:544-657.  gu = mu1 h^ + mu2 r^ + bu, gv = mv1 t^ + mv2 r^ + bv, energy = -gu . gv."""
+    kernel_name = "sme"
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "hidden_size"], kwargs))
+        d = self.hidden_size
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, d)
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation, d)
+        self.mu1 = NamedEmbedding("mu1", d, d)
+        self.mu2 = NamedEmbedding("mu2", d, d)
+        self.bu = NamedEmbedding("bu", d, 1)
+        self.mv1 = NamedEmbedding("mv1", d, d)
+        self.mv2 = NamedEmbedding("mv2", d, d)
+        self.bv = NamedEmbedding("bv", d, 1)
+        _xavier(self.ent_embeddings, self.rel_embeddings, self.mu1, self.mu2, self.bu, self.mv1, self.mv2, self.bv)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings, self.mu1, self.mu2, self.bu, self.mv1, self.mv2,
+                               self.bv]
+        self.loss = Criterion.pairwise_hinge
+
+    def desc_kwargs(self):
+        return dict(dim=self.hidden_size)
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+
+class SME_BL(SME):
+    """pairwise.py:660-724.  gu = (mu1 h^) * (mu2 r^) + bu, gv = (mv1 t^) * (mv2 r^) + bv, energy = +gu . gv (the reference's
+    sign: unlike SME, the sum is not negated)."""
+    kernel_name = "sme_bl"
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.model_name = self.__class__.__name__.lower()
+        self.loss = Criterion.pairwise_hinge
