@@ -49,7 +49,9 @@ enum kge_model {
     KGE_TRANSR = 14,  /* pairwise.py:367-470  ent_embeddings[E,dim], rel_embeddings[R,rel_dim], rel_matrix[R, dim*rel_dim] */
     KGE_SLM = 15,     /* pairwise.py:473-541  ent_embeddings[E,dim], rel_embeddings[R,rel_dim], mr1[dim,rel_dim], mr2[dim,rel_dim] */
     KGE_SME = 16,     /* pairwise.py:544-657  ent, rel, mu1[d,d], mu2[d,d], bu[d,1], mv1[d,d], mv2[d,d], bv[d,1] (rel_dim == dim) */
-    KGE_SME_BL = 17   /* pairwise.py:660-724  same tables as SME; bilinear hidden layer, energy = +gu.gv */
+    KGE_SME_BL = 17,  /* pairwise.py:660-724  same tables as SME; bilinear hidden layer, energy = +gu.gv */
+    KGE_KG2E = 18,    /* pairwise.py:966-1084 ent_mu, ent_sigma, rel_mu, rel_sigma (parameter_list order); KL energy of row-normalised Gaussians */
+    KGE_HOLE = 19     /* pairwise.py:1087-1142 ent, rel; energy = -sigmoid(x), x the legacy-FFT form of DESIGN.md section 9 */
 };
 
 #define KGE_FLAG_L1 1u /* l1_flag of TransE/TransH/TransD (pairwise.py:72-76) */

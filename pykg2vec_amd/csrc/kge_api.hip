@@ -21,7 +21,7 @@ bool is_vector_model(int model) {
     switch (model) {
         case KGE_TRANSE: case KGE_TRANSH: case KGE_TRANSD: case KGE_ROTATE:
         case KGE_DISTMULT: case KGE_COMPLEX: case KGE_ANALOGY:
-        case KGE_TRANSM: case KGE_CP: case KGE_SIMPLE: case KGE_SIMPLE_IGNR: case KGE_QUATE: return true;
+        case KGE_TRANSM: case KGE_CP: case KGE_SIMPLE: case KGE_SIMPLE_IGNR: case KGE_QUATE: case KGE_KG2E: return true;
         default: return false;
     }
 }
@@ -48,7 +48,8 @@ static int table_count(int model) {
         case KGE_TRANSM: case KGE_CP: case KGE_TRANSR: return 3;
         case KGE_SIMPLE: case KGE_SIMPLE_IGNR: return 4;
         case KGE_QUATE: case KGE_SME: case KGE_SME_BL: return 8;
-        case KGE_SLM: return 4;
+        case KGE_SLM: case KGE_KG2E: return 4;
+        case KGE_HOLE: return 2;
     }
     return -1;
 }
@@ -129,6 +130,7 @@ int kge_score_forward(const kge_model_desc* m, const int64_t* h, const int64_t* 
     if (m->model == KGE_NTN) return launch_ntn_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     if (m->model == KGE_TRANSR) return launch_transr_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     if (is_semantic_model(m->model)) return launch_semantic_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
+    if (m->model == KGE_HOLE) return launch_hole_forward(m, h, r, t, n, scores, s);
     return launch_score_forward(m, h, r, t, n, scores, s);
 }
 
@@ -143,6 +145,7 @@ int kge_score_backward(const kge_model_desc* m, const int64_t* h, const int64_t*
     if (m->model == KGE_NTN) return launch_ntn_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
     if (m->model == KGE_TRANSR) return launch_transr_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
     if (is_semantic_model(m->model)) return launch_semantic_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, s);
+    if (m->model == KGE_HOLE) return launch_hole_backward(m, h, r, t, n, dscore, s);
     return launch_score_backward(m, h, r, t, n, dscore, s);
 }
 
@@ -212,6 +215,11 @@ int kge_train_pairwise_hinge(const kge_model_desc* m, const int64_t* ph, const i
         if ((rc = launch_semantic_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
         if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
         return launch_semantic_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
+    }
+    if (m->model == KGE_HOLE) {   // kge_hole.hip: the same route, no scorer workspace (gws = 0)
+        if ((rc = launch_hole_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, s))) return rc;
+        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
+        return launch_hole_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, s);
     }
     set_error("kge_train_pairwise_hinge: unsupported model %d", m->model);
     return -1;

@@ -94,7 +94,7 @@ __device__ __forceinline__ void store_row(float* __restrict__ row, const float (
 __host__ __device__ constexpr int role_count(int M) {
     return M == KGE_TRANSE ? 3 : M == KGE_TRANSH ? 4 : M == KGE_TRANSD ? 6 : M == KGE_ROTATE ? 5
          : M == KGE_DISTMULT ? 3 : M == KGE_COMPLEX ? 6 : M == KGE_ANALOGY ? 9
-         : M == KGE_TRANSM ? 4 : M == KGE_CP ? 3 : (M == KGE_SIMPLE || M == KGE_SIMPLE_IGNR) ? 6 : M == KGE_QUATE ? 12 : 0;
+         : M == KGE_TRANSM ? 4 : M == KGE_CP ? 3 : (M == KGE_SIMPLE || M == KGE_SIMPLE_IGNR) ? 6 : M == KGE_QUATE ? 12 : M == KGE_KG2E ? 6 : 0;
 }
 __host__ __device__ constexpr int role_tab(int M, int r) {
     switch (M) {
@@ -108,6 +108,7 @@ __host__ __device__ constexpr int role_tab(int M, int r) {
         case KGE_CP: { constexpr int t[3] = {0, 1, 2}; return t[r]; }                   // sub[h], rel[r], obj[t]
         case KGE_SIMPLE: case KGE_SIMPLE_IGNR: { constexpr int t[6] = {0, 0, 2, 3, 1, 1}; return t[r]; }  // h1,h2,r1,r2,t1,t2
         case KGE_QUATE: { constexpr int t[12] = {0, 1, 2, 3, 0, 1, 2, 3, 4, 5, 6, 7}; return t[r]; }      // h sxyz, t sxyz, r sxyz
+        case KGE_KG2E: { constexpr int t[6] = {0, 1, 2, 3, 0, 1}; return t[r]; }       // h mu, h sigma, r mu, r sigma, t mu, t sigma
     }
     return 0;
 }
@@ -123,6 +124,7 @@ __host__ __device__ constexpr int role_sel(int M, int r) {
         case KGE_CP: { constexpr int s[3] = {0, 1, 2}; return s[r]; }
         case KGE_SIMPLE: case KGE_SIMPLE_IGNR: { constexpr int s[6] = {0, 2, 1, 1, 2, 0}; return s[r]; }  // h2 = head[t], t2 = tail[h]
         case KGE_QUATE: { constexpr int s[12] = {0, 0, 0, 0, 2, 2, 2, 2, 1, 1, 1, 1}; return s[r]; }
+        case KGE_KG2E: { constexpr int s[6] = {0, 0, 1, 1, 2, 2}; return s[r]; }
     }
     return 0;
 }
@@ -231,6 +233,7 @@ struct Saved {
     float aux[NCH];        // RotatE: sin(phase)
     float ph, pt, iw;      // projections h.w^ / t.w^ (TransH), h.hm / t.tm (TransD); 1/max(|w|,eps); TransM: theta_r
     bool fw;               // TransH: |w| > eps; SimplE: the clamp passes the gradient
+    float inv[6];          // KG2E: 1 / ||row|| of the six gathered rows (no eps, pairwise.py:1060-1063)
 };
 
 template <int M, int G, int NCH>
@@ -349,6 +352,32 @@ __device__ __forceinline__ float model_fwd(const Rows<M, NCH>& R, const DeviceMo
             p += a * ts + b * tx + c * ty + d * tz;
         }
         return -gsum<G>(p);
+    } else if constexpr (M == KGE_KG2E) {  // pairwise.py:1035-1084: every row divided by its own L2 norm, no eps
+        float n2[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            n2[q] = 0.f;
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) n2[q] = fmaf(R.x[q][i], R.x[q][i], n2[q]);
+        }
+        gsum3<G>(n2[0], n2[1], n2[2]);
+        gsum3<G>(n2[3], n2[4], n2[5]);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) sv.inv[q] = 1.0f / sqrtf(n2[q]);
+        const int gl = threadIdx.x % G;   // padding elements (e >= dim) would be 0/0: they contribute nothing
+        float tr = 0.f, mu = 0.f, dt = 0.f;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            if (i * G + gl >= m.dim) continue;
+            const float hm = R.x[0][i] * sv.inv[0], hs = R.x[1][i] * sv.inv[1], rm = R.x[2][i] * sv.inv[2];
+            const float rs = R.x[3][i] * sv.inv[3], tm = R.x[4][i] * sv.inv[4], ts = R.x[5][i] * sv.inv[5];
+            const float cs = hs + rs, u = tm - (hm + rm);
+            tr += cs / ts;
+            mu += (u * u) / ts;
+            dt += logf(ts) - logf(cs);
+        }
+        gsum3<G>(tr, mu, dt);
+        return ((tr + mu) + dt) - (float)m.dim;
     }
     return 0.f;
 }
@@ -494,6 +523,29 @@ __device__ __forceinline__ void model_bwd(const Rows<M, NCH>& R, const DeviceMod
             Gr.x[10][i] = (gy - py * dot) * inv;
             Gr.x[11][i] = (gz - pz * dot) * inv;
         }
+    } else if constexpr (M == KGE_KG2E) {
+        // d/d(normalised rows), then each through its normalisation: dx = (g - x^ (x^ . g)) / ||x||
+        const int gl = threadIdx.x % G;
+        float dot[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const bool ok = i * G + gl < m.dim;
+            const float hm = R.x[0][i] * sv.inv[0], hs = R.x[1][i] * sv.inv[1], rm = R.x[2][i] * sv.inv[2];
+            const float rs = R.x[3][i] * sv.inv[3], tm = R.x[4][i] * sv.inv[4], ts = R.x[5][i] * sv.inv[5];
+            const float cs = hs + rs, u = tm - (hm + rm);
+            const float gcs = ok ? ds * (1.0f / ts - 1.0f / cs) : 0.f;   // d/d h^s = d/d r^s
+            const float gtm = ok ? ds * (2.0f * u / ts) : 0.f;           // d/d t^m = -d/d h^m = -d/d r^m
+            const float gts = ok ? ds * ((ts - cs - u * u) / (ts * ts)) : 0.f;
+            Gr.x[0][i] = -gtm; Gr.x[1][i] = gcs; Gr.x[2][i] = -gtm; Gr.x[3][i] = gcs; Gr.x[4][i] = gtm; Gr.x[5][i] = gts;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) dot[q] = fmaf(R.x[q][i] * sv.inv[q], Gr.x[q][i], dot[q]);
+        }
+        gsum3<G>(dot[0], dot[1], dot[2]);
+        gsum3<G>(dot[3], dot[4], dot[5]);
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) Gr.x[q][i] = (Gr.x[q][i] - (R.x[q][i] * sv.inv[q]) * dot[q]) * sv.inv[q];
     }
 }
 

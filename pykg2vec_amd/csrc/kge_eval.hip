@@ -94,7 +94,7 @@ static bool make_plan(const kge_model_desc* m, int64_t n, void* ws, EvalPlan* p,
         default: return false;
     }
     p->post = m->model == KGE_TRANSM ? P_SCALE : (m->model == KGE_SIMPLE || m->model == KGE_SIMPLE_IGNR) ? P_CLAMP
-              : m->model == KGE_HEAD_1N_INTERNAL ? P_SIGMOID : P_NONE;
+              : (m->model == KGE_HEAD_1N_INTERNAL || (m->model == KGE_DOT_INTERNAL && (m->flags & kDotSigmoid))) ? P_SIGMOID : P_NONE;
     p->ntiles = (p->E + 63) / 64;
     // the dot-product forms (matrix-core sweep): k padded to whole 16-deep slabs (zeros add nothing to a chain) and one spare 64-candidate
     // tile behind the tables, so that k_eval_gemm's operand loads need neither a k predicate nor an odd-tile-count select (round 6)
@@ -122,6 +122,8 @@ static bool make_plan(const kge_model_desc* m, int64_t n, void* ws, EvalPlan* p,
 size_t eval_workspace_bytes(const kge_model_desc* m, int64_t n, int64_t tables) {
     if (m->model == KGE_NTN) return ntn_eval_workspace_bytes(m, n);
     if (is_semantic_model(m->model)) return semantic_eval_workspace_bytes(m, n);
+    if (m->model == KGE_HOLE) return hole_eval_workspace_bytes(m, n);
+    if (m->model == KGE_KG2E) return kg2e_eval_workspace_bytes(m, n);
     EvalPlan p;
     if (!make_plan(m, n, nullptr, &p, tables)) return 0;
     return p.bytes;
@@ -1772,6 +1774,10 @@ int launch_eval_ranks(const kge_model_desc* m, const int64_t* triples, int64_t n
     }
     if (is_semantic_model(m->model))
         return launch_semantic_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
+    if (m->model == KGE_HOLE)
+        return launch_hole_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
+    if (m->model == KGE_KG2E)
+        return launch_kg2e_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
     return run_pipeline(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s);
 }
 
@@ -1831,28 +1837,33 @@ int launch_eval_sweep_scores(const kge_model_desc* m, const int64_t* triples, in
     }
     if (is_semantic_model(m->model))
         return launch_semantic_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
+    if (m->model == KGE_HOLE)
+        return launch_hole_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
+    if (m->model == KGE_KG2E)
+        return launch_kg2e_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
     return run_pipeline(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
 }
 
-static kge_model_desc dot_desc(const float* cand, const float* q, int K, int64_t E) {
+static kge_model_desc dot_desc(const float* cand, const float* q, int K, int64_t E, bool sigmoid) {
     kge_model_desc m;
     memset(&m, 0, sizeof(m));
     m.model = KGE_DOT_INTERNAL;
+    m.flags = sigmoid ? kDotSigmoid : 0u;
     m.tot_entity = E; m.tot_relation = 1; m.dim = K; m.rel_dim = K;
     m.tables[0] = const_cast<float*>(cand); m.tables[2] = const_cast<float*>(q);
     return m;
 }
 
-size_t dot_eval_workspace_bytes(int64_t n, int K, int64_t E) {
-    const kge_model_desc m = dot_desc(nullptr, nullptr, K, E);
+size_t dot_eval_workspace_bytes(int64_t n, int K, int64_t E, bool sigmoid) {
+    const kge_model_desc m = dot_desc(nullptr, nullptr, K, E, sigmoid);
     EvalPlan p;
     return make_plan(&m, n, nullptr, &p) ? p.bytes : 0;
 }
 
 int launch_dot_eval(const float* cand, const float* q, int K, int64_t E, const int64_t* triples, int64_t n, const int64_t* tail_off,
                     const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes,
-                    int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side) {
-    const kge_model_desc m = dot_desc(cand, q, K, E);
+                    int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side, bool sigmoid) {
+    const kge_model_desc m = dot_desc(cand, q, K, E, sigmoid);
     return run_pipeline(&m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, scores, s, side);
 }
 

@@ -17,7 +17,7 @@
 namespace kge {
 
 void set_error(const char* fmt, ...);
-bool is_vector_model(int model);  // models handled by the gather/row kernels (everything but RESCAL, NTN, TransR, SLM, SME)
+bool is_vector_model(int model);  // models handled by the gather/row kernels (everything but RESCAL, NTN, TransR, SLM, SME, HoLE)
 
 // (G, NCH) geometry for a row length; returns false when the row is too long for the register-resident kernels
 struct Geometry { int G, NCH; };
@@ -275,12 +275,33 @@ int launch_rank_from_scores(const float* scores, int64_t nq, int64_t E, const in
 
 // Plain negated-dot sweep over caller-built rows (the SME / SME_BL rank): a pseudo-model, internal to the library, whose
 // candidate table is cand [E, K] and whose query rows are q [n, 2, K] (row 2i = tail sweep of triple i, 2i + 1 = head sweep);
-// energy = -(q . cand).  tables[0] = cand, tables[2] = q, dim = K.
+// energy = -(q . cand), or -sigmoid(q . cand) with `sigmoid` (HoLE).  tables[0] = cand, tables[2] = q, dim = K.
 constexpr int KGE_DOT_INTERNAL = 101;
-size_t dot_eval_workspace_bytes(int64_t n, int K, int64_t E);
+constexpr uint32_t kDotSigmoid = 1u << 8;   // flags bit of the KGE_DOT_INTERNAL descriptor: the P_SIGMOID post-op
+size_t dot_eval_workspace_bytes(int64_t n, int K, int64_t E, bool sigmoid = false);
 int launch_dot_eval(const float* cand, const float* q, int K, int64_t E, const int64_t* triples, int64_t n, const int64_t* tail_off,
                     const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes,
-                    int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side);
+                    int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side, bool sigmoid = false);
+
+// kge_hole.hip (HoLE)
+int launch_hole_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
+                        hipStream_t s);
+int launch_hole_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
+                         const float* dscore, hipStream_t s);
+int launch_hole_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                             const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, hipStream_t s);
+int launch_hole_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                              const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, hipStream_t s);
+size_t hole_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
+int launch_hole_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                     const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
+                     float* scores, hipStream_t s, int side);
+
+// kge_kg2e_eval.hip (KG2E rank)
+size_t kg2e_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
+int launch_kg2e_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                     const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
+                     float* scores, hipStream_t s, int side);
 
 // kge_semantic.hip (SLM / SME / SME_BL)
 size_t semantic_workspace_bytes(const kge_model_desc* m, int64_t n);

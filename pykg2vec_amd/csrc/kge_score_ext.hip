@@ -1,7 +1,7 @@
 // kge_score_ext.hip -- the generic row kernels (kge_row_kernels.h) instantiated for the second group of
 // gather-type models: TransM (pairwise.py:281-365), CP (pointwise.py:320-387), SimplE / SimplE_ignr
-// (pointwise.py:461-592) and QuatE (pointwise.py:595-768).  Pairwise kernels for the pairwise model, pointwise kernels
-// for the pointwise models (the reference trains each family with its own loss only, utils/trainer.py:147-180).
+// (pointwise.py:461-592), QuatE (pointwise.py:595-768) and KG2E (pairwise.py:966-1084).  Pairwise kernels for the pairwise
+// models, pointwise kernels for the pointwise models (the reference trains each family with its own loss only, utils/trainer.py:147-180).
 // Same roofline as kge_score.hip: row gather + atomic scatter, HBM/L2-bound.
 #include "kge_row_kernels.h"
 
@@ -10,6 +10,7 @@ namespace kge {
 #define KGE_DISPATCH_PAIRWISE(model_id, BODY)                   \
     switch (model_id) {                                         \
         KGE_FOR_MODEL(KGE_TRANSM, BODY)                         \
+        KGE_FOR_MODEL(KGE_KG2E, BODY)                           \
         default: break;                                         \
     }
 #define KGE_DISPATCH_POINTWISE(model_id, BODY)                  \
@@ -27,6 +28,7 @@ namespace kge {
         KGE_FOR_MODEL(KGE_SIMPLE, BODY)                         \
         KGE_FOR_MODEL(KGE_SIMPLE_IGNR, BODY)                    \
         KGE_FOR_MODEL(KGE_QUATE, BODY)                          \
+        KGE_FOR_MODEL(KGE_KG2E, BODY)                           \
         default: break;                                         \
     }
 

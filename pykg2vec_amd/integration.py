@@ -10,7 +10,8 @@ drop-in models, generator and evaluator.
 """
 import types
 
-PAIRWISE = ("TransE", "TransH", "TransD", "TransM", "TransR", "RotatE", "Rescal", "NTN", "SLM", "SME", "SME_BL")
+PAIRWISE = ("TransE", "TransH", "TransD", "TransM", "TransR", "RotatE", "Rescal", "NTN", "SLM", "SME", "SME_BL", "KG2E",
+            "HoLE")
 POINTWISE = ("DistMult", "Complex", "ComplexN3", "ANALOGY", "CP", "SimplE", "SimplE_ignr", "QuatE")
 
 

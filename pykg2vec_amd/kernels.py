@@ -14,7 +14,7 @@ from . import _lib as L
 MODEL_IDS = {"transe": L.TRANSE, "transh": L.TRANSH, "transd": L.TRANSD, "rotate": L.ROTATE, "rescal": L.RESCAL,
              "ntn": L.NTN, "distmult": L.DISTMULT, "complex": L.COMPLEX, "complexn3": L.COMPLEX, "analogy": L.ANALOGY,
              "transm": L.TRANSM, "cp": L.CP, "simple": L.SIMPLE, "simple_ignr": L.SIMPLE_IGNR, "quate": L.QUATE,
-             "transr": L.TRANSR, "slm": L.SLM, "sme": L.SME, "sme_bl": L.SME_BL}
+             "transr": L.TRANSR, "slm": L.SLM, "sme": L.SME, "sme_bl": L.SME_BL, "kg2e": L.KG2E, "hole": L.HOLE}
 OPTIMIZER_IDS = {"sgd": L.OPT_SGD, "adam": L.OPT_ADAM, "adagrad": L.OPT_ADAGRAD, "rms": L.OPT_RMSPROP,
                  "gradient": 4}   # KGE_OPT_GRADIENT: kge_pull_step writes the dense gradient instead of updating
 
@@ -54,6 +54,8 @@ _TABLE_SHAPES = {
     "slm": [("E", "d"), ("R", "k"), ("d", "k"), ("d", "k")],
     "sme": [("E", "d"), ("R", "d"), ("d", "d"), ("d", "d"), ("d", 1), ("d", "d"), ("d", "d"), ("d", 1)],
     "sme_bl": [("E", "d"), ("R", "d"), ("d", "d"), ("d", "d"), ("d", 1), ("d", "d"), ("d", "d"), ("d", 1)],
+    "kg2e": [("E", "d"), ("E", "d"), ("R", "d"), ("R", "d")],
+    "hole": [("E", "d"), ("R", "d")],
     "distmult": [("E", "d"), ("R", "d")],
     "complex": [("E", "d"), ("E", "d"), ("R", "d"), ("R", "d")],
     "complexn3": [("E", "d"), ("E", "d"), ("R", "d"), ("R", "d")],

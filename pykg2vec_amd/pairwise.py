@@ -292,3 +292,61 @@ class SME_BL(SME):
         super().__init__(**kwargs)
         self.model_name = self.__class__.__name__.lower()
         self.loss = Criterion.pairwise_hinge
+
+
+class KG2E(PairwiseModel):
+    """pairwise.py:966-1084.  Diagonal Gaussians, KL energy over the six gathered rows, each divided by its own L2 norm (no
+    eps: get_normalized_data):  cs = h^s + r^s, cm = h^m + r^m,
+        energy = sum cs / t^s + sum (t^m - cm)^2 / t^s + sum (log t^s - log cs) - d.
+    The sigma tables start at max(cmin, min(cmax, xavier + 1)) as in the reference; with its default (swapped) cmax = 0.05,
+    cmin = 5.0 every entry starts at 5.0.  A non-positive normalised sigma entry gives NaN, as in the reference."""
+    kernel_name = "kg2e"
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "hidden_size", "cmax", "cmin"], kwargs))
+        d = self.hidden_size
+        self.ent_embeddings_mu = NamedEmbedding("ent_embeddings_mu", self.tot_entity, d)
+        self.rel_embeddings_mu = NamedEmbedding("rel_embeddings_mu", self.tot_relation, d)
+        self.ent_embeddings_sigma = NamedEmbedding("ent_embeddings_sigma", self.tot_entity, d)
+        self.rel_embeddings_sigma = NamedEmbedding("rel_embeddings_sigma", self.tot_relation, d)
+        _xavier(self.ent_embeddings_mu, self.rel_embeddings_mu, self.ent_embeddings_sigma, self.rel_embeddings_sigma)
+        self.parameter_list = [self.ent_embeddings_mu, self.ent_embeddings_sigma, self.rel_embeddings_mu,
+                               self.rel_embeddings_sigma]
+        with torch.no_grad():   # the reference's clip, elementwise in float32: max(cmin, min(cmax, sigma + 1))
+            for e in (self.ent_embeddings_sigma, self.rel_embeddings_sigma):
+                w = e.weight
+                w.copy_(torch.max(torch.full_like(w, self.cmin), torch.min(torch.full_like(w, self.cmax), w + 1.0)))
+        self.loss = Criterion.pairwise_hinge
+
+    def desc_kwargs(self):
+        return dict(dim=self.hidden_size)
+
+    def embed(self, h, r, t):
+        """The reference's 6-tuple (h_mu, h_sigma, r_mu, r_sigma, t_mu, t_sigma), every row divided by its L2 norm."""
+        nz = lambda x: x.div(torch.norm(x, 2, 1).view(-1, 1).expand_as(x))
+        return (nz(self.ent_embeddings_mu(h)), nz(self.ent_embeddings_sigma(h)), nz(self.rel_embeddings_mu(r)),
+                nz(self.rel_embeddings_sigma(r)), nz(self.ent_embeddings_mu(t)), nz(self.ent_embeddings_sigma(t)))
+
+
+class HoLE(PairwiseModel):
+    """pairwise.py:1087-1142, with the semantics it shipped with (torch < 1.7: torch.fft on real [..., 2] tensors, torch.conj
+    the identity on them, `*` elementwise on real and imaginary parts).  With C[j,k] = cos(2 pi jk/d), S[j,k] = sin(2 pi jk/d):
+        x = (1/d) sum_k [(C h)_k (C t)_k (C r^)_k - (S h)_k (S t)_k (S r^)_k],   energy = -sigmoid(x),   r^ = F.normalize(r).
+    This is not circular correlation; it is what existing HoLE checkpoints were trained with."""
+    kernel_name = "hole"
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "hidden_size", "cmax", "cmin"], kwargs))
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, self.hidden_size)
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation, self.hidden_size)
+        _xavier(self.ent_embeddings, self.rel_embeddings)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings]
+        self.loss = Criterion.pairwise_hinge
+
+    def desc_kwargs(self):
+        return dict(dim=self.hidden_size)
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
