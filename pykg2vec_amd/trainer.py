@@ -769,13 +769,14 @@ class Trainer:
             ent = self.flat.views[0]
             st = self._rescal_stage = K.RescalStage(ent.shape[0], max(n_pairs, int(self.config.batch_size)), ent.shape[1], ent.device)
             self._graph = None     # (captured steps hold the old buffers' addresses)
-            self._report_rescal_reproducibility()
+            self._report_rescal_reproducibility()   # (reached at neg_rate 1 only: hinge steps refuse neg_rate > 1, kernels.train_pairwise_hinge)
         return st
 
     RESCAL_CHUNK_PAIRS = 64      # pairs of one relation a slab workgroup takes (csrc/kge_relgroup.h: kSlabChunk)
 
     def _report_rescal_reproducibility(self):
-        """The staged RESCAL step is bit-reproducible while no relation has more than 64 pairs in a batch: a longer relation spans
+        """The staged RESCAL step is bit-reproducible while no relation has more than 64 pairs in a batch (a pair is a positive and one
+        of its neg_rate negatives, which keep the positive's relation: a relation with c positives has c * neg_rate pairs): a longer relation spans
         several chunks, whose shares of the relation-matrix gradient meet in float atomics (and its pairs keep their arrival order in
         the grouping).  Batches are fixed slices of one permutation, so which side of that line a run is on is known up front: computed
         once (one bincount over the epoch order), exposed as `rescal_reproducible`, and said out loud when False (hub
@@ -792,10 +793,11 @@ class Trainer:
             return
         rel = gen.triples[gen.perm[:n], 1]
         key = (torch.arange(n, device=rel.device) // B) * R + rel
-        worst = int(torch.bincount(key, minlength=nb * R).max().item())
+        # the slab step groups the B * neg_rate pairs it is handed, and every negative keeps its positive's relation
+        worst = int(torch.bincount(key, minlength=nb * R).max().item()) * max(1, int(getattr(self.config, "neg_rate", 1) or 1))
         self.rescal_reproducible = worst <= self.RESCAL_CHUNK_PAIRS
         if not self.rescal_reproducible:
-            _log("RESCAL staged step: a relation occurs %d times in one batch of %d (> %d): its share of the relation-matrix gradient is "
+            _log("RESCAL staged step: a relation has %d pairs in one batch of %d (> %d): its share of the relation-matrix gradient is "
                  "summed with float atomics -- results are equal to rounding, not bit-reproducible, on this graph" % (worst, B, self.RESCAL_CHUNK_PAIRS))
 
     def _mean_type_loss(self):

@@ -61,6 +61,32 @@ def close(a, b, atol=ATOL, rtol=RTOL):
     return np.allclose(a, b, atol=atol, rtol=rtol)
 
 
+# ---- heavy-tailed ids.  Uniform draws give every C1 entity row ~4 incidences per batch; real graphs put thousands on a few hubs,
+# which is where the owner-computes steps split rows over several work items, walk overflow chains and pre-reduce relation lists.
+def zipf_ids(rng, n, N, s, perm=None):
+    """n ids of range(N) with p(rank k) proportional to (k + 1)^-s (a finite Zipf law).  The ranks are mapped through `perm`, by
+    default a permutation drawn from rng, so the hubs are not ids 0, 1, 2..."""
+    if perm is None:
+        perm = rng.permutation(N)
+    p = np.arange(1, N + 1, dtype=np.float64) ** -float(s)
+    return np.asarray(perm, dtype=np.int64)[rng.choice(N, size=n, p=p / p.sum())]
+
+
+def harmonic(N, s):
+    """H(N, s) = sum_{k=1..N} k^-s: the heaviest id of zipf_ids(.., N, s) is drawn with probability 1 / H(N, s)."""
+    return float(np.sum(np.arange(1, N + 1, dtype=np.float64) ** -float(s)))
+
+
+def skewed_triples(rng, n, E, R, s_ent=0.9, s_rel=1.0):
+    """n int64 triples (h, r, t): heads and tails Zipf(s_ent) over ONE entity permutation (a hub is heavy on both sides),
+    relations Zipf(s_rel)."""
+    ent_perm = rng.permutation(E)
+    h = zipf_ids(rng, n, E, s_ent, ent_perm)
+    r = zipf_ids(rng, n, R, s_rel)
+    t = zipf_ids(rng, n, E, s_ent, ent_perm)
+    return np.stack([h, r, t], 1)
+
+
 # ---- BASELINE.json configs at FULL table size, frozen from the live reference (oracle/make_golden_fullsize.py).
 # Only seeds and outputs are stored: tables and triples are re-created from the seed on either box (numpy Generator
 # streams of the same numpy build), so the fixtures stay small.
@@ -82,14 +108,41 @@ FULLSIZE = {
 }
 
 
+# the same configs on heavy-tailed ids (`skew` = (s_ent, s_rel): Zipf exponents of entities / relations over one seeded permutation
+# each, shared by every split).  Step fixtures only (DEFAULT_STEP): no forward / rank fixtures exist for them.
+FULLSIZE_SKEWED = {
+    "%s_zipf" % base: dict(FULLSIZE[base], seed=seed, skew=(0.9, 1.0))
+    for base, seed in (("c1_transe_l1", 9111), ("c2_complex", 9113), ("c3_rotate", 9114), ("c4_rescal", 9115))}
+HEAVY_ENT_ROWS, HEAVY_REL_ROWS = 16, 8      # heaviest rows of a skewed step batch that its fixture lists in full
+
+
+def heavy_step_rows(pos, nh, nr, nt, E, R):
+    """(entity rows, relation rows): the HEAVY_ENT_ROWS / HEAVY_REL_ROWS rows of a step batch with the most incidences (heads and
+    tails of positives and negatives; relations of both), ties by id."""
+    ent = np.bincount(np.concatenate([pos[:, 0], pos[:, 2], nh, nt]), minlength=E)
+    rel = np.bincount(np.concatenate([pos[:, 1], nr]), minlength=R)
+    return (np.lexsort((np.arange(E), -ent))[:HEAVY_ENT_ROWS].astype(np.int64),
+            np.lexsort((np.arange(R), -rel))[:HEAVY_REL_ROWS].astype(np.int64))
+
+
+def fullsize_spec(name):
+    return FULLSIZE[name] if name in FULLSIZE else FULLSIZE_SKEWED[name]
+
+
 def fullsize_inputs(name):
-    """Deterministic inputs of a FULLSIZE case: (spec, params, train, valid, test, score_ids, step_batch)."""
+    """Deterministic inputs of a FULLSIZE / FULLSIZE_SKEWED case: (spec, params, train, valid, test, score_ids, step_batch)."""
     import kge_oracle as ko
-    spec = FULLSIZE[name]
+    spec = fullsize_spec(name)
     rng = np.random.default_rng(spec["seed"])
     E, R = spec["E"], spec["R"]
+    skew = spec.get("skew")
+    if skew is not None:
+        ent_perm, rel_perm = rng.permutation(E), rng.permutation(R)
 
     def draw(n):
+        if skew is not None:
+            return np.stack([zipf_ids(rng, n, E, skew[0], ent_perm), zipf_ids(rng, n, R, skew[1], rel_perm),
+                             zipf_ids(rng, n, E, skew[0], ent_perm)], 1)
         return np.stack([rng.integers(E, size=n), rng.integers(R, size=n), rng.integers(E, size=n)], 1).astype(np.int64)
 
     train, valid, test = (draw(n) for n in spec["splits"])
@@ -173,6 +226,10 @@ DEFAULT_STEP = {
     "c2_complex": dict(B=5000, optimizer="adagrad", lr=0.01),
     "c3_rotate": dict(B=1024, optimizer="adam", lr=0.01),
     "c4_rescal": dict(B=1024, optimizer="adam", lr=0.01),
+    "c1_transe_l1_zipf": dict(B=32768, optimizer="adam", lr=0.01),
+    "c2_complex_zipf": dict(B=5000, optimizer="adagrad", lr=0.01),
+    "c3_rotate_zipf": dict(B=1024, optimizer="adam", lr=0.01),
+    "c4_rescal_zipf": dict(B=1024, optimizer="adam", lr=0.01),
 }
 GENERATOR_SEED = 0
 

@@ -175,6 +175,12 @@ GRAD_FLOOR_REL = 1e-4  # the first Adam / Adagrad step is p -= lr * g / (|g| + e
                        # of that) may step the other way.  Such elements are held to |delta p| <= 2 lr and counted in the report.
 UPDATED_ROW_ATOL = {}                      # (round 4: {"c4_rescal": 5e-7} -- RESCAL's entity gradients were float atomics; round 5 stages them
                                            #  per (pair, side) and sums them in slot order: C4's default path is deterministic like the others)
+UPDATED_ROW_ATOL["c4_rescal_zipf"] = 2e-7  # Zipf relations span several 64-pair slab chunks, whose relation-matrix shares meet in float atomics;
+                                           # measured 8.9e-8 (entity rows) / 7.4e-8 (relation matrices): Adam's first step is ~lr sign(g), so
+                                           # the atomics' rounding barely reaches the tables.  2x that, below round 4's atomic 5e-7
+# Zipf relations of C2 sum ~2 600 cancelling logistic terms per row (the uniform case ~900): Adagrad's squared state of those rows sits at
+# 8.5e-5 of the state's scale (measured); the element-wise floor of that case is 2e-4 of the scale (the oracle test's state_rtol)
+STATE_FLOOR = {"c2_complex_zipf": 2e-4}
 UPDATED_ROW_ATOL_DET = 2e-7                # every default path sums in a fixed order: 2x the largest deviation observed (profiles/r05_step_agreement_fullsize.json: 9e-8)
 
 
@@ -211,7 +217,7 @@ def check_step_against_reference(name, loss, tables, state1, state2, report, los
         dp = np.abs(got_rows - ref_rows)
         untouched = ~np.any(ref_s1 != 0, axis=1)
         # rows nobody touched: bit-identical -- except RESCAL, whose forward renormalises every row (same value to rounding)
-        if name == "c4_rescal":
+        if name.startswith("c4_rescal"):
             assert np.all(dp[untouched] <= 2e-6), (key, "untouched rows", float(dp[untouched].max()))
         else:
             assert np.array_equal(got_rows[untouched], ref_rows[untouched]), (key, "untouched rows moved")
@@ -220,7 +226,7 @@ def check_step_against_reference(name, loss, tables, state1, state2, report, los
         # table's largest gradient element) shifts it by at most lr * e / |g|, which matters only for the smallest elements
         gmax = max(float(g.max()), 1e-30)
         tol_solid = (row_atol if row_atol is not None else UPDATED_ROW_ATOL.get(name, UPDATED_ROW_ATOL_DET)) + lr * 1e-6 * gmax / np.maximum(g, 1e-30)
-        tol_solid = np.where(untouched[:, None], 2e-6 if name == "c4_rescal" else 0.0, tol_solid)
+        tol_solid = np.where(untouched[:, None], 2e-6 if name.startswith("c4_rescal") else 0.0, tol_solid)
         assert np.all(dp[solid] <= tol_solid[solid]), (key, "post rows", float((dp - tol_solid)[solid].max()))
         assert np.all(dp[~solid] <= 2.0 * lr * 1.001 + 1e-6), (key, "noise-gradient elements", float(dp[~solid].max()))
         # digests over ALL rows of the gradient-carrying state
@@ -289,8 +295,10 @@ def test_hip_default_path_step_matches_reference_at_full_size(name):
     torch.cuda.synchronize()
     path = ("hipGraph" if tr._graph is not None else "staged" if getattr(tr, "_staged", None) is not None else
             "own" if getattr(tr, "_own", None) is not None else "pull" if getattr(tr, "_pull", None) is not None else "eager")
-    want = {"c1_transe_l1": "pull", "c1_transe_l2": "pull", "c2_complex": "own", "c3_rotate": "staged", "c4_rescal": "hipGraph"}[name]
+    want = {"c1_transe_l1": "pull", "c1_transe_l2": "pull", "c2_complex": "own", "c3_rotate": "staged", "c4_rescal": "hipGraph"}[name.replace("_zipf", "")]
     assert path == want, (name, path)
+    if name == "c4_rescal_zipf":   # hub relations of several 64-pair chunks: float atomics on the relation-matrix gradient, and said so
+        assert tr.rescal_reproducible is False
     flat = tr.flat
     named = hip_util.table_parameters(m)
     off = [v.data_ptr() - flat.param.data_ptr() for v in flat.views]
@@ -305,7 +313,8 @@ def test_hip_default_path_step_matches_reference_at_full_size(name):
     # round 6 ratchet: ~3x the largest deviations on record (profiles/r05_step_agreement_fullsize.json,
     # r06_step_agreement_fullsize.json) -- loss 1.2e-7 relative, row digests of the optimiser state 3.2e-6 relative; the element-wise
     # floor stays at 5e-5 of the state's scale: C2's relation rows (Adagrad: SQUARED sums of ~900 cancelling terms) sit at 2.4e-5
-    rep = check_step_against_reference(name, loss, tables, s1, s2, doc, loss_rtol=5e-7, state_rtol=1e-5, state_floor=5e-5, state2_rtol=1e-4)
+    rep = check_step_against_reference(name, loss, tables, s1, s2, doc, loss_rtol=5e-7, state_rtol=1e-5, state_floor=STATE_FLOOR.get(name, 5e-5),
+                                       state2_rtol=1e-4)
     rep["path"] = path + (", two-phase" if path == "pull" and tr._pull.direction is not None else "")
     json.dump(doc, open(fn, "w"), indent=1)
 

@@ -258,23 +258,54 @@ def test_gradient_mode_equals_the_atomic_gradient(hip, world, l1, monkeypatch):
 def test_device_built_index_equals_the_numpy_one(hip, E, R, B, nb, seg, gpb, compact, slice_):
     """csrc/kge_index.hip (kge_pull_index_build: keys -> batched bitonic sorts -> row list -> placement) against
     generator.build_pull_batch, the numpy statement of the same layout rule: identical arrays for every batch."""
-    from pykg2vec_amd import kernels as K
-    from pykg2vec_amd.generator import PullIndex
     rng = np.random.default_rng(E * 31 + B)
     n_train = nb * B + 17
     train = np.stack([rng.integers(E, size=n_train), rng.integers(R, size=n_train), rng.integers(E, size=n_train)], 1)
     perm = rng.permutation(n_train)
+    _device_index_equals_host_index(hip, train, perm, E, R, B, nb, seg, gpb, compact, slice_)
+
+
+@pytest.mark.parametrize("E,R,B,nb,seg,gpb,compact,draw", [
+    (14951, 1345, 32768, 2, 8, 8, None, "zipf"),    # C1 sizes, Zipf(0.9) entities / Zipf(1.0) relations: hubs of thousands
+    (14951, 1345, 32768, 2, 8, 8, True, "zipf"),
+    (14951, 1345, 4096, 2, 1, 8, None, "hub"),      # one entity holds over half of every batch's incidences
+    (14951, 1345, 4096, 2, 8, 8, None, "hub"),
+    (14951, 1345, 4096, 2, 8, 8, True, "hub"),
+    (14951, 1345, 4096, 2, 1, 8, True, "hub")])
+def test_device_built_index_equals_the_numpy_one_on_skewed_ids(hip, E, R, B, nb, seg, gpb, compact, draw):
+    """The same comparison on heavy-tailed batches: hub rows are cut into hundreds to thousands of items and listed in `multi`."""
+    from golden_util import skewed_triples
+    rng = np.random.default_rng(E * 37 + B + seg)
+    n_train = nb * B + 17
+    if draw == "zipf":
+        train = skewed_triples(rng, n_train, E, R)
+    else:
+        train = np.stack([rng.integers(E, size=n_train), rng.integers(R, size=n_train), rng.integers(E, size=n_train)], 1)
+        train[:, 0] = 4321
+        train[rng.random(n_train) < 0.55, 2] = 4321
+    perm = rng.permutation(n_train)
+    multi = _device_index_equals_host_index(hip, train, perm, E, R, B, nb, seg, gpb, compact, None)
+    assert multi > 0
+
+
+def _device_index_equals_host_index(hip, train, perm, E, R, B, nb, seg, gpb, compact, slice_):
+    """Both builders on batches b = train[perm[b * B + lo : b * B + lo + n]]: identical arrays; returns the rows listed in `multi`."""
+    from pykg2vec_amd import kernels as K
+    from pykg2vec_amd.generator import PullIndex
     lo, n = slice_ if slice_ is not None else (0, B)
     host = PullIndex([train[perm[b * B + lo:b * B + lo + n]] for b in range(nb)], E, R, "cpu", segment=seg, groups_per_block=gpb,
                      compact=compact)
     devx = PullIndex.build_on_device(K, hip.dev(train), hip.dev(perm), nb, B, lo, n, E, R, segment=seg, groups_per_block=gpb,
                                      compact=compact)
     assert devx.compact == host.compact and devx.max_slots == host.max_slots and devx.n_batches == nb and devx.batch_size == n
+    n_multi = 0
     for b in range(nb):
         for name, a, d in zip(("pairs", "inc", "items", "multi"), host.batch(b), devx.batch(b)):
             a, d = a.numpy(), d.cpu().numpy()
             assert a.shape == d.shape, (b, name, a.shape, d.shape)
             assert np.array_equal(a, d), (b, name, np.flatnonzero((a != d).reshape(len(a), -1).any(1))[:8])
+        n_multi += len(host.batch(b)[3])
         assert np.array_equal(host.inv(b).numpy(), devx.inv(b).cpu().numpy())
         if host.compact:
             assert np.array_equal(host.skip(b).numpy(), devx.skip(b).cpu().numpy())
+    return n_multi

@@ -425,6 +425,123 @@ def test_pull_index_structure(E, R, B, seg, gpb):
     assert n_partial == nglob
 
 
+def test_zipf_ids_are_seeded_and_heavy_tailed():
+    """golden_util.zipf_ids / skewed_triples, the skewed-id source of the skew tests: reproducible from the seed, the heaviest id
+    drawn with probability ~1 / H(N, s), hubs not at ids 0, 1, 2..., and at C1's sizes the top entity of a B = 32 768 batch has more
+    incidences than one owner group has lanes (32)."""
+    from golden_util import harmonic, skewed_triples, zipf_ids
+    a = skewed_triples(np.random.default_rng(3), 50000, 14951, 1345)
+    b = skewed_triples(np.random.default_rng(3), 50000, 14951, 1345)
+    assert a.dtype == np.int64 and a.shape == (50000, 3) and np.array_equal(a, b)
+    assert not np.array_equal(a, skewed_triples(np.random.default_rng(4), 50000, 14951, 1345))
+    assert a[:, [0, 2]].min() >= 0 and a[:, [0, 2]].max() < 14951 and a[:, 1].min() >= 0 and a[:, 1].max() < 1345
+    R, n = 37, 200000
+    r = zipf_ids(np.random.default_rng(5), n, R, 1.0)
+    share = np.bincount(r, minlength=R).max() / n
+    assert abs(share - 1.0 / harmonic(R, 1.0)) < 0.01, (share, 1.0 / harmonic(R, 1.0))
+    p = np.random.default_rng(6).permutation(R)
+    assert p[0] != 0 and np.argmax(np.bincount(zipf_ids(np.random.default_rng(5), n, R, 1.0, perm=p), minlength=R)) == p[0]
+    pos = skewed_triples(np.random.default_rng(7), 32768, 14951, 1345)
+    ent = np.bincount(np.concatenate([pos[:, 0], pos[:, 2]]), minlength=14951)
+    assert ent.max() > 32, ent.max()
+    assert np.bincount(pos[:, 1], minlength=1345).max() > 32
+    # heads and tails share their hubs (one entity permutation)
+    assert np.argmax(np.bincount(pos[:, 0], minlength=14951)) == np.argmax(np.bincount(pos[:, 2], minlength=14951))
+
+
+def _hub_batch(rng, E, R, B):
+    """A batch in which ONE entity holds more than half of all 3 B incidences (every head, half of the tails)."""
+    pos = np.stack([rng.integers(E, size=B), rng.integers(R, size=B), rng.integers(E, size=B)], 1)
+    hub = int(rng.integers(E))
+    pos[:, 0] = hub
+    pos[: B // 2, 2] = hub
+    return pos
+
+
+@pytest.mark.parametrize("E,R,B,seg,gpb,compact,kind", [
+    (14951, 1345, 32768, 8, 8, False, "zipf"),     # C1 sizes: thousands of incidences on the hub rows
+    (14951, 1345, 32768, 32, 8, False, "zipf"),    # the two-phase step's 32-incidence items
+    (14951, 1345, 4096, 8, 8, True, "zipf"),       # compact: touched rows only + bitmap
+    (14951, 1345, 4096, 1, 8, False, "hub"),
+    (14951, 1345, 4096, 8, 8, True, "hub"),
+    (2000, 11, 2048, 2, 4, False, "zipf"),
+    (300, 3, 1000, 1, 16, False, "hub")])
+def test_pull_index_layout_under_skew(E, R, B, seg, gpb, compact, kind):
+    """generator.build_pull_batch on heavy-tailed batches against a plain numpy count per row: every (pair, role) incidence listed
+    once; each row's items tile [beg, beg + count) in order with the kind bits its item count calls for; `multi` lists exactly the rows
+    of more than gpb items, with consecutive partial slots; the partial-slot total is the sum of their item counts."""
+    from golden_util import skewed_triples
+    from pykg2vec_amd.generator import build_pull_batch
+    rng = np.random.default_rng(E + B + seg)
+    pos = skewed_triples(rng, B, E, R) if kind == "zipf" else _hub_batch(rng, E, R, B)
+    out = build_pull_batch(pos, E, R, seg, gpb, compact=compact)
+    pairs, inc, items, multi, nglob = out[:5]
+    nrows = E + R
+    # the plain count: row of every incidence, incidences per row, start of each row's run in the sorted list
+    i = np.arange(B)
+    row_of = {4 * k + role: g for role, col in ((0, 0), (1, 2)) for k, g in zip(i, pos[:, col])}
+    row_of.update({4 * k + 2: E + g for k, g in zip(i, pos[:, 1])})
+    count = np.bincount(np.concatenate([pos[:, 0], pos[:, 2], E + pos[:, 1]]), minlength=nrows)
+    beg = np.concatenate([[0], np.cumsum(count)[:-1]])
+    assert kind != "hub" or count.max() * 2 >= 3 * B
+    assert np.array_equal(np.sort(inc), np.sort(np.fromiter(row_of, dtype=np.int64)))
+    assert np.array_equal(np.asarray([row_of[int(v)] for v in inc]), np.repeat(np.arange(nrows), count))
+    nseg = np.maximum(1, -(-count // seg))
+    live = items[items[:, 0] >= 0]
+    listed = np.flatnonzero(count > 0) if compact else np.arange(nrows)
+    assert np.array_equal(np.unique(live[:, 0]), listed)
+    order = np.lexsort((live[:, 1], live[:, 0]))
+    live = live[order]
+    per_row = np.bincount(live[:, 0], minlength=nrows)
+    assert np.array_equal(per_row[listed], nseg[listed])
+    first = np.concatenate([[0], np.cumsum(per_row[listed])[:-1]])
+    glob = set()
+    for u, g in enumerate(listed):
+        its = live[first[u]:first[u] + nseg[g]]
+        lo = beg[g] + seg * np.arange(nseg[g])
+        assert np.array_equal(its[:, 1], lo) and np.array_equal(its[:, 2], np.minimum(lo + seg, beg[g] + count[g])), g
+        k = its[:, 3] & 3
+        if nseg[g] == 1:
+            assert k[0] == 0, g
+        elif nseg[g] <= gpb:
+            assert (k == 3).all() and np.array_equal((its[:, 3] >> 2) & 15, np.arange(nseg[g])) and ((its[:, 3] >> 6) == nseg[g]).all(), g
+        else:
+            assert k[0] == 1 and (k[1:] == 2).all(), g
+            slots = its[:, 3] >> 2
+            assert np.array_equal(slots, slots[0] + np.arange(nseg[g])), g
+            glob.add(int(g))
+    want_glob = {int(g) for g in listed if nseg[g] > gpb}
+    assert glob == want_glob and len(want_glob) > 0
+    assert sorted(multi[:, 0].tolist()) == sorted(want_glob)
+    assert all(int(n_) == nseg[g] for g, _, n_, _ in multi)
+    assert nglob == int(sum(nseg[g] for g in want_glob))
+    # partial slots of different rows never overlap and fill [0, nglob)
+    taken = np.concatenate([np.arange(o, o + n_) for _, o, n_, _ in multi])
+    assert np.array_equal(np.sort(taken), np.arange(nglob))
+
+
+@pytest.mark.parametrize("neg_rate,R,B,want", [(1, 7, 256, True), (2, 7, 256, False), (1, 3, 256, False), (2, 40, 256, True)])
+def test_rescal_reproducibility_counts_pairs_not_positives(neg_rate, R, B, want):
+    """The staged RESCAL step groups pairs: every negative keeps its positive's relation, so a relation with c positives in a batch
+    has c * neg_rate pairs, and more than 64 of them spread over several chunks that meet in float atomics.  R = 7, B = 256:
+    ~37 positives per relation (one chunk at neg_rate 1), ~73 pairs at neg_rate 2 (not bit-reproducible)."""
+    from pykg2vec_amd.trainer import Trainer
+    rng = np.random.default_rng(R * 10 + neg_rate)
+    n = 4 * B
+    train = np.stack([rng.integers(500, size=n), rng.integers(R, size=n), rng.integers(500, size=n)], 1)
+    perm = rng.permutation(n)
+    worst = max(int(np.bincount(train[perm[lo:lo + B], 1], minlength=R).max()) for lo in range(0, n, B))
+    assert (worst * neg_rate <= 64) == want and (neg_rate == 1 or not want or worst <= 32)
+    if neg_rate == 2 and not want:
+        assert worst <= 64          # every relation fits one chunk by its POSITIVES: only the pair count crosses the line
+    fake = types.SimpleNamespace(generator=types.SimpleNamespace(perm=torch.from_numpy(perm), triples=torch.from_numpy(train),
+                                                                 batch_size=B, n_train=n),
+                                 config=types.SimpleNamespace(tot_relation=R, neg_rate=neg_rate),
+                                 RESCAL_CHUNK_PAIRS=Trainer.RESCAL_CHUNK_PAIRS)
+    Trainer._report_rescal_reproducibility(fake)
+    assert fake.rescal_reproducible is want, (fake.rescal_reproducible, worst, neg_rate)
+
+
 def test_copies_of_a_model_get_their_own_op_handle():
     """torch.ops.kge.score finds its model through an integer handle (pykg2vec_amd/ops.py): deepcopy / pickle must not share it."""
     import copy
