@@ -51,8 +51,17 @@ enum kge_model {
     KGE_SME = 16,     /* pairwise.py:544-657  ent, rel, mu1[d,d], mu2[d,d], bu[d,1], mv1[d,d], mv2[d,d], bv[d,1] (rel_dim == dim) */
     KGE_SME_BL = 17,  /* pairwise.py:660-724  same tables as SME; bilinear hidden layer, energy = +gu.gv */
     KGE_KG2E = 18,    /* pairwise.py:966-1084 ent_mu, ent_sigma, rel_mu, rel_sigma (parameter_list order); KL energy of row-normalised Gaussians */
-    KGE_HOLE = 19     /* pairwise.py:1087-1142 ent, rel; energy = -sigmoid(x), x the legacy-FFT form of DESIGN.md section 9 */
+    KGE_HOLE = 19,    /* pairwise.py:1087-1142 ent, rel; energy = -sigmoid(x), x the legacy-FFT form of DESIGN.md section 9 */
+    KGE_OCTONIONE = 20 /* pointwise.py:772-1001 component blocks (below); energy = -sum(o(h, r / |r|) . t), o the octonion product */
 };
+
+/* Component-block convention of KGE_OCTONIONE.  Its 16 tables (ent_embedding_1..8, rel_embedding_1..8) travel as two blocks:
+ *   tables[0]: entity block; component c (ent_embedding_{c+1}, [E, d]) starts at tables[0] + c * S_E floats, S_E = roundup4(E * d);
+ *   tables[1]: relation block; component c (rel_embedding_{c+1}, [R, d]) starts at tables[1] + c * S_R floats, S_R = roundup4(R * d);
+ *   grads[0] / grads[1]: the same layout.  No other slot is read.
+ * E = tot_entity, R = tot_relation, d = dim, roundup4(x) = (x + 3) & ~3.  This is the layout of segments laid out in parameter_list
+ * order, each rounded up to 4 floats, so one flat parameter buffer holds both blocks without a copy.  rel_w_embedding is never
+ * passed: no kernel reads it and it receives no gradient (its .grad stays None in the reference). */
 
 #define KGE_FLAG_L1 1u /* l1_flag of TransE/TransH/TransD (pairwise.py:72-76) */
 
@@ -88,7 +97,7 @@ const char* kge_last_error(void);
  * Covered: kge_score_forward/backward, kge_train_pairwise_hinge, kge_train_pairwise_selfadv, kge_train_pointwise_logistic,
  * kge_rescal_pair_step, every *_sampled entry point (the batch rows triples[perm[start..start+n)]), kge_sample_batch, kge_corrupt,
  * kge_triple_set_build, kge_pull_index_build (all listed batches: which covers the owner-computes runs built on that index),
- * kge_eval_ranks / _grouped / kge_eval_sweep_scores, kge_rank_from_scores. */
+ * kge_eval_ranks / _grouped / kge_eval_sweep_scores (and _side), kge_rank_from_scores. */
 int kge_set_debug(int32_t check_ids);
 /* A/B switches of the dispatch rules: RESCAL_UNFUSED, RESCAL_ROWS, RESCAL_G, RESCAL_G2, TRANSR_ROWS, TRANSR_G,
  * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an

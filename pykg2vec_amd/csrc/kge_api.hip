@@ -50,6 +50,7 @@ static int table_count(int model) {
         case KGE_QUATE: case KGE_SME: case KGE_SME_BL: return 8;
         case KGE_SLM: case KGE_KG2E: return 4;
         case KGE_HOLE: return 2;
+        case KGE_OCTONIONE: return 2;   // the entity and relation component blocks
     }
     return -1;
 }
@@ -89,6 +90,13 @@ static int validate(const kge_model_desc* m, bool need_grads, const char* who) {
 
 // The train-triple hash set packs a triple into one 64-bit key h:24 | r:16 | t:24 (kge_sampler_device.h): beyond these
 // ranges keys alias and valid negatives would be rejected silently, so every entry point that probes the set refuses.
+// OctonionE has the pointwise-logistic step only (as the reference trains it); the pairwise / staged / owner-computes steps refuse it
+static int refuse_octonione(const kge_model_desc* m, const char* who) {
+    if (m->model != KGE_OCTONIONE) return 0;
+    set_error("%s: OctonionE is trained with the pointwise logistic step only (kge_train_pointwise_logistic / _sampled)", who);
+    return -1;
+}
+
 static int validate_packed_key(const kge_model_desc* m, const char* who) {
     if (m->tot_entity > (1 << 24) || m->tot_relation > (1 << 16)) {
         set_error("%s: the packed train-triple key holds 2^24 entities and 2^16 relations (got %lld / %lld)", who,
@@ -112,7 +120,7 @@ static const int64_t kTransRRowsMinPairs = 1;      // the two-launch step wins a
 
 size_t kge_workspace_bytes(const kge_model_desc* m, int64_t n) {
     if (validate(m, false, "kge_workspace_bytes") || n < 0) return 0;
-    if (is_vector_model(m->model)) return 0;
+    if (is_vector_model(m->model) || m->model == KGE_OCTONIONE) return 0;
     // the pairwise step keeps one scorer workspace per side (positive / negative) plus the two score vectors
     size_t b = 2 * align256(dense_workspace_bytes(m, n)) + align256((size_t)2 * n * sizeof(float));
     if (m->model == KGE_RESCAL) b += rescal_slab_extra_bytes(m, n);   // V rows + energy shares of the slab form of the pairwise step
@@ -131,6 +139,7 @@ int kge_score_forward(const kge_model_desc* m, const int64_t* h, const int64_t* 
     if (m->model == KGE_TRANSR) return launch_transr_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     if (is_semantic_model(m->model)) return launch_semantic_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     if (m->model == KGE_HOLE) return launch_hole_forward(m, h, r, t, n, scores, s);
+    if (m->model == KGE_OCTONIONE) return launch_octonion_forward(m, h, r, t, n, scores, s);
     return launch_score_forward(m, h, r, t, n, scores, s);
 }
 
@@ -146,6 +155,7 @@ int kge_score_backward(const kge_model_desc* m, const int64_t* h, const int64_t*
     if (m->model == KGE_TRANSR) return launch_transr_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
     if (is_semantic_model(m->model)) return launch_semantic_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, s);
     if (m->model == KGE_HOLE) return launch_hole_backward(m, h, r, t, n, dscore, s);
+    if (m->model == KGE_OCTONIONE) return launch_octonion_backward(m, h, r, t, n, dscore, s);
     return launch_score_backward(m, h, r, t, n, dscore, s);
 }
 
@@ -168,7 +178,7 @@ int kge_rescal_normalize_ws(float* ent, int64_t tot_entity, float* rel, int64_t 
 int kge_train_pairwise_hinge(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
                              const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, float margin,
                              void* workspace, size_t workspace_bytes, float* loss, void* stream) {
-    if (validate(m, true, "kge_train_pairwise_hinge")) return -1;
+    if (validate(m, true, "kge_train_pairwise_hinge") || refuse_octonione(m, "kge_train_pairwise_hinge")) return -1;
     if (n == 0) return 0;
     if (n < 0 || !ph || !pr || !pt || !nh || !nr || !nt || !loss) { set_error("kge_train_pairwise_hinge: bad arguments"); return -1; }
     hipStream_t s = (hipStream_t)stream;
@@ -229,7 +239,7 @@ int kge_train_pairwise_hinge_sampled(const kge_model_desc* m, const int64_t* tri
                                      int64_t n, const float* bern_prob, const uint64_t* slots, int64_t n_slots,
                                      uint64_t seed, uint64_t offset, const int64_t* dev_cursor, float margin, float* loss,
                                      void* stream) {
-    if (validate(m, true, "kge_train_pairwise_hinge_sampled")) return -1;
+    if (validate(m, true, "kge_train_pairwise_hinge_sampled") || refuse_octonione(m, "kge_train_pairwise_hinge_sampled")) return -1;
     if (validate_packed_key(m, "kge_train_pairwise_hinge_sampled")) return -1;
     if (n == 0) return 0;
     if (n < 0 || start < 0 || !triples || !perm || !loss) { set_error("kge_train_pairwise_hinge_sampled: bad arguments"); return -1; }
@@ -247,7 +257,7 @@ int kge_train_pairwise_hinge_sampled(const kge_model_desc* m, const int64_t* tri
 int kge_train_pairwise_selfadv(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
                                const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n_pos,
                                int32_t neg_rate, float alpha, float* workspace, float* loss, void* stream) {
-    if (validate(m, true, "kge_train_pairwise_selfadv")) return -1;
+    if (validate(m, true, "kge_train_pairwise_selfadv") || refuse_octonione(m, "kge_train_pairwise_selfadv")) return -1;
     if (n_pos == 0) return 0;
     if (n_pos < 0 || neg_rate <= 0 || !ph || !pr || !pt || !nh || !nr || !nt || !workspace || !loss) {
         set_error("kge_train_pairwise_selfadv: bad arguments");
@@ -276,7 +286,7 @@ int kge_train_pairwise_selfadv_sampled(const kge_model_desc* m, const int64_t* t
                                        int64_t n_pos, int32_t neg_rate, float alpha, const float* bern_prob,
                                        const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t offset,
                                        const int64_t* dev_cursor, float* loss, void* stream) {
-    if (validate(m, true, "kge_train_pairwise_selfadv_sampled")) return -1;
+    if (validate(m, true, "kge_train_pairwise_selfadv_sampled") || refuse_octonione(m, "kge_train_pairwise_selfadv_sampled")) return -1;
     if (validate_packed_key(m, "kge_train_pairwise_selfadv_sampled")) return -1;
     if (n_pos == 0) return 0;
     if (n_pos < 0 || start < 0 || neg_rate <= 0 || !triples || !perm || !loss) {
@@ -329,7 +339,7 @@ int kge_train_pairwise_selfadv_sampled_staged(const kge_model_desc* m, const int
                                               const float* bern_prob, const uint64_t* slots, int64_t n_slots, uint64_t seed,
                                               uint64_t offset, const kge_staged_step* st, float* loss, void* stream) {
     const char* who = "kge_train_pairwise_selfadv_sampled_staged";
-    if (validate(m, false, who)) return -1;
+    if (validate(m, false, who) || refuse_octonione(m, who)) return -1;
     if (validate_packed_key(m, who)) return -1;
     if (n_pos == 0) return 0;
     if (n_pos < 0 || start < 0 || neg_rate <= 0 || !triples || !perm || !loss || !st) { set_error("%s: bad arguments", who); return -1; }
@@ -351,7 +361,7 @@ int kge_train_pointwise_logistic_sampled_staged(const kge_model_desc* m, const i
                                                 float lmbda, int32_t reg_type, const kge_staged_step* st, float* loss,
                                                 void* stream) {
     const char* who = "kge_train_pointwise_logistic_sampled_staged";
-    if (validate(m, false, who)) return -1;
+    if (validate(m, false, who) || refuse_octonione(m, who)) return -1;
     if (validate_packed_key(m, who)) return -1;
     if (n_pos == 0) return 0;
     if (n_pos < 0 || neg_rate < 1 || start < 0 || !triples || !perm || !loss || !st) { set_error("%s: bad arguments", who); return -1; }
@@ -379,8 +389,9 @@ int kge_train_pointwise_logistic(const kge_model_desc* m, const int64_t* h, cons
     if (n == 0) return 0;
     if (n < 0 || !h || !r || !t || !y || !loss) { set_error("kge_train_pointwise_logistic: bad arguments"); return -1; }
     if (reg_type < KGE_REG_NONE || reg_type > KGE_REG_ID_N3) { set_error("kge_train_pointwise_logistic: bad reg_type %d", reg_type); return -1; }
-    if (!is_vector_model(m->model)) { set_error("kge_train_pointwise_logistic: unsupported model %d", m->model); return -1; }
+    if (!is_vector_model(m->model) && m->model != KGE_OCTONIONE) { set_error("kge_train_pointwise_logistic: unsupported model %d", m->model); return -1; }
     if (int rc = debug_check_hrt("kge_train_pointwise_logistic", m, h, r, t, n, (hipStream_t)stream)) return rc;
+    if (m->model == KGE_OCTONIONE) return launch_octonion_pointwise(m, h, r, t, y, n, bundle, lmbda, reg_type, loss, (hipStream_t)stream);
     return launch_pointwise_logistic(m, h, r, t, y, n, bundle, lmbda, reg_type, loss, nullptr, (hipStream_t)stream);
 }
 
@@ -394,9 +405,12 @@ int kge_train_pointwise_logistic_sampled(const kge_model_desc* m, const int64_t*
     if (n_pos < 0 || neg_rate < 1 || start < 0 || !triples || !perm || !loss) { set_error("kge_train_pointwise_logistic_sampled: bad arguments"); return -1; }
     if (slots && (n_slots & (n_slots - 1))) { set_error("kge_train_pointwise_logistic_sampled: n_slots must be a power of two"); return -1; }
     if (reg_type < KGE_REG_NONE || reg_type > KGE_REG_ID_N3) { set_error("kge_train_pointwise_logistic_sampled: bad reg_type %d", reg_type); return -1; }
-    if (!is_vector_model(m->model)) { set_error("kge_train_pointwise_logistic_sampled: unsupported model %d", m->model); return -1; }
+    if (!is_vector_model(m->model) && m->model != KGE_OCTONIONE) { set_error("kge_train_pointwise_logistic_sampled: unsupported model %d", m->model); return -1; }
     if (!dev_cursor)
         if (int rc = debug_check_triples("kge_train_pointwise_logistic_sampled", m->tot_entity, m->tot_relation, triples, n_pos, (hipStream_t)stream, perm, start)) return rc;
+    if (m->model == KGE_OCTONIONE)
+        return launch_octonion_pointwise_sampled(m, triples, perm, start, n_pos, neg_rate, bern_prob, slots, n_slots, seed, offset,
+                                                 dev_cursor, lmbda, reg_type, loss, (hipStream_t)stream);
     return launch_pointwise_logistic_sampled(m, triples, perm, start, n_pos, neg_rate, bern_prob, slots, n_slots, seed, offset,
                                              dev_cursor, lmbda, reg_type, loss, (hipStream_t)stream);
 }
@@ -738,7 +752,7 @@ int kge_own_step(const kge_model_desc* m, const int32_t* pairs, int64_t n_pairs,
                  int32_t reg_type, int32_t reset_lists, const int32_t* next_pairs, const int32_t* next_inv, int64_t next_n,
                  const float* bern_prob, const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t next_offset,
                  const kge_pull_lists* next_lists, float* loss, float* stage, void* stream) {
-    if (validate(m, true, "kge_own_step")) return -1;
+    if (validate(m, true, "kge_own_step") || refuse_octonione(m, "kge_own_step")) return -1;
     if (m->model != KGE_DISTMULT && m->model != KGE_COMPLEX) { set_error("kge_own_step: DistMult / ComplEx only (model %d)", m->model); return -1; }
     if (n_pairs <= 0 || n_items <= 0 || !pairs || !lists_ok(lists) || !items || !inc || !partials || !loss ||
         reg_type < KGE_REG_NONE || reg_type > KGE_REG_N3_ABS) {
@@ -759,7 +773,7 @@ int kge_own_step(const kge_model_desc* m, const int32_t* pairs, int64_t n_pairs,
 int kge_own_apply(const kge_model_desc* m, float* const* state1, float* const* state2, const int32_t* pairs, int64_t n_pairs,
                   const kge_pull_lists* lists, const int32_t* items, int64_t n_items, const uint32_t* listed, const int32_t* multi,
                   int64_t n_multi, float* partials, int32_t dense, int32_t optimizer, float lr, int64_t step, void* stream) {
-    if (validate(m, true, "kge_own_apply")) return -1;
+    if (validate(m, true, "kge_own_apply") || refuse_octonione(m, "kge_own_apply")) return -1;
     if (m->model != KGE_DISTMULT && m->model != KGE_COMPLEX) { set_error("kge_own_apply: DistMult / ComplEx only (model %d)", m->model); return -1; }
     if (n_pairs <= 0 || n_items <= 0 || n_multi < 0 || !pairs || !lists || !lists->pc || !items || (n_multi > 0 && (!multi || !partials)) || step < 1) {
         set_error("kge_own_apply: bad arguments");

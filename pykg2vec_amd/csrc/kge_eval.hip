@@ -124,6 +124,7 @@ size_t eval_workspace_bytes(const kge_model_desc* m, int64_t n, int64_t tables) 
     if (is_semantic_model(m->model)) return semantic_eval_workspace_bytes(m, n);
     if (m->model == KGE_HOLE) return hole_eval_workspace_bytes(m, n);
     if (m->model == KGE_KG2E) return kg2e_eval_workspace_bytes(m, n);
+    if (m->model == KGE_OCTONIONE) return octonion_eval_workspace_bytes(m, n);
     EvalPlan p;
     if (!make_plan(m, n, nullptr, &p, tables)) return 0;
     return p.bytes;
@@ -1778,6 +1779,8 @@ int launch_eval_ranks(const kge_model_desc* m, const int64_t* triples, int64_t n
         return launch_hole_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
     if (m->model == KGE_KG2E)
         return launch_kg2e_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
+    if (m->model == KGE_OCTONIONE)
+        return launch_octonion_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
     return run_pipeline(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s);
 }
 
@@ -1841,6 +1844,8 @@ int launch_eval_sweep_scores(const kge_model_desc* m, const int64_t* triples, in
         return launch_hole_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
     if (m->model == KGE_KG2E)
         return launch_kg2e_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
+    if (m->model == KGE_OCTONIONE)
+        return launch_octonion_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
     return run_pipeline(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
 }
 

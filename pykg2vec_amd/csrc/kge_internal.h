@@ -17,7 +17,7 @@
 namespace kge {
 
 void set_error(const char* fmt, ...);
-bool is_vector_model(int model);  // models handled by the gather/row kernels (everything but RESCAL, NTN, TransR, SLM, SME, HoLE)
+bool is_vector_model(int model);  // models handled by the gather/row kernels (everything but RESCAL, NTN, TransR, SLM, SME, HoLE, OctonionE)
 
 // (G, NCH) geometry for a row length; returns false when the row is too long for the register-resident kernels
 struct Geometry { int G, NCH; };
@@ -296,6 +296,22 @@ size_t hole_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
 int launch_hole_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
                      const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
                      float* scores, hipStream_t s, int side);
+
+// kge_octonion.hip (OctonionE: component-block tables, include/kge_hip.h)
+int launch_octonion_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
+                            hipStream_t s);
+int launch_octonion_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
+                             const float* dscore, hipStream_t s);
+int launch_octonion_pointwise(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, const int64_t* y,
+                              int64_t n, int bundle, float lmbda, int reg_type, float* loss, hipStream_t s);
+int launch_octonion_pointwise_sampled(const kge_model_desc* m, const int64_t* triples, const int64_t* perm, int64_t start,
+                                      int64_t n_pos, int neg_rate, const float* bern, const uint64_t* slots, int64_t n_slots,
+                                      uint64_t seed, uint64_t offset, const int64_t* cursor, float lmbda, int reg_type, float* loss,
+                                      hipStream_t s);
+size_t octonion_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
+int launch_octonion_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                         const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
+                         float* scores, hipStream_t s, int side);
 
 // kge_kg2e_eval.hip (KG2E rank)
 size_t kg2e_eval_workspace_bytes(const kge_model_desc* m, int64_t n);

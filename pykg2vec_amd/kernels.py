@@ -14,7 +14,8 @@ from . import _lib as L
 MODEL_IDS = {"transe": L.TRANSE, "transh": L.TRANSH, "transd": L.TRANSD, "rotate": L.ROTATE, "rescal": L.RESCAL,
              "ntn": L.NTN, "distmult": L.DISTMULT, "complex": L.COMPLEX, "complexn3": L.COMPLEX, "analogy": L.ANALOGY,
              "transm": L.TRANSM, "cp": L.CP, "simple": L.SIMPLE, "simple_ignr": L.SIMPLE_IGNR, "quate": L.QUATE,
-             "transr": L.TRANSR, "slm": L.SLM, "sme": L.SME, "sme_bl": L.SME_BL, "kg2e": L.KG2E, "hole": L.HOLE}
+             "transr": L.TRANSR, "slm": L.SLM, "sme": L.SME, "sme_bl": L.SME_BL, "kg2e": L.KG2E, "hole": L.HOLE,
+             "octonione": L.OCTONIONE}
 OPTIMIZER_IDS = {"sgd": L.OPT_SGD, "adam": L.OPT_ADAM, "adagrad": L.OPT_ADAGRAD, "rms": L.OPT_RMSPROP,
                  "gradient": 4}   # KGE_OPT_GRADIENT: kge_pull_step writes the dense gradient instead of updating
 
@@ -66,6 +67,8 @@ _TABLE_SHAPES = {
     # QuatE's four relation tables are allocated with tot_entity rows (models/pointwise.py:622-631) but looked up by RELATION
     # id: tot_relation > tot_entity is an IndexError in the reference and a refused descriptor here
     "quate": [("E", "d")] * 4 + [("R", "d")] * 4,
+    # ent_embedding_1..8, rel_embedding_1..8, rel_w_embedding (never read: the descriptor carries two component blocks)
+    "octonione": [("E", "d")] * 8 + [("R", "d")] * 8 + [("R", "d")],
 }
 
 
@@ -149,6 +152,77 @@ def make_desc(model_name, tables, grads=None, *, tot_entity, tot_relation, dim, 
     return d
 
 
+def _block_of(tensors, rows, dim):
+    """The first tensor if tensors[c] is the fp32 contiguous [rows, dim] table at data_ptr(tensors[0]) + c * roundup4(rows * dim)
+    floats for every c (a component block of include/kge_hip.h's KGE_OCTONIONE convention, e.g. FlatState's views), else None."""
+    stride = (rows * dim + 3) // 4 * 4 * 4
+    t0 = tensors[0]
+    for c, t in enumerate(tensors):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, dim)
+                and t.device == t0.device and t.data_ptr() == t0.data_ptr() + c * stride):
+            return None
+    return t0
+
+
+def _pack_block(tensors, rows, dim):
+    """A fresh component block holding rows [0, rows) of every table."""
+    stride = (rows * dim + 3) // 4 * 4
+    for i, t in enumerate(tensors):
+        _dev(t, torch.float32, "table %d" % i)
+    blk = torch.zeros(len(tensors) * stride, dtype=torch.float32, device=tensors[0].device)
+    for c, t in enumerate(tensors):
+        blk[c * stride:c * stride + rows * dim].view(rows, dim).copy_(t[:rows])
+    return blk
+
+
+def octonion_desc(tables, grads=None, *, tot_entity, tot_relation, dim):
+    """kge_model_desc of OctonionE: `tables` / `grads` in parameter_list order (ent_embedding_1..8, rel_embedding_1..8 and
+    optionally rel_w_embedding, which is never read).  Tables that already sit as component blocks (FlatState, or a model kept in
+    block layout) are passed by address; otherwise they are packed into temporary blocks, and packed gradients are copied back
+    into `grads` by the call that accumulates into them (score_backward / train_pointwise_logistic / _sampled)."""
+    _check_table_shapes("octonione", tables, tot_entity, tot_relation, dim, dim)
+    E, R, d = int(tot_entity), int(tot_relation), int(dim)
+    desc = L.ModelDesc()
+    desc.model = L.OCTONIONE
+    desc.flags = 0
+    desc.tot_entity, desc.tot_relation = E, R
+    desc.dim = desc.rel_dim = d
+    desc.margin = desc.phase_scale = 0.0
+    keep, after = [], []
+    for slot, (lo, rows) in enumerate(((0, E), (8, R))):
+        parts = list(tables[lo:lo + 8])
+        blk = _block_of(parts, rows, d)
+        if blk is None:
+            blk = _pack_block(parts, rows, d)
+        desc.tables[slot] = blk.data_ptr()
+        keep.append(blk)
+        if grads is not None:
+            gparts = list(grads[lo:lo + 8])
+            for g, t in zip(gparts, parts):
+                if g.shape != t.shape:
+                    raise ValueError("grad shape %s != table shape %s" % (tuple(g.shape), tuple(t.shape)))
+            gblk = _block_of(gparts, rows, d)
+            if gblk is None:
+                gblk = _pack_block(gparts, rows, d)
+                stride = (rows * d + 3) // 4 * 4
+
+                def unpack(gblk=gblk, gparts=gparts, rows=rows, stride=stride):
+                    for c, g in enumerate(gparts):
+                        g[:rows].copy_(gblk[c * stride:c * stride + rows * d].view(rows, d))
+                after.append(unpack)
+            desc.grads[slot] = gblk.data_ptr()
+            keep.append(gblk)
+    desc._keepalive = (tables, grads, keep)
+    desc._after = after
+    return desc
+
+
+def _finish(desc):
+    """Work a descriptor asks for after a call that wrote its gradient buffers (octonion_desc's packed gradients)."""
+    for fn in getattr(desc, "_after", ()):
+        fn()
+
+
 def model_desc(model, weights=None, grads=None):
     """Descriptor of a drop-in model object (kgmeta.Model.make_desc)."""
     return model.make_desc(weights, grads)
@@ -179,6 +253,7 @@ def score_backward(desc, h, r, t, dscore):
     wp, wb, _keep = _workspace(desc, n, h.device)
     L.check(L.load().kge_score_backward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
                                         _dev(dscore, torch.float32, "dscore"), wp, wb, _stream()), "kge_score_backward")
+    _finish(desc)
 
 
 _rescal_scratch = {}
@@ -242,6 +317,7 @@ def train_pointwise_logistic_sampled(desc, triples, perm, start, n_pos, neg_rate
                                                           int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), pc,
                                                           float(lmbda), int(reg_type), _dev(loss_buf, torch.float32, "loss"),
                                                           _stream()), "kge_train_pointwise_logistic_sampled")
+    _finish(desc)
 
 
 def train_pairwise_selfadv_sampled(desc, triples, perm, start, n_pos, neg_rate, alpha, bern_prob, slots, seed, offset,
@@ -430,6 +506,7 @@ def train_pointwise_logistic(desc, h, r, t, y, lmbda, reg_type, loss_buf, bundle
                                                   _ids(y, "y"), n, int(bundle), float(lmbda), int(reg_type),
                                                   _dev(loss_buf, torch.float32, "loss"), _stream()),
             "kge_train_pointwise_logistic")
+    _finish(desc)
 
 
 def l2norm_reg(param, grad, lmbda, loss_buf):

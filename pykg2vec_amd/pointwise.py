@@ -1,11 +1,12 @@
 """Drop-in pointwise (semantic-matching) models mirroring pykg2vec/models/pointwise.py (DistMult, Complex,
-ComplexN3, ANALOGY, CP, SimplE, SimplE_ignr, QuatE), scored by HIP kernels.  `get_reg` keeps the reference's
+ComplexN3, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, OctonionE), scored by HIP kernels.  `get_reg` keeps the reference's
 tensor-level form for use under the unmodified reference Trainer; the fused training kernel applies the same
 regulariser from registers."""
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import kernels as K
 from .criterion import Criterion
 from .kgmeta import NamedEmbedding, PointwiseModel
 
@@ -229,6 +230,83 @@ class QuatE(DistMult):
         rt = (reg_type or self.default_reg).lower()
         if rt not in ("f2", "n3"):
             raise NotImplementedError("Unknown regularizer type: %s" % rt)
+        p = 2 if rt == "f2" else 3
+        return self.lmbda * sum(torch.mean(torch.abs(x) ** p) for x in self.embed(h, r, t))
+
+    def kernel_lmbda(self):
+        return self.lmbda / self.hidden_size  # means over all B*k elements, not over the B rows
+
+    def kernel_reg_type(self, reg_type=None):
+        rt = (reg_type or self.default_reg).lower()
+        if rt == "f2":
+            return L.REG_F2
+        if rt == "n3":
+            return L.REG_N3_ABS
+        raise NotImplementedError("Unknown regularizer type: %s" % rt)
+
+
+class OctonionE(DistMult):
+    """pointwise.py:772-1001.  energy = -sum(o(h, r / |r|) . t) with element-wise octonions of 8 components (the product built from
+    quaternion products and conjugates, _omult).  rel_w_embedding is in parameter_list and the state dict but unused by forward.
+
+    The kernels take the 8 entity and the 8 relation tables as two component blocks (include/kge_hip.h, KGE_OCTONIONE).  The
+    model keeps its tables in that layout -- at construction and after every .to() / .cuda() -- so descriptors pass them by
+    address; tables moved out of it (a caller re-binding .data) still work through a packed copy (kernels.octonion_desc)."""
+    kernel_name = "octonione"
+    default_reg, reg_abs = "N3", True
+
+    def __init__(self, **kwargs):
+        PointwiseModel.__init__(self, self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "hidden_size", "lmbda"], kwargs))
+        k = self.hidden_size
+        for i in range(1, 9):
+            setattr(self, "ent_embedding_%d" % i, NamedEmbedding("ent_embedding_%d" % i, self.tot_entity, k))
+        for i in range(1, 9):
+            setattr(self, "rel_embedding_%d" % i, NamedEmbedding("rel_embedding_%d" % i, self.tot_relation, k))
+        self.rel_w_embedding = NamedEmbedding("rel_w_embedding", self.tot_relation, k)
+        self.parameter_list = ([getattr(self, "ent_embedding_%d" % i) for i in range(1, 9)]
+                               + [getattr(self, "rel_embedding_%d" % i) for i in range(1, 9)] + [self.rel_w_embedding])
+        _xavier(*self.parameter_list)
+        self.loss = Criterion.pointwise_logistic
+        self._to_blocks()
+
+    def _to_blocks(self):
+        """Re-home ent_embedding_1..8 and rel_embedding_1..8 into one component block each (segments rounded up to 4 floats)."""
+        for group in (self.parameter_list[0:8], self.parameter_list[8:16]):
+            w = [e.weight for e in group]
+            if w[0].dtype != torch.float32:
+                continue
+            stride = (w[0].numel() + 3) // 4 * 4
+            if all(x.device == w[0].device and x.is_contiguous() and x.data_ptr() == w[0].data_ptr() + 4 * c * stride
+                   for c, x in enumerate(w)):
+                continue
+            blk = torch.zeros(8 * stride, dtype=torch.float32, device=w[0].device)
+            for c, x in enumerate(w):
+                v = blk[c * stride:c * stride + x.numel()].view_as(x)
+                v.copy_(x.data)
+                x.data = v
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._to_blocks()   # .to() / .cuda() move every table on its own
+        return out
+
+    def make_desc(self, weights=None, grads=None):
+        if weights is None:
+            weights = [p.weight for p in self.parameter_list]
+        return K.octonion_desc(list(weights), None if grads is None else list(grads), tot_entity=self.tot_entity,
+                               tot_relation=self.tot_relation, dim=self.hidden_size)
+
+    def embed(self, h, r, t):
+        e = self.parameter_list[0:8]
+        q = self.parameter_list[8:16]
+        return tuple(x(h) for x in e) + tuple(x(t) for x in e) + tuple(x(r) for x in q)
+
+    def get_reg(self, h, r, t, reg_type="N3"):
+        """pointwise.py:894-956: lmbda * sum over the 24 gathered row sets of mean(|x|^p) (means over B * d; raw r, rel_w excluded)."""
+        rt = reg_type.lower()
+        if rt not in ("f2", "n3"):
+            raise NotImplementedError("Unknown regularizer type: %s" % reg_type)
         p = 2 if rt == "f2" else 3
         return self.lmbda * sum(torch.mean(torch.abs(x) ** p) for x in self.embed(h, r, t))
 

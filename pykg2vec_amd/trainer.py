@@ -169,6 +169,8 @@ class Trainer:
         if not (self.K is K and self.model.training_strategy == TrainingStrategy.POINTWISE_BASED):
             return False
         group = 32 if self.model.hidden_size <= 256 else 64
+        if self.model.kernel_name == "octonione":   # the bundle's positive holds a lane of the group too (csrc/kge_octonion.hip)
+            group -= 1
         return 1 <= int(self.config.neg_rate) <= group
 
     def _fused_rotate_ok(self, staged=False):
