@@ -17,14 +17,8 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-bool is_vector_model(int model) {
-    switch (model) {
-        case KGE_TRANSE: case KGE_TRANSH: case KGE_TRANSD: case KGE_ROTATE:
-        case KGE_DISTMULT: case KGE_COMPLEX: case KGE_ANALOGY:
-        case KGE_TRANSM: case KGE_CP: case KGE_SIMPLE: case KGE_SIMPLE_IGNR: case KGE_QUATE: case KGE_KG2E: return true;
-        default: return false;
-    }
-}
+// models handled by the gather / row kernels (everything but RESCAL, NTN, TransR, SLM, SME, SME_BL, HoLE, OctonionE); validate() first
+static bool is_vector_model(int model) { return model_ops(model)->row_kernels; }
 
 bool pick_geometry(int d, Geometry* out) {
     if (d <= 0) return false;
@@ -39,23 +33,6 @@ bool pick_geometry(int d, Geometry* out) {
     return true;
 }
 
-static int table_count(int model) {
-    switch (model) {
-        case KGE_TRANSE: case KGE_DISTMULT: case KGE_RESCAL: return 2;
-        case KGE_TRANSH: case KGE_ROTATE: return 3;
-        case KGE_TRANSD: case KGE_COMPLEX: return 4;
-        case KGE_NTN: case KGE_ANALOGY: return 6;
-        case KGE_TRANSM: case KGE_CP: case KGE_TRANSR: return 3;
-        case KGE_SIMPLE: case KGE_SIMPLE_IGNR: return 4;
-        case KGE_QUATE: case KGE_SME: case KGE_SME_BL: return 8;
-        case KGE_SLM: case KGE_KG2E: return 4;
-        case KGE_HOLE: return 2;
-        case KGE_OCTONIONE: return 2;   // the entity and relation component blocks
-    }
-    return -1;
-}
-static int grad_count(int model) { return model == KGE_TRANSM ? 2 : table_count(model); }  // TransM's theta is a fixed input
-
 DeviceModel to_device_model(const kge_model_desc* m) {
     DeviceModel d;
     for (int i = 0; i < KGE_MAX_TABLES; ++i) { d.tab[i] = m->tables[i]; d.grad[i] = m->grads[i]; }
@@ -69,8 +46,8 @@ DeviceModel to_device_model(const kge_model_desc* m) {
 
 static int validate(const kge_model_desc* m, bool need_grads, const char* who) {
     if (!m) { set_error("%s: null model descriptor", who); return -1; }
-    const int nt = table_count(m->model);
-    if (nt < 0) { set_error("%s: unknown model id %d", who, m->model); return -1; }
+    const ModelOps* ops = model_ops(m->model);
+    if (!ops) { set_error("%s: unknown model id %d", who, m->model); return -1; }
     if (m->dim <= 0 || m->tot_entity <= 0 || m->tot_relation <= 0) {
         set_error("%s: bad sizes (dim %d, entities %lld, relations %lld)", who, m->dim, (long long)m->tot_entity,
                   (long long)m->tot_relation);
@@ -81,9 +58,9 @@ static int validate(const kge_model_desc* m, bool need_grads, const char* who) {
         return -1;
     }
     if (m->model == KGE_ANALOGY && (m->dim & 1)) { set_error("%s: ANALOGY needs an even hidden size", who); return -1; }
-    for (int i = 0; i < nt; ++i) {
+    for (int i = 0; i < ops->tables; ++i) {
         if (!m->tables[i]) { set_error("%s: table %d is null", who, i); return -1; }
-        if (need_grads && i < grad_count(m->model) && !m->grads[i]) { set_error("%s: gradient buffer %d is null", who, i); return -1; }
+        if (need_grads && i < ops->grads && !m->grads[i]) { set_error("%s: gradient buffer %d is null", who, i); return -1; }
     }
     return 0;
 }
@@ -115,14 +92,17 @@ extern "C" {
 int kge_abi_version(void) { return KGE_ABI_VERSION; }
 const char* kge_last_error(void) { return g_err; }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static const int64_t kTransRRowsMinPairs = 1;      // the two-launch step wins at every batch size measured (128 ... 32 768 pairs: profiles/r04_transr_threshold.txt)
+// one scorer workspace per side (positive / negative) of the pairwise step
+static size_t scorer_ws_bytes(const ModelOps* ops, const kge_model_desc* m, int64_t n) {
+    return align256(ops->scorer_ws ? ops->scorer_ws(m, n) : 0);
+}
 
 size_t kge_workspace_bytes(const kge_model_desc* m, int64_t n) {
     if (validate(m, false, "kge_workspace_bytes") || n < 0) return 0;
-    if (is_vector_model(m->model) || m->model == KGE_OCTONIONE) return 0;
-    // the pairwise step keeps one scorer workspace per side (positive / negative) plus the two score vectors
-    size_t b = 2 * align256(dense_workspace_bytes(m, n)) + align256((size_t)2 * n * sizeof(float));
+    const ModelOps* ops = model_ops(m->model);
+    if (!ops->pair_forward) return 0;   // row-kernel models and OctonionE
+    // the pairwise step keeps one scorer workspace per side plus the two score vectors
+    size_t b = 2 * scorer_ws_bytes(ops, m, n) + align256((size_t)2 * n * sizeof(float));
     if (m->model == KGE_RESCAL) b += rescal_slab_extra_bytes(m, n);   // V rows + energy shares of the slab form of the pairwise step
     return b;
 }
@@ -134,12 +114,7 @@ int kge_score_forward(const kge_model_desc* m, const int64_t* h, const int64_t* 
     if (n < 0 || !h || !r || !t || !scores) { set_error("kge_score_forward: bad arguments"); return -1; }
     hipStream_t s = (hipStream_t)stream;
     if (int rc = debug_check_hrt("kge_score_forward", m, h, r, t, n, s)) return rc;
-    if (m->model == KGE_RESCAL) return launch_rescal_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
-    if (m->model == KGE_NTN) return launch_ntn_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
-    if (m->model == KGE_TRANSR) return launch_transr_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
-    if (is_semantic_model(m->model)) return launch_semantic_forward(m, h, r, t, n, scores, workspace, workspace_bytes, s);
-    if (m->model == KGE_HOLE) return launch_hole_forward(m, h, r, t, n, scores, s);
-    if (m->model == KGE_OCTONIONE) return launch_octonion_forward(m, h, r, t, n, scores, s);
+    if (ScoreFwdFn* own = model_ops(m->model)->forward) return own(m, h, r, t, n, scores, workspace, workspace_bytes, s);
     return launch_score_forward(m, h, r, t, n, scores, s);
 }
 
@@ -150,12 +125,7 @@ int kge_score_backward(const kge_model_desc* m, const int64_t* h, const int64_t*
     if (n < 0 || !h || !r || !t || !dscore) { set_error("kge_score_backward: bad arguments"); return -1; }
     hipStream_t s = (hipStream_t)stream;
     if (int rc = debug_check_hrt("kge_score_backward", m, h, r, t, n, s)) return rc;
-    if (m->model == KGE_RESCAL) return launch_rescal_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
-    if (m->model == KGE_NTN) return launch_ntn_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
-    if (m->model == KGE_TRANSR) return launch_transr_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, false, s);
-    if (is_semantic_model(m->model)) return launch_semantic_backward(m, h, r, t, n, dscore, workspace, workspace_bytes, s);
-    if (m->model == KGE_HOLE) return launch_hole_backward(m, h, r, t, n, dscore, s);
-    if (m->model == KGE_OCTONIONE) return launch_octonion_backward(m, h, r, t, n, dscore, s);
+    if (ScoreBwdFn* own = model_ops(m->model)->backward) return own(m, h, r, t, n, dscore, workspace, workspace_bytes, s);
     return launch_score_backward(m, h, r, t, n, dscore, s);
 }
 
@@ -184,9 +154,11 @@ int kge_train_pairwise_hinge(const kge_model_desc* m, const int64_t* ph, const i
     hipStream_t s = (hipStream_t)stream;
     if (int rc = debug_check_hrt("kge_train_pairwise_hinge (positives)", m, ph, pr, pt, n, s)) return rc;
     if (int rc = debug_check_hrt("kge_train_pairwise_hinge (negatives)", m, nh, nr, nt, n, s)) return rc;
-    if (is_vector_model(m->model)) return launch_pairwise_hinge(m, ph, pr, pt, nh, nr, nt, n, margin, loss, s);
-    // dense-contraction models: forward over [positives | negatives], hinge coefficients in place, backward over the same 2n
-    const size_t gws = align256(dense_workspace_bytes(m, n));
+    const ModelOps* ops = model_ops(m->model);
+    if (ops->row_kernels) return launch_pairwise_hinge(m, ph, pr, pt, nh, nr, nt, n, margin, loss, s);
+    if (!ops->pair_forward) { set_error("kge_train_pairwise_hinge: unsupported model %d", m->model); return -1; }
+    // the other models: forward over [positives | negatives], hinge coefficients in place, backward over the same 2n
+    const size_t gws = scorer_ws_bytes(ops, m, n);
     if (!workspace || workspace_bytes < 2 * gws + align256((size_t)2 * n * sizeof(float))) {
         set_error("kge_train_pairwise_hinge: workspace too small (need kge_workspace_bytes)");
         return -1;
@@ -194,45 +166,16 @@ int kge_train_pairwise_hinge(const kge_model_desc* m, const int64_t* ph, const i
     void* wsp = workspace;                       // scorer workspace: both sides as one batch of 2n triples (2 gws bytes)
     float* sp = (float*)((char*)workspace + 2 * gws);
     float* sn = sp + n;
+    if (ops->pair_fast) {   // the whole step in one or two launches where the model has such a form and the batch allows it
+        const int rc1 = ops->pair_fast(m, ph, pr, pt, nh, nr, nt, n, margin, loss, wsp, 2 * gws, workspace_bytes, s);
+        if (rc1 <= 0) return rc1;
+    }
+    // scores / coefficients contiguous (sp | sn); RESCAL and TransR keep the grouping of the 2n triples in the scorer workspace
+    // between the two passes (group_ws_bytes(R, 2n) <= 2 gws)
     int rc;
-    if (m->model == KGE_RESCAL) {
-        // nr == pr (the same buffer: the caller's way of saying that negatives keep their positives' relations, as every sampler
-        // of the reference does): scores, hinge and gradients of a (relation, 16 pairs) tile in one launch
-        const bool unfused = switch_value("RESCAL_UNFUSED") == 1;   // A/B switch (same 0 / 1 meaning as Trainer.switches)
-        if (nr == pr && rescal_pair_step_ok(m, n, 2 * gws) && !unfused)
-            return launch_rescal_pair_step(m, ph, pr, pt, nh, nt, n, margin, loss, wsp, workspace_bytes, nullptr, nullptr, s);
-        // positives and negatives as ONE grouped batch of 2n triples (scores / coefficients contiguous: sp | sn); the
-        // region of the two per-side workspaces holds the grouping of 2n triples (group_ws_bytes(R, 2n) <= 2 gws)
-        if ((rc = launch_rescal_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
-        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
-        return launch_rescal_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
-    }
-    if (m->model == KGE_NTN) {
-        if ((rc = launch_ntn_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
-        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
-        return launch_ntn_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
-    }
-    if (m->model == KGE_TRANSR) {
-        // nr == pr (one buffer): the two-launch step of kge_transr_rows.hip (KGE_TRANSR_ROWS=0: the tile kernels)
-        const int rows_sw = switch_value("TRANSR_ROWS");
-        if (nr == pr && rows_sw != 0 && (rows_sw >= 1 || n >= kTransRRowsMinPairs) && transr_rows_ok(m, n, 2 * gws))
-            return launch_transr_pair_step(m, ph, pr, pt, nh, nt, n, margin, loss, wsp, 2 * gws, s);
-        if ((rc = launch_transr_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
-        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
-        return launch_transr_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
-    }
-    if (is_semantic_model(m->model)) {   // SLM / SME / SME_BL (kge_semantic.hip): the NTN route
-        if ((rc = launch_semantic_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
-        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
-        return launch_semantic_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
-    }
-    if (m->model == KGE_HOLE) {   // kge_hole.hip: the same route, no scorer workspace (gws = 0)
-        if ((rc = launch_hole_pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, s))) return rc;
-        if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
-        return launch_hole_pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, s);
-    }
-    set_error("kge_train_pairwise_hinge: unsupported model %d", m->model);
-    return -1;
+    if ((rc = ops->pair_forward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s))) return rc;
+    if ((rc = launch_hinge_coeffs(sp, sn, n, margin, loss, s))) return rc;
+    return ops->pair_backward(m, ph, pr, pt, nh, nr, nt, n, sp, wsp, 2 * gws, s);
 }
 
 int kge_train_pairwise_hinge_sampled(const kge_model_desc* m, const int64_t* triples, const int64_t* perm, int64_t start,

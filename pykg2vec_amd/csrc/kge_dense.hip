@@ -466,15 +466,7 @@ static size_t rescal_lds_bytes(int k) {
            (size_t)2 * TILE * sizeof(long long) + (size_t)4 * 16 * 64 * sizeof(float);   // + the K-split accumulators
 }
 
-
-
-size_t dense_workspace_bytes(const kge_model_desc* m, int64_t n) {
-    if (m->model == KGE_RESCAL) return group_ws_bytes(m->tot_relation, n);
-    if (m->model == KGE_NTN) return ntn_workspace_bytes(m, n);
-    if (m->model == KGE_TRANSR) return transr_workspace_bytes(m, n);
-    if (is_semantic_model(m->model)) return semantic_workspace_bytes(m, n);
-    return 0;
-}
+size_t rescal_workspace_bytes(const kge_model_desc* m, int64_t n) { return group_ws_bytes(m->tot_relation, n); }
 
 static int rescal_run(int mode, const kge_model_desc* m, IdSplit h, IdSplit r, IdSplit t, int64_t n,
                       const float* dscore, float* scores, void* ws, size_t ws_bytes, bool grouped, hipStream_t s) {
@@ -521,8 +513,8 @@ int launch_rescal_forward(const kge_model_desc* m, const int64_t* h, const int64
     return rescal_run(0, m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, nullptr, scores, ws, ws_bytes, false, s);
 }
 int launch_rescal_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                           const float* dscore, void* ws, size_t ws_bytes, bool grouped, hipStream_t s) {
-    return rescal_run(1, m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, dscore, nullptr, ws, ws_bytes, grouped, s);
+                           const float* dscore, void* ws, size_t ws_bytes, hipStream_t s) {
+    return rescal_run(1, m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, dscore, nullptr, ws, ws_bytes, false, s);
 }
 
 // The fused pairwise step scores / back-propagates positives and negatives as ONE batch of 2n triples: one grouping pass and
@@ -1478,14 +1470,13 @@ static size_t rescal_pair_ws_bytes(int64_t R, int64_t n) {
 // Below the split thresholds the step runs as (relation chunk, 32-column slab) workgroups (kge_rescal_slab.hip) when the caller's
 // workspace has room for the V rows and the slabs' energy shares BEHIND the pairwise step's standard layout (two grouping
 // workspaces + 2 n scores, kge_workspace_bytes); KGE_RESCAL_SLAB=0: the one-launch tile kernel k_rescal_pair (A/B).
-static size_t align256d(size_t x) { return (x + 255) & ~(size_t)255; }
 static size_t rescal_slab_offset(int64_t R, int64_t n) {
-    return 2 * align256d(group_ws_bytes(R, n)) + align256d((size_t)2 * n * sizeof(float));
+    return 2 * align256(group_ws_bytes(R, n)) + align256((size_t)2 * n * sizeof(float));
 }
 size_t rescal_slab_extra_bytes(const kge_model_desc* m, int64_t n) {
     if (m->dim % 2 != 0 || m->dim > 256 || n >= kPairSplitG) return 0;
     if (!group_small_ok(n, m->tot_relation)) return 0;
-    return align256d(rescal_slab_ws_bytes(m->dim, m->tot_relation, n));
+    return align256(rescal_slab_ws_bytes(m->dim, m->tot_relation, n));
 }
 
 bool rescal_pair_step_ok(const kge_model_desc* m, int64_t n, size_t ws_bytes) {
@@ -1579,6 +1570,17 @@ int launch_rescal_pair_step(const kge_model_desc* m, const int64_t* ph, const in
 #undef KGE_RG
     }
     return check_launch("k_rescal_pair");
+}
+
+// The pairwise hinge step's shortcut: nr == pr (the same buffer: the caller's way of saying that negatives keep their positives'
+// relations, as every sampler of the reference does): scores, hinge and gradients of a (relation, 16 pairs) tile in one launch
+int rescal_pair_fast(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                     const int64_t* nr, const int64_t* nt, int64_t n, float margin, float* loss, void* ws, size_t ws_bytes,
+                     size_t total_bytes, hipStream_t s) {
+    const bool unfused = switch_value("RESCAL_UNFUSED") == 1;   // A/B switch (same 0 / 1 meaning as Trainer.switches)
+    if (nr == pr && rescal_pair_step_ok(m, n, ws_bytes) && !unfused)
+        return launch_rescal_pair_step(m, ph, pr, pt, nh, nt, n, margin, loss, ws, total_bytes, nullptr, nullptr, s);
+    return 1;
 }
 
 // ---- hinge coefficients for models scored by separate forward/backward launches (RESCAL, NTN):

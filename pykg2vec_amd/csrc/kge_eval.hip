@@ -65,8 +65,6 @@ struct EvalPlan {
     size_t bytes;
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int sweep_K(const kge_model_desc* m) {
     switch (m->model) {
         case KGE_COMPLEX: case KGE_ROTATE: case KGE_ANALOGY: return 2 * m->dim;
@@ -120,11 +118,7 @@ static bool make_plan(const kge_model_desc* m, int64_t n, void* ws, EvalPlan* p,
 }
 
 size_t eval_workspace_bytes(const kge_model_desc* m, int64_t n, int64_t tables) {
-    if (m->model == KGE_NTN) return ntn_eval_workspace_bytes(m, n);
-    if (is_semantic_model(m->model)) return semantic_eval_workspace_bytes(m, n);
-    if (m->model == KGE_HOLE) return hole_eval_workspace_bytes(m, n);
-    if (m->model == KGE_KG2E) return kg2e_eval_workspace_bytes(m, n);
-    if (m->model == KGE_OCTONIONE) return octonion_eval_workspace_bytes(m, n);
+    if (WsBytesFn* own = model_ops(m->model)->eval_ws) return own(m, n);
     EvalPlan p;
     if (!make_plan(m, n, nullptr, &p, tables)) return 0;
     return p.bytes;
@@ -1672,7 +1666,7 @@ static void launch_tf_and_sweep(const EvalPlan& p, const kge_model_desc* m, cons
 
 static int run_pipeline(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off,
                         const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws,
-                        size_t ws_bytes, int32_t* ranks, int32_t* ties, float* scores_out, hipStream_t s, int side = 2) {
+                        size_t ws_bytes, int32_t* ranks, int32_t* ties, float* scores_out, hipStream_t s, int side) {
     EvalPlan p;
     if (!make_plan(m, n, ws, &p)) { set_error("kge_eval: model %d has no sweep form", m->model); return -1; }
     if (side != 2) {   // one-sided: scores [n, E], or ranks [2, n] = (rank, filtered rank) of that side (ties [n])
@@ -1769,19 +1763,8 @@ static int run_pipeline(const kge_model_desc* m, const int64_t* triples, int64_t
 int launch_eval_ranks(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off,
                       const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws,
                       size_t ws_bytes, int32_t* ranks, int32_t* ties, hipStream_t s) {
-    if (m->model == KGE_NTN) {   // (the NTN sweep does not count ties: reported as unknown, -1)
-        if (ties) (void)hipMemsetAsync(ties, 0xFF, (size_t)2 * n * sizeof(int32_t), s);
-        return launch_ntn_eval_ranks(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, s);
-    }
-    if (is_semantic_model(m->model))
-        return launch_semantic_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
-    if (m->model == KGE_HOLE)
-        return launch_hole_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
-    if (m->model == KGE_KG2E)
-        return launch_kg2e_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
-    if (m->model == KGE_OCTONIONE)
-        return launch_octonion_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
-    return run_pipeline(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s);
+    EvalFn* eval = model_ops(m->model)->eval;
+    return (eval ? eval : run_pipeline)(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, nullptr, s, 2);
 }
 
 // TransR over several relation groups in one pass: one projected candidate table per group, every sweep workgroup
@@ -1834,19 +1817,8 @@ int launch_eval_ranks_grouped(const kge_model_desc* m, const int64_t* triples, i
 // side 0 / 1: float [n, E], the tail / head sweep only
 int launch_eval_sweep_scores(const kge_model_desc* m, const int64_t* triples, int64_t n, void* ws, size_t ws_bytes,
                              float* scores, hipStream_t s, int side) {
-    if (m->model == KGE_NTN) {
-        if (side != 2) { set_error("kge_eval_sweep_scores_side: the NTN sweep computes both sides per call"); return -1; }
-        return launch_ntn_eval_scores(m, triples, n, ws, ws_bytes, scores, s);
-    }
-    if (is_semantic_model(m->model))
-        return launch_semantic_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
-    if (m->model == KGE_HOLE)
-        return launch_hole_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
-    if (m->model == KGE_KG2E)
-        return launch_kg2e_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
-    if (m->model == KGE_OCTONIONE)
-        return launch_octonion_eval(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
-    return run_pipeline(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
+    EvalFn* eval = model_ops(m->model)->eval;
+    return (eval ? eval : run_pipeline)(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, nullptr, scores, s, side);
 }
 
 static kge_model_desc dot_desc(const float* cand, const float* q, int K, int64_t E, bool sigmoid) {
@@ -1870,6 +1842,19 @@ int launch_dot_eval(const float* cand, const float* q, int K, int64_t E, const i
                     int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side, bool sigmoid) {
     const kge_model_desc m = dot_desc(cand, q, K, E, sigmoid);
     return run_pipeline(&m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, scores, s, side);
+}
+
+DotRowsPlan dot_rows_plan(void* ws, int64_t E, int64_t n, int K, bool sigmoid) {
+    DotRowsPlan w;
+    size_t off = 0;
+    char* base = (char*)ws;
+    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += align256(b); return p; };
+    w.cand = (float*)take((size_t)E * K * 4);
+    w.qrows = (float*)take((size_t)2 * n * K * 4);
+    w.pipe_bytes = dot_eval_workspace_bytes(n, K, E, sigmoid);
+    w.pipe = take(w.pipe_bytes);
+    w.bytes = off;
+    return w;
 }
 
 static kge_model_desc head_rank_desc(const float* x, int dim, const float* ent, int64_t E, const float* bias) {

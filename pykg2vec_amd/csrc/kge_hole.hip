@@ -21,7 +21,6 @@ namespace kge {
 
 constexpr int kHoleMaxDim = 2048;
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int hole_waves(int d) { return d <= 256 ? 4 : 1; }
 // LDS floats: angle tables (2d) + per wave rows h, t, r^ (3d) and projections Ch, Sh, Ct, St, Cr, Sr (6d)
 static size_t hole_lds(int d) { return (size_t)(2 * d + 9 * d * hole_waves(d)) * sizeof(float); }
@@ -177,23 +176,24 @@ static int hole_run(const kge_model_desc* m, IdSplit h, IdSplit r, IdSplit t, in
     return check_launch("k_hole<forward>");
 }
 
+// (table signatures: HoLE needs no scorer workspace and ignores the one it is handed)
 int launch_hole_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
-                        hipStream_t s) {
+                        void*, size_t, hipStream_t s) {
     return hole_run(m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, scores, nullptr, s);
 }
 
 int launch_hole_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                         const float* dscore, hipStream_t s) {
+                         const float* dscore, void*, size_t, hipStream_t s) {
     return hole_run(m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, nullptr, dscore, s);
 }
 
 int launch_hole_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                             const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, hipStream_t s) {
+                             const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, void*, size_t, hipStream_t s) {
     return hole_run(m, IdSplit{ph, nh, n}, IdSplit{pr, nr, n}, IdSplit{pt, nt, n}, 2 * n, scores2, nullptr, s);
 }
 
 int launch_hole_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                              const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, hipStream_t s) {
+                              const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, void*, size_t, hipStream_t s) {
     return hole_run(m, IdSplit{ph, nh, n}, IdSplit{pr, nr, n}, IdSplit{pt, nt, n}, 2 * n, nullptr, dscore2, s);
 }
 
@@ -257,24 +257,8 @@ __global__ __launch_bounds__(256) void k_hole_queries(const float* __restrict__ 
     }
 }
 
-struct HoleEvalWs { float *cand, *qrows; void* pipe; size_t pipe_bytes, bytes; };
-
-static void hole_eval_plan(const kge_model_desc* m, int64_t n, void* ws, HoleEvalWs* w) {
-    const int K = 2 * m->dim;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += a256(b); return p; };
-    w->cand = (float*)take((size_t)m->tot_entity * K * 4);
-    w->qrows = (float*)take((size_t)2 * n * K * 4);
-    w->pipe_bytes = dot_eval_workspace_bytes(n, K, m->tot_entity, true);
-    w->pipe = take(w->pipe_bytes);
-    w->bytes = off;
-}
-
 size_t hole_eval_workspace_bytes(const kge_model_desc* m, int64_t n) {
-    HoleEvalWs w;
-    hole_eval_plan(m, n, nullptr, &w);
-    return w.bytes;
+    return dot_rows_plan(nullptr, m->tot_entity, n, 2 * m->dim, true).bytes;
 }
 
 static void hole_eval_lds_attr() {
@@ -291,8 +275,7 @@ int launch_hole_eval(const kge_model_desc* m, const int64_t* triples, int64_t n,
                      const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
                      float* scores, hipStream_t s, int side) {
     if (hole_check(m, "kge_eval")) return -1;
-    HoleEvalWs w;
-    hole_eval_plan(m, n, ws, &w);
+    const DotRowsPlan w = dot_rows_plan(ws, m->tot_entity, n, 2 * m->dim, true);
     if (!ws || ws_bytes < w.bytes) { set_error("kge_eval (HoLE): workspace too small (%zu < %zu)", ws_bytes, w.bytes); return -1; }
     if (n <= 0) return 0;
     hole_eval_lds_attr();

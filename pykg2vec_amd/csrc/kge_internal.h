@@ -17,7 +17,43 @@
 namespace kge {
 
 void set_error(const char* fmt, ...);
-bool is_vector_model(int model);  // models handled by the gather/row kernels (everything but RESCAL, NTN, TransR, SLM, SME, HoLE, OctonionE)
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // every carved workspace region starts on 256 bytes
+
+// kge_models.hip -- ONE row per kge_model id says which launchers serve it; the entry points of kge_api.hip and kge_eval.hip look
+// the row up and call through it.  A new model is one row there plus its launchers.  The function types below are also what
+// the per-model launchers are declared with further down, so a launcher that is in the table has the table's signature.
+typedef size_t WsBytesFn(const kge_model_desc* m, int64_t n);
+typedef int ScoreFwdFn(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
+                       void* ws, size_t ws_bytes, hipStream_t s);
+typedef int ScoreBwdFn(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, const float* dscore,
+                       void* ws, size_t ws_bytes, hipStream_t s);
+// both sides of the fused pairwise step as ONE batch of 2n triples: scores2 / dscore2 [2n], positives first
+typedef int PairFwdFn(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                      const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, void* ws, size_t ws_bytes, hipStream_t s);
+typedef int PairBwdFn(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                      const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, void* ws, size_t ws_bytes, hipStream_t s);
+// the whole pairwise step at once where the shape allows; returns 1 when not taken (as launch_selfadv_bundle does).
+// ws_bytes: the scorer part of the workspace (2 per-side workspaces), total_bytes: all of the caller's workspace
+typedef int PairFastFn(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                       const int64_t* nr, const int64_t* nt, int64_t n, float margin, float* loss, void* ws, size_t ws_bytes,
+                       size_t total_bytes, hipStream_t s);
+// filtered ranks [4, n] (+ ties [2, n] or NULL) when scores == NULL, else the sweep's energies: [2n, E] for side 2, [n, E] for side 0 / 1
+typedef int EvalFn(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                   const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
+                   float* scores, hipStream_t s, int side);
+struct ModelOps {
+    int tables, grads;        // parameter tables / gradient buffers the descriptor must carry
+    bool row_kernels;         // served by the gather / row kernels of kge_score*.hip (fused steps included)
+    WsBytesFn* scorer_ws;     // per-side scorer workspace; NULL: none
+    ScoreFwdFn* forward;      // NULL: launch_score_forward
+    ScoreBwdFn* backward;     // NULL: launch_score_backward
+    PairFwdFn* pair_forward;  // the pairwise hinge step of the models without row kernels: forward, launch_hinge_coeffs, backward
+    PairBwdFn* pair_backward;
+    PairFastFn* pair_fast;    // optional, tried first
+    WsBytesFn* eval_ws;       // NULL: the generic sweep pipeline of kge_eval.hip
+    EvalFn* eval;
+};
+const ModelOps* model_ops(int model);   // NULL for an unknown id
 
 // (G, NCH) geometry for a row length; returns false when the row is too long for the register-resident kernels
 struct Geometry { int G, NCH; };
@@ -99,11 +135,9 @@ int launch_pointwise_logistic_sampled_staged(const kge_model_desc* m, const int6
                                              int64_t n_slots, uint64_t seed, uint64_t offset, float lmbda, int reg_type,
                                              float* loss, const StageSink& sink, hipStream_t s);
 // kge_score_generic.hip: generic (roles-table) tail of the sampler-fused hinge step, after the shared-row specialisations
-struct FusedSampler;
 int launch_pairwise_hinge_sampled_generic(const kge_model_desc* m, Geometry geo, const FusedSampler& fs, int64_t n,
                                           float margin, float* loss, hipStream_t s);
 // kge_score_ext.hip: the same generic kernels instantiated for TransM / CP / SimplE / SimplE_ignr / QuatE
-struct FusedSampler;
 int launch_score_forward_ext(const kge_model_desc* m, Geometry geo, const int64_t* h, const int64_t* r, const int64_t* t,
                              int64_t n, float* scores, hipStream_t s);
 int launch_score_backward_ext(const kge_model_desc* m, Geometry geo, const int64_t* h, const int64_t* r, const int64_t* t,
@@ -120,46 +154,19 @@ int launch_selfadv_coeffs(float* pos_scores, float* neg_scores, int64_t n_pos, i
 // kge_dense.hip (RESCAL / NTN: f32 MFMA contraction paths) + table normalisation
 int launch_rescal_normalize(float* ent, int64_t E, float* rel, int64_t R, int k, float* scratch, size_t scratch_floats,
                             hipStream_t s);
-size_t dense_workspace_bytes(const kge_model_desc* m, int64_t n);
-size_t ntn_workspace_bytes(const kge_model_desc* m, int64_t n);
 int launch_l2norm_reg(const float* param, float* grad, int64_t numel, float lmbda, float* scratch, float* loss, hipStream_t s);
-int launch_rescal_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t,
-                          int64_t n, float* scores, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_rescal_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t,
-                           int64_t n, const float* dscore, void* ws, size_t ws_bytes, bool grouped, hipStream_t s);
-int launch_ntn_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                            const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, void* ws, size_t ws_bytes,
-                            hipStream_t s);
-int launch_ntn_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                             const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, void* ws, size_t ws_bytes,
-                             hipStream_t s);
-int launch_transr_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
-                               const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, void* ws,
-                               size_t ws_bytes, hipStream_t s);
-int launch_transr_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
-                                const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2,
-                                void* ws, size_t ws_bytes, hipStream_t s);
-int launch_rescal_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
-                               const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, void* ws,
-                               size_t ws_bytes, hipStream_t s);
-int launch_rescal_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
-                                const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2,
-                                void* ws, size_t ws_bytes, hipStream_t s);
-int launch_ntn_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t,
-                       int64_t n, float* scores, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_ntn_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t,
-                        int64_t n, const float* dscore, void* ws, size_t ws_bytes, bool forward_in_ws, hipStream_t s);
+WsBytesFn rescal_workspace_bytes, ntn_workspace_bytes;
+ScoreFwdFn launch_rescal_forward, launch_ntn_forward;
+ScoreBwdFn launch_rescal_backward, launch_ntn_backward;
+PairFwdFn launch_rescal_pair_forward, launch_ntn_pair_forward, launch_transr_pair_forward;
+PairBwdFn launch_rescal_pair_backward, launch_ntn_pair_backward, launch_transr_pair_backward;
+PairFastFn rescal_pair_fast, transr_pair_fast;
 // kge_transr_rows.hip: the pairwise TransR step of large batches (negatives keep their positives' relations) in two launches
 size_t transr_rows_ws_bytes(const kge_model_desc* m, int64_t n);
-bool transr_rows_ok(const kge_model_desc* m, int64_t n, size_t ws_bytes);
-int launch_transr_pair_step(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                            const int64_t* nt, int64_t n, float margin, float* loss, void* ws, size_t ws_bytes, hipStream_t s);
 // kge_transr.hip
-size_t transr_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_transr_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t,
-                          int64_t n, float* scores, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_transr_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t,
-                           int64_t n, const float* dscore, void* ws, size_t ws_bytes, bool grouped, hipStream_t s);
+WsBytesFn transr_workspace_bytes;
+ScoreFwdFn launch_transr_forward;
+ScoreBwdFn launch_transr_backward;
 int launch_transr_eval_prepare(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* group_rel,
                                int64_t n_groups, int Kpad, int64_t ntiles, float* cand, float* qvec, float* qscale,
                                hipStream_t s);
@@ -282,68 +289,28 @@ size_t dot_eval_workspace_bytes(int64_t n, int K, int64_t E, bool sigmoid = fals
 int launch_dot_eval(const float* cand, const float* q, int K, int64_t E, const int64_t* triples, int64_t n, const int64_t* tail_off,
                     const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes,
                     int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side, bool sigmoid = false);
+// Workspace of a model that ranks through launch_dot_eval over rows it builds itself: cand [E, K], qrows [2n, K] and the sweep's
+// own workspace, carved in this order (ws == NULL: the pointers are NULL, the sizes are the query's answer)
+struct DotRowsPlan { float* cand; float* qrows; void* pipe; size_t pipe_bytes, bytes; };
+DotRowsPlan dot_rows_plan(void* ws, int64_t E, int64_t n, int K, bool sigmoid = false);
 
-// kge_hole.hip (HoLE)
-int launch_hole_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
-                        hipStream_t s);
-int launch_hole_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                         const float* dscore, hipStream_t s);
-int launch_hole_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                             const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, hipStream_t s);
-int launch_hole_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                              const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, hipStream_t s);
-size_t hole_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_hole_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
-                     const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
-                     float* scores, hipStream_t s, int side);
-
-// kge_octonion.hip (OctonionE: component-block tables, include/kge_hip.h)
-int launch_octonion_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
-                            hipStream_t s);
-int launch_octonion_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                             const float* dscore, hipStream_t s);
+// kge_hole.hip (HoLE), kge_octonion.hip (OctonionE: component-block tables, include/kge_hip.h), kge_kg2e_eval.hip (KG2E rank),
+// kge_semantic.hip (SLM / SME / SME_BL), kge_ntn_eval.hip: the launchers of the model table
+ScoreFwdFn launch_hole_forward, launch_octonion_forward, launch_semantic_forward;
+ScoreBwdFn launch_hole_backward, launch_octonion_backward, launch_semantic_backward;
+PairFwdFn launch_hole_pair_forward, launch_semantic_pair_forward;
+PairBwdFn launch_hole_pair_backward, launch_semantic_pair_backward;
+WsBytesFn semantic_workspace_bytes;
+WsBytesFn hole_eval_workspace_bytes, octonion_eval_workspace_bytes, kg2e_eval_workspace_bytes, semantic_eval_workspace_bytes,
+          ntn_eval_workspace_bytes;
+EvalFn launch_hole_eval, launch_octonion_eval, launch_kg2e_eval, launch_semantic_eval, launch_ntn_eval;
 int launch_octonion_pointwise(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, const int64_t* y,
                               int64_t n, int bundle, float lmbda, int reg_type, float* loss, hipStream_t s);
 int launch_octonion_pointwise_sampled(const kge_model_desc* m, const int64_t* triples, const int64_t* perm, int64_t start,
                                       int64_t n_pos, int neg_rate, const float* bern, const uint64_t* slots, int64_t n_slots,
                                       uint64_t seed, uint64_t offset, const int64_t* cursor, float lmbda, int reg_type, float* loss,
                                       hipStream_t s);
-size_t octonion_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_octonion_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
-                         const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
-                         float* scores, hipStream_t s, int side);
-
-// kge_kg2e_eval.hip (KG2E rank)
-size_t kg2e_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_kg2e_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
-                     const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
-                     float* scores, hipStream_t s, int side);
-
-// kge_semantic.hip (SLM / SME / SME_BL)
-size_t semantic_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_semantic_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                            float* scores, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_semantic_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                             const float* dscore, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_semantic_pair_forward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
-                                 const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, float* scores2, void* ws,
-                                 size_t ws_bytes, hipStream_t s);
-int launch_semantic_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt,
-                                  const int64_t* nh, const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2,
-                                  void* ws, size_t ws_bytes, hipStream_t s);
-size_t semantic_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_semantic_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off,
-                         const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes,
-                         int32_t* ranks, int32_t* ties, float* scores, hipStream_t s, int side);
 inline bool is_semantic_model(int model) { return model == KGE_SLM || model == KGE_SME || model == KGE_SME_BL; }
-
-// kge_ntn_eval.hip
-size_t ntn_eval_workspace_bytes(const kge_model_desc* m, int64_t n);
-int launch_ntn_eval_ranks(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off,
-                          const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws,
-                          size_t ws_bytes, int32_t* ranks, hipStream_t s);
-int launch_ntn_eval_scores(const kge_model_desc* m, const int64_t* triples, int64_t n, void* ws, size_t ws_bytes,
-                           float* scores, hipStream_t s);
 
 // kge_head.hip (1-N scoring head of the projection models)
 int launch_head_forward(const float* x, int64_t B, int d, const float* ent, int64_t E, const float* bias, float* preds,

@@ -16,8 +16,6 @@ namespace kge {
 constexpr int kKg2eMaxDim = 2048;
 constexpr int kKg2eChunk = 256;   // test triples per scored chunk
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Kg2eEvalWs {
     float *cmu, *csg, *clog, *q4, *qc, *scores;
     int64_t* truth;
@@ -28,7 +26,7 @@ struct Kg2eEvalWs {
 static void kg2e_eval_plan(const kge_model_desc* m, int64_t n, void* ws, Kg2eEvalWs* w, int ns) {
     size_t off = 0;
     char* base = (char*)ws;
-    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += a256(b); return p; };
+    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += align256(b); return p; };
     const int64_t E = m->tot_entity;
     const int d = m->dim;
     w->chunk = (int)(n < kKg2eChunk ? (n < 1 ? 1 : n) : kKg2eChunk);

@@ -856,8 +856,8 @@ static int ntn_backward_core(const kge_model_desc* m, IdSplit h, IdSplit r, IdSp
                              size_t ws_bytes, bool forward_in_ws, hipStream_t s);
 
 int launch_ntn_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                        const float* dscore, void* ws, size_t ws_bytes, bool forward_in_ws, hipStream_t s) {
-    return ntn_backward_core(m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, dscore, ws, ws_bytes, forward_in_ws, s);
+                        const float* dscore, void* ws, size_t ws_bytes, hipStream_t s) {
+    return ntn_backward_core(m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, dscore, ws, ws_bytes, false, s);
 }
 int launch_ntn_pair_backward(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
                              const int64_t* nr, const int64_t* nt, int64_t n, const float* dscore2, void* ws, size_t ws_bytes,

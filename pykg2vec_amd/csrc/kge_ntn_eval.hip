@@ -27,8 +27,6 @@ struct NtnEvalWs {
     size_t bytes;
 };
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static void ntn_eval_plan(const kge_model_desc* m, int64_t n, void* ws, NtnEvalWs* w, bool want_all_scores) {
     const int d = m->dim, kr = m->rel_dim;
     w->Kpad = (d + 7) / 8 * 8;
@@ -38,7 +36,7 @@ static void ntn_eval_plan(const kge_model_desc* m, int64_t n, void* ws, NtnEvalW
     w->ntiles = (m->tot_entity + 63) / 64;
     size_t off = 0;
     char* base = (char*)ws;
-    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += a256(b); return p; };
+    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += align256(b); return p; };
     const int64_t E = m->tot_entity, C = w->chunk;
     w->cand = (float*)take((size_t)w->ntiles * w->Kpad * 64 * 4);
     w->EM1 = (float*)take((size_t)E * w->krp * 4);
@@ -307,15 +305,13 @@ static int ntn_eval_common(const kge_model_desc* m, const int64_t* triples, int6
     return check_launch("NTN sweep");
 }
 
-int launch_ntn_eval_ranks(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off,
-                          const int32_t* tail_ids, const int64_t* head_off, const int32_t* head_ids, void* ws,
-                          size_t ws_bytes, int32_t* ranks, hipStream_t s) {
-    return ntn_eval_common(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, nullptr, s);
-}
-
-int launch_ntn_eval_scores(const kge_model_desc* m, const int64_t* triples, int64_t n, void* ws, size_t ws_bytes,
-                           float* scores, hipStream_t s) {
-    return ntn_eval_common(m, triples, n, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, scores, s);
+// (the NTN sweep computes both sides per call and does not count ties: they are reported as unknown, -1)
+int launch_ntn_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                    const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
+                    float* scores, hipStream_t s, int side) {
+    if (side != 2) { set_error("kge_eval_sweep_scores_side: the NTN sweep computes both sides per call"); return -1; }
+    if (ties) (void)hipMemsetAsync(ties, 0xFF, (size_t)2 * n * sizeof(int32_t), s);
+    return ntn_eval_common(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, scores, s);
 }
 
 }  // namespace kge

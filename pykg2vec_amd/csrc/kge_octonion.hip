@@ -321,7 +321,6 @@ __global__ __launch_bounds__(kBlock) void k_oct_pointwise(OctArgs a, const int64
 }
 
 // ---------------------------------------------------------------- host side
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t roundup4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 static int oct_group(int d) { return d <= 256 ? 32 : 64; }   // the lane group: also the most negatives a sampled bundle may draw
 
@@ -364,13 +363,14 @@ static int oct_score(const kge_model_desc* m, const int64_t* h, const int64_t* r
     return check_launch("k_oct_score<forward>");
 }
 
+// (table signatures: no scorer workspace, the one handed in is ignored)
 int launch_octonion_forward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
-                            hipStream_t s) {
+                            void*, size_t, hipStream_t s) {
     return oct_score(m, h, r, t, n, scores, nullptr, s);
 }
 
 int launch_octonion_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                             const float* dscore, hipStream_t s) {
+                             const float* dscore, void*, size_t, hipStream_t s) {
     return oct_score(m, h, r, t, n, nullptr, dscore, s);
 }
 
@@ -447,24 +447,9 @@ __global__ __launch_bounds__(kBlock) void k_oct_queries(OctArgs a, const int64_t
     }
 }
 
-struct OctEvalWs { float *cand, *qrows; void* pipe; size_t pipe_bytes, bytes; };
-
-static void oct_eval_plan(const kge_model_desc* m, int64_t n, void* ws, OctEvalWs* w) {
-    const int K = 8 * m->dim;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += a256(b); return p; };
-    w->cand = (float*)take((size_t)m->tot_entity * K * 4);
-    w->qrows = (float*)take((size_t)2 * n * K * 4);
-    w->pipe_bytes = dot_eval_workspace_bytes(n, K, m->tot_entity);
-    w->pipe = take(w->pipe_bytes);
-    w->bytes = off;
-}
-
 size_t octonion_eval_workspace_bytes(const kge_model_desc* m, int64_t n) {
     if (m->dim > kOctMaxDim) return 0;
-    OctEvalWs w;
-    oct_eval_plan(m, n, nullptr, &w);
+    const DotRowsPlan w = dot_rows_plan(nullptr, m->tot_entity, n, 8 * m->dim);
     return w.pipe_bytes ? w.bytes : 0;
 }
 
@@ -472,8 +457,7 @@ int launch_octonion_eval(const kge_model_desc* m, const int64_t* triples, int64_
                          const int64_t* head_off, const int32_t* head_ids, void* ws, size_t ws_bytes, int32_t* ranks, int32_t* ties,
                          float* scores, hipStream_t s, int side) {
     if (oct_check(m, "kge_eval")) return -1;
-    OctEvalWs w;
-    oct_eval_plan(m, n, ws, &w);
+    const DotRowsPlan w = dot_rows_plan(ws, m->tot_entity, n, 8 * m->dim);
     if (!ws || ws_bytes < w.bytes) { set_error("kge_eval (OctonionE): workspace too small (%zu < %zu)", ws_bytes, w.bytes); return -1; }
     if (n <= 0) return 0;
     const OctArgs a = oct_args(m);

@@ -411,19 +411,18 @@ __global__ __launch_bounds__(256, 2) void k_rescal_slab_bwd(SlabArgs a) {
     SLAB_TS(1, 8)
 }
 
-static size_t align256s(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t slab_tiles(int64_t R, int64_t n) { return n / kSlabChunk + R + 1; }   // >= sum_r ceil(n_r / kSlabChunk)
 
 // layout of the slab form's workspace: tile descriptors | grouped ids | V rows | energy shares
 size_t rescal_slab_ws_bytes(int k, int64_t R, int64_t n) {
     const int n_slab = (k + 31) / 32;
-    return align256s((size_t)slab_tiles(R, n) * sizeof(int4)) + align256s((size_t)n * sizeof(int4)) +
-           align256s(((size_t)2 * n * k + (size_t)n_slab * 2 * n) * sizeof(float));
+    return align256((size_t)slab_tiles(R, n) * sizeof(int4)) + align256((size_t)n * sizeof(int4)) +
+           align256(((size_t)2 * n * k + (size_t)n_slab * 2 * n) * sizeof(float));
 }
 
 void rescal_slab_gather(void* ws_slab, int k, int64_t R, int64_t n, PairGather* pg) {
     pg->tdesc = (int4*)ws_slab;
-    pg->gids = (int4*)((char*)ws_slab + align256s((size_t)slab_tiles(R, n) * sizeof(int4)));
+    pg->gids = (int4*)((char*)ws_slab + align256((size_t)slab_tiles(R, n) * sizeof(int4)));
 }
 
 // the grouping (kSlabChunk pairs per tile, with the PairGather of rescal_slab_gather) has been enqueued on s before this call
@@ -441,7 +440,7 @@ int launch_rescal_slab_step(const kge_model_desc* m, int64_t n, const GroupWs& g
     a.gstage = stage ? stage->gstage : nullptr; a.dsv = stage ? stage->dsv : nullptr;
     a.st_count = stage ? stage->count : nullptr; a.st_bucket = stage ? stage->bucket : nullptr;
     a.st_head = stage ? stage->head : nullptr; a.st_next = stage ? stage->next : nullptr; a.st_cap = stage ? stage->cap : 0;
-    a.wsV = (float*)((char*)pg.gids + align256s((size_t)n * sizeof(int4)));
+    a.wsV = (float*)((char*)pg.gids + align256((size_t)n * sizeof(int4)));
     a.wsP = a.wsV + (size_t)2 * n * k;
     const unsigned grid = (unsigned)((slab_tiles(R, n) + 7) / 8 * 8 * a.n_slab);
     const bool v4 = (k & 3) == 0 && (reinterpret_cast<uintptr_t>(m->tables[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(m->tables[1]) & 15) == 0;

@@ -45,7 +45,6 @@ constexpr int kChunks = 128;     // partial slots of the shared-matrix gradients
 constexpr int kSub = 32;         // triples per LDS stage of k_sem_wgrad
 constexpr int kSlmChunk = 256;   // SLM eval: test triples per scored chunk
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 static bool is_sme(int model) { return model == KGE_SME || model == KGE_SME_BL; }
 
 // ---------------------------------------------------------------- shapes and workspace
@@ -75,7 +74,7 @@ static SemWs sem_carve(const SemShape& s, int64_t N2, void* ws) {
     SemWs w;
     size_t off = 0;
     char* base = (char*)ws;
-    auto take = [&](size_t b) { float* p = base ? (float*)(base + off) : nullptr; off += a256(b); return p; };
+    auto take = [&](size_t b) { float* p = base ? (float*)(base + off) : nullptr; off += align256(b); return p; };
     w.inv = take((size_t)3 * N2 * sizeof(float));
     w.prod = take((size_t)s.nslot * s.sw * N2 * sizeof(float));
     w.part = take((size_t)kChunks * s.wsize * sizeof(float));
@@ -666,7 +665,7 @@ struct SlmEvalWs { float *P1, *P2, *qlin, *qr, *scores; int64_t* truth; int32_t 
 static void slm_eval_plan(const kge_model_desc* m, int64_t n, void* ws, SlmEvalWs* w) {
     size_t off = 0;
     char* base = (char*)ws;
-    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += a256(b); return p; };
+    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += align256(b); return p; };
     const int64_t E = m->tot_entity;
     const int kr = m->rel_dim;
     w->chunk = (int)(n < kSlmChunk ? (n < 1 ? 1 : n) : kSlmChunk);
@@ -813,25 +812,9 @@ static int slm_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, 
 }
 
 // ---------------------------------------------------------------- host side: rank entry points (called from kge_eval.hip)
-struct SmeEvalWs { float *cand, *qrows; void* pipe; size_t pipe_bytes, bytes; };
-
-static void sme_eval_plan(const kge_model_desc* m, int64_t n, void* ws, SmeEvalWs* w) {
-    const int K = m->dim + 1;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t b) { char* p = base ? base + off : nullptr; off += a256(b); return p; };
-    w->cand = (float*)take((size_t)m->tot_entity * K * 4);
-    w->qrows = (float*)take((size_t)2 * n * K * 4);
-    w->pipe_bytes = dot_eval_workspace_bytes(n, K, m->tot_entity);
-    w->pipe = take(w->pipe_bytes);
-    w->bytes = off;
-}
-
 size_t semantic_eval_workspace_bytes(const kge_model_desc* m, int64_t n) {
     if (m->model == KGE_SLM) { SlmEvalWs w; slm_eval_plan(m, n, nullptr, &w); return w.bytes; }
-    SmeEvalWs w;
-    sme_eval_plan(m, n, nullptr, &w);
-    return w.bytes;
+    return dot_rows_plan(nullptr, m->tot_entity, n, m->dim + 1).bytes;
 }
 
 int launch_semantic_eval(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* tail_off,
@@ -842,8 +825,7 @@ int launch_semantic_eval(const kge_model_desc* m, const int64_t* triples, int64_
         if (side != 2) { set_error("kge_eval_sweep_scores_side: the SLM sweep computes both sides per call"); return -1; }
         return slm_eval(m, triples, n, tail_off, tail_ids, head_off, head_ids, ws, ws_bytes, ranks, ties, scores, s);
     }
-    SmeEvalWs w;
-    sme_eval_plan(m, n, ws, &w);
+    const DotRowsPlan w = dot_rows_plan(ws, m->tot_entity, n, m->dim + 1);
     if (!ws || ws_bytes < w.bytes) { set_error("kge_eval (SME): workspace too small (%zu < %zu)", ws_bytes, w.bytes); return -1; }
     if (n <= 0) return 0;
     const int64_t E = m->tot_entity;

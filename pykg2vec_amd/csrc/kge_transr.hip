@@ -315,8 +315,8 @@ int launch_transr_forward(const kge_model_desc* m, const int64_t* h, const int64
     return transr_run(0, m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, nullptr, scores, ws, ws_bytes, false, s);
 }
 int launch_transr_backward(const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
-                           const float* dscore, void* ws, size_t ws_bytes, bool grouped, hipStream_t s) {
-    return transr_run(1, m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, dscore, nullptr, ws, ws_bytes, grouped, s);
+                           const float* dscore, void* ws, size_t ws_bytes, hipStream_t s) {
+    return transr_run(1, m, id_whole(h, n), id_whole(r, n), id_whole(t, n), n, dscore, nullptr, ws, ws_bytes, false, s);
 }
 
 // positives and negatives of the fused pairwise step as ONE grouped batch of 2n triples (see launch_rescal_pair_forward)

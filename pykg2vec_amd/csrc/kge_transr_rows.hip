@@ -713,7 +713,7 @@ size_t transr_rows_ws_bytes(const kge_model_desc* m, int64_t n) {
     return gi + (size_t)4 * n * (m->rel_dim + 1) * sizeof(float);
 }
 
-bool transr_rows_ok(const kge_model_desc* m, int64_t n, size_t ws_bytes) {
+static bool transr_rows_ok(const kge_model_desc* m, int64_t n, size_t ws_bytes) {
     if (!(m->dim >= 1 && m->rel_dim >= 1 && m->dim <= 128 && m->rel_dim <= 128 && n >= 1 && n < (1ll << 29) &&
           ws_bytes >= transr_rows_ws_bytes(m, n)))
         return false;
@@ -760,8 +760,8 @@ static bool launch_transr_rows_nb(const TransRRowsArgs& a, unsigned tiles, hipSt
 }
 
 // negatives share pr (the caller passed nr == pr); ws: the pairwise step's scorer workspace
-int launch_transr_pair_step(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
-                            const int64_t* nt, int64_t n, float margin, float* loss, void* ws, size_t ws_bytes, hipStream_t s) {
+static int launch_transr_pair_step(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                                   const int64_t* nt, int64_t n, float margin, float* loss, void* ws, size_t ws_bytes, hipStream_t s) {
     if (!transr_rows_ok(m, n, ws_bytes)) { set_error("TransR pair step: unsupported shape or workspace"); return -1; }
     const int64_t R = m->tot_relation;
     const GroupWs g = carve_group_ws(ws, R, n);       // (tile_rel, the last array, holds n / 16 + R + 1 entries here)
@@ -793,6 +793,18 @@ int launch_transr_pair_step(const kge_model_desc* m, const int64_t* ph, const in
     }
     if (!ok) return -1;
     return check_launch("k_transr_rows / k_transr_g");
+}
+
+static const int64_t kTransRRowsMinPairs = 1;      // the two-launch step wins at every batch size measured (128 ... 32 768 pairs: profiles/r04_transr_threshold.txt)
+
+// The pairwise hinge step's shortcut: nr == pr (one buffer) takes the two-launch step above (KGE_TRANSR_ROWS=0: the tile kernels)
+int transr_pair_fast(const kge_model_desc* m, const int64_t* ph, const int64_t* pr, const int64_t* pt, const int64_t* nh,
+                     const int64_t* nr, const int64_t* nt, int64_t n, float margin, float* loss, void* ws, size_t ws_bytes, size_t,
+                     hipStream_t s) {
+    const int rows_sw = switch_value("TRANSR_ROWS");
+    if (nr == pr && rows_sw != 0 && (rows_sw >= 1 || n >= kTransRRowsMinPairs) && transr_rows_ok(m, n, ws_bytes))
+        return launch_transr_pair_step(m, ph, pr, pt, nh, nt, n, margin, loss, ws, ws_bytes, s);
+    return 1;
 }
 
 }  // namespace kge

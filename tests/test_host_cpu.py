@@ -276,6 +276,41 @@ def test_new_entry_points_validate_arguments_without_gpu():
     assert b"exceed the LDS-resident tile kernel" in lib.kge_last_error()
 
 
+def test_host_answers_of_every_model_equal_the_recorded_ones(golden_dir, monkeypatch):
+    """Workspace sizes (byte for byte) and the refusals issued before the first HIP call (return code and text), for all 21
+    model ids, equal what tools/host_answers.py recorded from the library of the commit named in the fixture, which routed
+    models through per-entry-point ladders.  A refusal's text names the launcher that refused, so equal texts are equal routes:
+    per model, the scorer (kge_score_forward / _backward), the pair step (kge_train_pairwise_hinge) and the rank (kge_eval_ranks,
+    kge_eval_sweep_scores_side) are each reached at least once.  Out of reach without a launch, and left to the GPU tests: the
+    backward half of the pair step (the forward half launches first), a RESCAL / TransR shortcut that is taken, and the scorers
+    of HoLE and OctonionE at a valid hidden size."""
+    import json
+    from tools import host_answers
+    monkeypatch.delenv("KGE_DEBUG_IDS", raising=False)
+    want = json.load(open(os.path.join(golden_dir, "host_answers.json")))
+    got = host_answers.collect()
+    assert want["recorded_from"] == host_answers.RECORDED_FROM
+    assert len(got["sizes"]) == len(want["sizes"]) and len(got["refusals"]) == len(want["refusals"])
+    for g, w in zip(got["sizes"], want["sizes"]):
+        assert g == w, (g, w)
+    for g, w in zip(got["refusals"], want["refusals"]):
+        assert g == w, (g, w)
+    # the fixture holds what the test claims: every shape and model, rel_dim != dim, a hidden size that is no multiple of 4 ...
+    assert {r["model"] for r in want["sizes"]} == set(host_answers.MODELS) and len(host_answers.MODELS) == 21
+    assert {(r["E"], r["R"], r["dim"], r["n"]) for r in want["sizes"]} >= {(1000, 20, 32, 64), (14951, 1345, 100, 1024)}
+    assert any(r["dim"] % 4 for r in want["sizes"])
+    assert {r["model"] for r in want["sizes"] if r["rel_dim"] != r["dim"]} == {"transr", "ntn", "slm"}
+    assert all(("eval_grouped_workspace" in r) == (r["model"] in ("transh", "transd", "transr")) for r in want["sizes"])
+    assert all(r["workspace"] > 0 for r in want["sizes"] if r["model"] in ("rescal", "ntn", "transr", "slm", "sme", "sme_bl", "hole"))
+    assert all(r["eval_workspace"] > 0 for r in want["sizes"] if not (r["model"] == "analogy" and r["dim"] % 2))
+    # ... and every (routed entry point, model) pair
+    reached = {(r["entry"], r["model"]) for r in want["refusals"]}
+    entries = ("kge_score_forward", "kge_score_backward", "kge_train_pairwise_hinge", "kge_train_pointwise_logistic",
+               "kge_eval_ranks", "kge_eval_sweep_scores_side")
+    assert reached == {(e, m) for e in entries for m in host_answers.MODELS}
+    assert all(r["rc"] == -1 and r["error"] for r in want["refusals"])
+
+
 def test_pull_plan_struct_layout_matches_the_library():
     """struct kge_pull_plan is filled by the Python binding and read by kge_pull_run: the layouts must agree."""
     from pykg2vec_amd import _lib
