@@ -783,6 +783,73 @@ int kge_head_1n_bce(const float* x, int64_t batch, int32_t dim, const float* ent
                     void* workspace, size_t workspace_bytes, float* loss, float* dx, float* g_ent, float* g_bias,
                     void* stream);
 
+/* ---- ConvKB (models/pointwise.py:241-318) as the reference executes it: the convolutions feed fc1 with no activation and no dropout
+ * in between, so the score is affine in the three gathered rows (csrc/kge_convkb.hip):
+ *     preds(h, r, t) = c0 + <A_h, ent[h]> + <A_r, rel[r]> + <A_t, ent[t]>,
+ *     W = sum_j (dim - widths[j] + 1),  off_j = sum_{i<j} (dim - widths[i] + 1),
+ *     A_row[d] = sum_j sum_f sum_{c < s_j, 0 <= d-c <= dim-s_j} conv_j.weight[f,0,row,c] * fc1.weight[0, f*W + off_j + d - c],
+ *     c0       = fc1.bias + sum_j sum_f conv_j.bias[f] * sum_p fc1.weight[0, f*W + off_j + p].
+ * The model has no kge_model id: the filter geometry does not fit kge_model_desc, so it has its own descriptor and entry points.
+ * conv_w: the flattened conv_list[j].weight tensors concatenated in list order (block j: num_filters*3*widths[j] floats, [f][row][c]);
+ * conv_b: the concatenated conv_list[j].bias tensors (n_widths*num_filters floats).  The filters are FIXED inputs: the reference keeps
+ * conv_list in a plain list, so they are in no optimiser and no checkpoint.  The trainable tensors are ent, rel, fc_w (fc1.weight) and
+ * fc_b (fc1.bias); their dense gradients are accumulated into g_*.  The fc1 gradients are sums in a fixed order: bit-identical run to
+ * run.  Every entry point takes a caller-owned workspace (its own *_workspace_bytes; 0 = the descriptor is refused) and runs the
+ * collapse itself, on the same stream.  Refused before any launch, with the entry point's name in kge_last_error(): null tables,
+ * n_widths outside 1..KGE_CONVKB_MAX_WIDTHS, a width < 1 or > dim, num_filters < 1, a workspace that is too small. */
+#define KGE_CONVKB_MAX_WIDTHS 8
+typedef struct kge_convkb_desc {
+    int64_t tot_entity, tot_relation;
+    int32_t dim, num_filters, n_widths;
+    int32_t widths[KGE_CONVKB_MAX_WIDTHS]; /* conv_list order: it fixes off_j */
+    const float *ent, *rel;                /* [E,k], [R,k] */
+    const float *fc_w, *fc_b;              /* [F*W], [1] */
+    const float *conv_w, *conv_b;          /* fixed inputs: see above */
+    float *g_ent, *g_rel, *g_fc_w, *g_fc_b; /* dense grads, may be NULL for forward */
+} kge_convkb_desc;
+
+/* out: 3*dim + 1 floats = A_h | A_r | A_t | c0.  Needs no workspace (the query answers 0; the arguments are ignored). */
+size_t kge_convkb_collapse_workspace_bytes(const kge_convkb_desc* d);
+int kge_convkb_collapse(const kge_convkb_desc* d, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ConvKB.forward(h, r, t) -> preds[n] and its autograd backward (g_* += d(sum_i dscore[i] * preds_i) / d tensor), as
+ * kge_score_forward / kge_score_backward. */
+size_t kge_convkb_score_forward_workspace_bytes(const kge_convkb_desc* d, int64_t n);
+int kge_convkb_score_forward(const kge_convkb_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, float* scores,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t kge_convkb_score_backward_workspace_bytes(const kge_convkb_desc* d, int64_t n);
+int kge_convkb_score_backward(const kge_convkb_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
+                              const float* dscore, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fused Trainer.train_step_pointwise (utils/trainer.py:176-180) with Criterion.pointwise_logistic (utils/criterion.py:31-34):
+ * loss += mean(softplus(y * preds)), all four dense gradients.  Arguments as kge_train_pointwise_logistic; ConvKB has no regulariser
+ * (get_reg is the base class's 0.0). */
+size_t kge_convkb_train_logistic_workspace_bytes(const kge_convkb_desc* d, int64_t n);
+int kge_convkb_train_logistic(const kge_convkb_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, const int64_t* y,
+                              int64_t n, int32_t bundle, void* workspace, size_t workspace_bytes, float* loss, void* stream);
+
+/* The same step with the negative sampler fused in front: arguments and Philox counters of kge_train_pointwise_logistic_sampled, so
+ * kge_sample_batch(layout 1) + kge_convkb_train_logistic see the rows this call sees.  1 + neg_rate rows must fit the lane group (32,
+ * or 64 above 256 floats per row). */
+size_t kge_convkb_train_logistic_sampled_workspace_bytes(const kge_convkb_desc* d, int64_t n_pos, int32_t neg_rate);
+int kge_convkb_train_logistic_sampled(const kge_convkb_desc* d, const int64_t* triples, const int64_t* perm, int64_t start,
+                                      int64_t n_pos, int32_t neg_rate, const float* bern_prob, const uint64_t* slots,
+                                      int64_t n_slots, uint64_t seed, uint64_t offset, const int64_t* dev_cursor, void* workspace,
+                                      size_t workspace_bytes, float* loss, void* stream);
+
+/* Filtered and raw ranks, filter CSR arguments and `ranks` layout of kge_eval_ranks.  The order of the candidates does not depend on
+ * the query (tail candidates are ordered by <A_t, ent[e]>, head candidates by <A_h, ent[e]>): one pass over the entity table for both
+ * projections, then counting.  The energy of candidate e is the fp32 sum kge_convkb_sweep_scores_side stores, and the ranks equal
+ * kge_rank_from_scores over those rows exactly. */
+size_t kge_convkb_eval_ranks_workspace_bytes(const kge_convkb_desc* d, int64_t n);
+int kge_convkb_eval_ranks(const kge_convkb_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                          const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                          void* stream);
+/* As kge_eval_sweep_scores_side: scores float [n, E], side 0 = preds of (h_i, r_i, e), side 1 = preds of (e, r_i, t_i). */
+size_t kge_convkb_sweep_scores_side_workspace_bytes(const kge_convkb_desc* d, int64_t n);
+int kge_convkb_sweep_scores_side(const kge_convkb_desc* d, const int64_t* triples, int64_t n, int side, void* workspace,
+                                 size_t workspace_bytes, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

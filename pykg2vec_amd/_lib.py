@@ -121,7 +121,43 @@ class StagedStep(ctypes.Structure):
                 ("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("stage_spare", ctypes.c_int32)]
 
 
+CONVKB_MAX_WIDTHS = 8
+
+
+class ConvKBDesc(ctypes.Structure):
+    """struct kge_convkb_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("dim", ctypes.c_int32),
+                ("num_filters", ctypes.c_int32), ("n_widths", ctypes.c_int32), ("widths", ctypes.c_int32 * CONVKB_MAX_WIDTHS),
+                ("ent", ctypes.c_void_p), ("rel", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p),
+                ("conv_w", ctypes.c_void_p), ("conv_b", ctypes.c_void_p), ("g_ent", ctypes.c_void_p), ("g_rel", ctypes.c_void_p),
+                ("g_fc_w", ctypes.c_void_p), ("g_fc_b", ctypes.c_void_p)]
+
+
+_CKB = ctypes.POINTER(ConvKBDesc)
+
 _SIGNATURES = {
+    "kge_convkb_collapse_workspace_bytes": (ctypes.c_size_t, [_CKB]),
+    "kge_convkb_collapse": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_convkb_score_forward_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),
+    "kge_convkb_score_forward": (ctypes.c_int, [_CKB] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                                               ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_convkb_score_backward_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),
+    "kge_convkb_score_backward": (ctypes.c_int, [_CKB] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                                                ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_convkb_train_logistic_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),
+    "kge_convkb_train_logistic": (ctypes.c_int, [_CKB] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                                                ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_convkb_train_logistic_sampled_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64, ctypes.c_int32]),
+    "kge_convkb_train_logistic_sampled": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_convkb_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),
+    "kge_convkb_eval_ranks": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                              + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_convkb_sweep_scores_side_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),
+    "kge_convkb_sweep_scores_side": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                    ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_staged_step_bytes": (ctypes.c_size_t, []),
     "kge_train_pairwise_selfadv_sampled_staged": (ctypes.c_int, [ctypes.POINTER(ModelDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                                   ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p,

@@ -238,6 +238,8 @@ def _workspace(desc, n, device):
 
 
 def score_forward(desc, h, r, t):
+    if isinstance(desc, L.ConvKBDesc):
+        return convkb_score_forward(desc, h, r, t)
     n = h.numel()
     if r.numel() != n or t.numel() != n:
         raise ValueError("h, r, t must have equal lengths")
@@ -249,6 +251,8 @@ def score_forward(desc, h, r, t):
 
 
 def score_backward(desc, h, r, t, dscore):
+    if isinstance(desc, L.ConvKBDesc):
+        return convkb_score_backward(desc, h, r, t, dscore)
     n = h.numel()
     wp, wb, _keep = _workspace(desc, n, h.device)
     L.check(L.load().kge_score_backward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
@@ -308,6 +312,10 @@ def train_pointwise_logistic_sampled(desc, triples, perm, start, n_pos, neg_rate
                                      reg_type, loss_buf, cursor=None):
     """Sampler + scoring + pointwise logistic loss + regulariser + backward in ONE launch; the rows equal
     sample_batch(start, n_pos, neg_rate, pointwise=True)."""
+    if isinstance(desc, L.ConvKBDesc):
+        _convkb_no_reg(lmbda, reg_type)
+        return convkb_train_logistic_sampled(desc, triples, perm, start, n_pos, neg_rate, bern_prob, slots, seed, offset, loss_buf,
+                                             cursor=cursor)
     bp = _dev(bern_prob, torch.float32, "bern_prob") if bern_prob is not None else None
     sp = ctypes.c_void_p(slots.data_ptr()) if slots is not None else None
     pc = _dev(cursor, torch.int64, "cursor") if cursor is not None else None
@@ -501,6 +509,9 @@ def train_pairwise_selfadv(desc, ph, pr, pt, nh, nr, nt, neg_rate, alpha, loss_b
 
 
 def train_pointwise_logistic(desc, h, r, t, y, lmbda, reg_type, loss_buf, bundle=1):
+    if isinstance(desc, L.ConvKBDesc):
+        _convkb_no_reg(lmbda, reg_type)
+        return convkb_train_logistic(desc, h, r, t, y, loss_buf, bundle=bundle)
     n = h.numel()
     L.check(L.load().kge_train_pointwise_logistic(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"),
                                                   _ids(y, "y"), n, int(bundle), float(lmbda), int(reg_type),
@@ -705,6 +716,10 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
     """triples int64 [n,3]; CSR filter lists (int64 offsets [n+1], int32 ids) or None.  Returns int32 [4,n]:
     rank_head, rank_tail, filtered_rank_head, filtered_rank_tail (0-based).  ties: optional int32 [2, n] that receives, per head /
     tail sweep, the number of other candidates whose energy equals the true one's (kge_eval_ranks_ties)."""
+    if isinstance(desc, L.ConvKBDesc):
+        if ties is not None:
+            ties.fill_(-1)   # not counted
+        return convkb_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -748,6 +763,9 @@ def eval_ranks_grouped(desc, triples, group_of_triple, group_rel, qblocks, tail_
 
 def eval_sweep_scores(desc, triples, workspace=None):
     """float32 [2n, E]: row 2i = energies of (h_i, r_i, e) for all e, row 2i+1 = energies of (e, r_i, t_i)."""
+    if isinstance(desc, L.ConvKBDesc):   # one-sided entry point only: the two sides interleaved
+        both = torch.stack([convkb_sweep_scores_side(desc, triples, 0), convkb_sweep_scores_side(desc, triples, 1)], 1)
+        return both.view(2 * triples.shape[0], desc.tot_entity)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -761,6 +779,8 @@ def eval_sweep_scores(desc, triples, workspace=None):
 def eval_sweep_scores_side(desc, triples, side, workspace=None):
     """float32 [n, E]: side 0 = energies of (h_i, r_i, e) for all e, side 1 = energies of (e, r_i, t_i); the other side's query
     is never swept (kge_eval_sweep_scores_side).  TransR / NTN / SLM compute both sides per call: the full sweep, sliced."""
+    if isinstance(desc, L.ConvKBDesc):
+        return convkb_sweep_scores_side(desc, triples, side)
     if desc.model in (MODEL_IDS["transr"], MODEL_IDS["ntn"], MODEL_IDS["slm"]):
         return eval_sweep_scores(desc, triples, workspace)[int(side)::2]
     n = triples.shape[0]
@@ -1394,3 +1414,127 @@ def head_1n_bce(x, ent, bias, label_off, label_ids, label_smoothing, loss_buf, g
                                 _f32(g_ent, "g_ent"), _f32(g_bias, "g_bias") if g_bias is not None else None, _stream()),
             "kge_head_1n_bce")
     return dx
+
+
+# ---------------------------------------------------------------- ConvKB (csrc/kge_convkb.hip): its own descriptor and entry points
+def _convkb_no_reg(lmbda, reg_type):
+    if float(lmbda) != 0.0 and int(reg_type) != L.REG_NONE:
+        raise L.KgeHipError("convkb: the model has no regulariser (get_reg is 0.0); got lmbda %r, reg_type %r" % (lmbda, reg_type))
+
+
+def convkb_desc(tables, grads=None, *, tot_entity, tot_relation, dim, num_filters, filter_sizes, conv_w, conv_b):
+    """kge_convkb_desc.  `tables` / `grads`: ent_embeddings.weight, rel_embeddings.weight, fc1.weight, fc1.bias (the model's trainable
+    tensors, in this order); conv_w / conv_b: the packed filters (flattened conv_list[j].weight / .bias concatenated in list order), fixed
+    inputs.  Shapes are checked here (the kernels index rows by id without a bounds test); the filter geometry is checked by the
+    library, which refuses a bad one loudly."""
+    sizes = [int(s) for s in filter_sizes]
+    E, R, k, F = int(tot_entity), int(tot_relation), int(dim), int(num_filters)
+    if len(tables) != 4:
+        raise L.KgeHipError("convkb: 4 tensors expected (ent, rel, fc1.weight, fc1.bias), got %d" % len(tables))
+    ent, rel, fc_w, fc_b = tables
+    for name, t, rows in (("ent_embeddings", ent, E), ("rel_embeddings", rel, R)):
+        if t.dim() != 2 or t.shape[1] != k or t.shape[0] < rows:
+            raise L.KgeHipError("convkb: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
+                                % (name, rows, k, tuple(t.shape)))
+    W = sum(k - s + 1 for s in sizes)
+    for name, t, numel in (("fc1.weight", fc_w, F * W), ("fc1.bias", fc_b, 1), ("conv_w", conv_w, F * 3 * sum(sizes)),
+                           ("conv_b", conv_b, F * len(sizes))):
+        if 1 <= len(sizes) <= L.CONVKB_MAX_WIDTHS and all(1 <= s <= k for s in sizes) and F >= 1 and t.numel() != numel:
+            raise L.KgeHipError("convkb: %s must hold %d floats (got %d)" % (name, numel, t.numel()))
+    d = L.ConvKBDesc()
+    d.tot_entity, d.tot_relation, d.dim, d.num_filters, d.n_widths = E, R, k, F, len(sizes)
+    for j, s in enumerate(sizes[:L.CONVKB_MAX_WIDTHS]):
+        d.widths[j] = s
+    d.ent, d.rel = _dev(ent, torch.float32, "ent_embeddings").value, _dev(rel, torch.float32, "rel_embeddings").value
+    d.fc_w, d.fc_b = _dev(fc_w, torch.float32, "fc1.weight").value, _dev(fc_b, torch.float32, "fc1.bias").value
+    d.conv_w, d.conv_b = _dev(conv_w, torch.float32, "conv_w").value, _dev(conv_b, torch.float32, "conv_b").value
+    if grads is not None:
+        for g, t in zip(grads, tables):
+            if g.shape != t.shape:
+                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
+        d.g_ent, d.g_rel, d.g_fc_w, d.g_fc_b = (_dev(g, torch.float32, "grad %d" % i).value for i, g in enumerate(grads))
+    d._keepalive = (tables, grads, conv_w, conv_b)
+    d._ws = None
+    return d
+
+
+def _convkb_ws(desc, query, *args):
+    """(pointer, bytes) of the descriptor's workspace, grown to what `query` asks for; kept with the descriptor, so the captured steps
+    of a Trainer allocate nothing."""
+    need = int(getattr(L.load(), query)(ctypes.byref(desc), *args))
+    if desc._ws is None or desc._ws.numel() < need:
+        desc._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=desc._keepalive[0][0].device)
+    return ctypes.c_void_p(desc._ws.data_ptr()), desc._ws.numel()
+
+
+def convkb_collapse(desc):
+    """float32 [3 dim + 1]: A_h | A_r | A_t | c0."""
+    out = torch.empty(3 * desc.dim + 1, dtype=torch.float32, device=desc._keepalive[0][0].device)
+    L.check(L.load().kge_convkb_collapse(ctypes.byref(desc), _dev(out, torch.float32, "out"), None, 0, _stream()), "kge_convkb_collapse")
+    return out
+
+
+def convkb_score_forward(desc, h, r, t):
+    n = h.numel()
+    if r.numel() != n or t.numel() != n:
+        raise ValueError("h, r, t must have equal lengths")
+    out = torch.empty(n, dtype=torch.float32, device=h.device)
+    wp, wb = _convkb_ws(desc, "kge_convkb_score_forward_workspace_bytes", n)
+    L.check(L.load().kge_convkb_score_forward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
+                                              _dev(out, torch.float32, "scores"), wp, wb, _stream()), "kge_convkb_score_forward")
+    return out
+
+
+def convkb_score_backward(desc, h, r, t, dscore):
+    n = h.numel()
+    wp, wb = _convkb_ws(desc, "kge_convkb_score_backward_workspace_bytes", n)
+    L.check(L.load().kge_convkb_score_backward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
+                                               _dev(dscore, torch.float32, "dscore"), wp, wb, _stream()), "kge_convkb_score_backward")
+
+
+def convkb_train_logistic(desc, h, r, t, y, loss_buf, bundle=1):
+    n = h.numel()
+    wp, wb = _convkb_ws(desc, "kge_convkb_train_logistic_workspace_bytes", n)
+    L.check(L.load().kge_convkb_train_logistic(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), _ids(y, "y"), n,
+                                               int(bundle), wp, wb, _dev(loss_buf, torch.float32, "loss"), _stream()),
+            "kge_convkb_train_logistic")
+
+
+def convkb_train_logistic_sampled(desc, triples, perm, start, n_pos, neg_rate, bern_prob, slots, seed, offset, loss_buf, cursor=None):
+    """Sampler + scoring + pointwise logistic loss + all four gradients; the rows equal sample_batch(start, n_pos, neg_rate,
+    pointwise=True)."""
+    bp = _dev(bern_prob, torch.float32, "bern_prob") if bern_prob is not None else None
+    sp = ctypes.c_void_p(slots.data_ptr()) if slots is not None else None
+    pc = _dev(cursor, torch.int64, "cursor") if cursor is not None else None
+    wp, wb = _convkb_ws(desc, "kge_convkb_train_logistic_sampled_workspace_bytes", int(n_pos), int(neg_rate))
+    L.check(L.load().kge_convkb_train_logistic_sampled(ctypes.byref(desc), _ids(triples, "triples"), _ids(perm, "perm"), int(start),
+                                                       int(n_pos), int(neg_rate), bp, sp, slots.numel() if slots is not None else 0,
+                                                       int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), pc, wp, wb,
+                                                       _dev(loss_buf, torch.float32, "loss"), _stream()),
+            "kge_convkb_train_logistic_sampled")
+
+
+def convkb_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids):
+    """int32 [4, n] as eval_ranks, in one kge_convkb_eval_ranks call."""
+    n = triples.shape[0]
+    ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
+    args = []
+    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
+        if off is None:
+            args += [None, None]
+        else:
+            args += [_dev(off, torch.int64, "csr offsets"), _dev(ids, torch.int32, "csr ids")]
+    wp, wb = _convkb_ws(desc, "kge_convkb_eval_ranks_workspace_bytes", n)
+    L.check(L.load().kge_convkb_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
+                                           _dev(ranks, torch.int32, "ranks"), _stream()), "kge_convkb_eval_ranks")
+    return ranks
+
+
+def convkb_sweep_scores_side(desc, triples, side):
+    """float32 [n, E]: side 0 = preds of (h_i, r_i, e) for all e, side 1 = preds of (e, r_i, t_i)."""
+    n = triples.shape[0]
+    out = torch.empty((n, desc.tot_entity), dtype=torch.float32, device=triples.device)
+    wp, wb = _convkb_ws(desc, "kge_convkb_sweep_scores_side_workspace_bytes", n)
+    L.check(L.load().kge_convkb_sweep_scores_side(ctypes.byref(desc), _ids(triples, "triples"), n, int(side), wp, wb,
+                                                  _dev(out, torch.float32, "scores"), _stream()), "kge_convkb_sweep_scores_side")
+    return out

@@ -39,6 +39,11 @@ class Model:
     def desc_kwargs(self):
         raise NotImplementedError
 
+    def trainable_tensors(self):
+        """The tensors a Trainer re-homes into its flat parameter buffer and steps, in descriptor order: the weights of
+        `parameter_list`, unless a model trains more than its tables (ConvKB: fc1)."""
+        return [p.weight for p in self.parameter_list]
+
     def make_desc(self, weights=None, grads=None):
         if weights is None:
             weights = [p.weight for p in self.parameter_list]

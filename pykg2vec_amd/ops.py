@@ -3,6 +3,8 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
 
   torch.ops.kge.score(key, h, r, t, weights) -> float32 [N]        Model.forward of models/pairwise.py / pointwise.py
   torch.ops.kge.score_backward(key, h, r, t, dscore, weights) -> dense gradients of `weights` (nn.Embedding(sparse=False) semantics)
+  torch.ops.kge.convkb_score(key, h, r, t, weights) -> float32 [N]   ConvKB.forward (models/pointwise.py:302-318); weights = ent, rel, fc1.weight, fc1.bias
+  torch.ops.kge.convkb_score_backward(key, h, r, t, dscore, weights) -> their dense gradients (the filters are fixed inputs)
   torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]   the projection models' 1-N head (models/projection.py:100-102)
   torch.ops.kge.one_to_n_scores_backward(x, ent, preds, dpreds, need_bias) -> (dx, g_ent, g_bias)
 
@@ -86,6 +88,44 @@ def _score_backward(ctx, dscore):
 
 
 score.register_autograd(_score_backward, setup_context=_score_setup)
+
+
+# ConvKB has its own descriptor and entry points (include/kge_hip.h: kge_convkb_*): the same op pair under its own names
+@torch.library.custom_op("kge::convkb_score", mutates_args=(), device_types="cuda")
+def convkb_score(key: int, h: Tensor, r: Tensor, t: Tensor, weights: List[Tensor]) -> Tensor:
+    m = _model(key)
+    return K.convkb_score_forward(m.make_desc(list(weights)), h.contiguous(), r.contiguous(), t.contiguous())
+
+
+@convkb_score.register_fake
+def _(key, h, r, t, weights):
+    return h.new_empty((h.numel(),), dtype=torch.float32)
+
+
+@convkb_score.register_kernel("cpu")
+def _(key, h, r, t, weights):
+    raise L.KgeHipError("kge::convkb_score: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % h.device)
+
+
+@torch.library.custom_op("kge::convkb_score_backward", mutates_args=(), device_types="cuda")
+def convkb_score_backward(key: int, h: Tensor, r: Tensor, t: Tensor, dscore: Tensor, weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.convkb_score_backward(m.make_desc(list(weights), grads), h.contiguous(), r.contiguous(), t.contiguous(), dscore.contiguous())
+    return grads
+
+
+@convkb_score_backward.register_fake
+def _(key, h, r, t, dscore, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _convkb_backward(ctx, dscore):
+    h, r, t, *weights = ctx.saved_tensors
+    return None, None, None, None, convkb_score_backward(ctx.key, h, r, t, dscore, weights)
+
+
+convkb_score.register_autograd(_convkb_backward, setup_context=_score_setup)
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

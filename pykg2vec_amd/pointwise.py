@@ -1,5 +1,5 @@
 """Drop-in pointwise (semantic-matching) models mirroring pykg2vec/models/pointwise.py (DistMult, Complex,
-ComplexN3, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, OctonionE), scored by HIP kernels.  `get_reg` keeps the reference's
+ComplexN3, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, OctonionE, ConvKB), scored by HIP kernels.  `get_reg` keeps the reference's
 tensor-level form for use under the unmodified reference Trainer; the fused training kernel applies the same
 regulariser from registers."""
 import torch
@@ -320,3 +320,67 @@ class OctonionE(DistMult):
         if rt == "n3":
             return L.REG_N3_ABS
         raise NotImplementedError("Unknown regularizer type: %s" % rt)
+
+
+class ConvKB(PointwiseModel):
+    """pointwise.py:241-318.  preds = fc1(cat_j conv_j(stack(h, r, t))) with NO activation and NO dropout in between (the published
+    ConvKB has both; this follows the reference), so the score is affine in the three rows: the kernels collapse the filters and
+    fc1 into three vectors and a constant (csrc/kge_convkb.hip).
+
+    conv_list is a plain Python list, as in the reference: the filters are in neither parameters() nor state_dict(), no optimiser
+    steps them, and they are built on the constructor's `device`.  Trained state is the two tables plus fc1."""
+    kernel_name = "convkb"
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "hidden_size", "num_filters", "filter_sizes", "device"],
+                                              kwargs))
+        k, F = self.hidden_size, self.num_filters
+        self.filter_sizes = [int(s) for s in self.filter_sizes]
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, k)
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation, k)
+        _xavier(self.ent_embeddings, self.rel_embeddings)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings]
+        self.conv_list = [nn.Conv2d(1, F, (3, s), stride=(1, 1)).to(self.device) for s in self.filter_sizes]
+        self.fc1 = nn.Linear(in_features=F * sum(k - s + 1 for s in self.filter_sizes), out_features=1, bias=True)
+        self.loss = Criterion.pointwise_logistic
+        self._packed = None
+
+    def trainable_tensors(self):
+        return [self.ent_embeddings.weight, self.rel_embeddings.weight, self.fc1.weight, self.fc1.bias]
+
+    def packed_filters(self, device):
+        """(conv_w, conv_b) on `device`: the flattened conv_list[j].weight / .bias tensors concatenated in list order.  Rebuilt when
+        the tables moved to another device or a filter was written to."""
+        stamp = (torch.device(device), tuple((c.weight._version, c.bias._version) for c in self.conv_list))
+        if self._packed is None or self._packed[0] != stamp:
+            w = torch.cat([c.weight.detach().reshape(-1) for c in self.conv_list]).to(device=device, dtype=torch.float32).contiguous()
+            b = torch.cat([c.bias.detach().reshape(-1) for c in self.conv_list]).to(device=device, dtype=torch.float32).contiguous()
+            self._packed = (stamp, w, b)
+        return self._packed[1], self._packed[2]
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._packed = None   # .to() / .cuda() moved the tables; the packed filters follow them at the next descriptor
+        return out
+
+    def make_desc(self, weights=None, grads=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        weights = list(weights)
+        conv_w, conv_b = self.packed_filters(weights[0].device)
+        return K.convkb_desc(weights, None if grads is None else list(grads), tot_entity=self.tot_entity,
+                             tot_relation=self.tot_relation, dim=self.hidden_size, num_filters=self.num_filters,
+                             filter_sizes=self.filter_sizes, conv_w=conv_w, conv_b=conv_b)
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def forward(self, h, r, t):
+        return torch.ops.kge.convkb_score(self._kge_op_key, h, r, t, self.trainable_tensors())
+
+    def kernel_lmbda(self):
+        return 0.0
+
+    def kernel_reg_type(self, reg_type=None):
+        return L.REG_NONE

@@ -56,7 +56,8 @@ class FlatState:
         # distributed (default: world_size > 1): the step goes through the collectives and needs a reduce-scatter target that
         # is distinct from the local gradient buffer -- also at world size 1 when a process group was given explicitly
         distributed = world_size > 1 if distributed is None else bool(distributed)
-        params = [p.weight for p in model.parameter_list]
+        hook = getattr(model, "trainable_tensors", None)   # kgmeta.Model: the parameter_list weights unless the model says otherwise
+        params = list(hook()) if hook is not None else [p.weight for p in model.parameter_list]
         dev = params[0].device
         offs, tot = [], 0
         for p in params:

@@ -91,6 +91,11 @@ class Trainer:
         if self.config.optimizer not in K.OPTIMIZER_IDS:  # sgd / adam / adagrad / rms (utils/trainer.py:112-131)
             raise NotImplementedError("No support for %s optimizer" % self.config.optimizer)
         self.model.to(self.config.device)
+        if self.distributed:
+            self._refuse_convkb("data-parallel training")
+        for switch, what in (("pw_pull", "the owner-computes step (KGE_PW_PULL=1)"), ("staged", "the staged step (KGE_STAGED=1)")):
+            if self.switches.get(switch):
+                self._refuse_convkb(what)
         self._sparse_dp = self._sparse_dp_wanted()
         self._dp_allreduce = (not self._sparse_dp) and self._dp_allreduce_wanted()
         self.flat = FlatState(self.model, self.config.optimizer, self.K, self.world_size, self.rank, self.distributed,
@@ -105,6 +110,12 @@ class Trainer:
         self._selfadv_ws = None
         if self.distributed:  # replicas must start identical
             torch.distributed.broadcast(self.flat.param, src=0, group=self.process_group)
+
+    def _refuse_convkb(self, what):
+        """ConvKB trains through the fused atomic-scatter step on one GPU (csrc/kge_convkb.hip): its flat buffer carries fc1 next to the
+        tables and its descriptor is not a kge_model_desc, which the other step forms and the gradient exchange assume."""
+        if getattr(self.model, "kernel_name", None) == "convkb":
+            raise NotImplementedError("ConvKB: %s is not supported (single-GPU fused step only)" % what)
 
     def _mark(self, name):
         """Per-phase timing of the multi-GPU step (bench.py --gpus N): an event on the current stream at a phase boundary.  The
@@ -169,7 +180,7 @@ class Trainer:
         if not (self.K is K and self.model.training_strategy == TrainingStrategy.POINTWISE_BASED):
             return False
         group = 32 if self.model.hidden_size <= 256 else 64
-        if self.model.kernel_name == "octonione":   # the bundle's positive holds a lane of the group too (csrc/kge_octonion.hip)
+        if self.model.kernel_name in ("octonione", "convkb"):   # the bundle's positive holds a lane of the group too (csrc/kge_octonion.hip)
             group -= 1
         return 1 <= int(self.config.neg_rate) <= group
 
@@ -394,6 +405,7 @@ class Trainer:
     def pull_step_explicit(self, ph, pr, pt, nh, nr, nt, segment=None, compact=None):
         """The owner-computes step on an explicit batch (positives + given negatives, neg_rate 1): the incidence index
         of this one batch is built on the host first, so this is for parity tests and one-off batches, not the hot loop."""
+        self._refuse_convkb("the owner-computes step")
         import numpy as np
         from .generator import PullIndex
         pos = np.stack([x.detach().cpu().numpy() for x in (ph, pr, pt)], 1)
@@ -505,6 +517,7 @@ class Trainer:
     def own_step_explicit(self, h, r, t, y):
         """The two-phase step on an explicit pointwise batch in the sampler's layout for neg_rate 1 (rows 2i = positive i, 2i+1 = its
         corruption): the incidence index of this one batch is built on the host first -- parity tests and one-off batches."""
+        self._refuse_convkb("the owner-computes step")
         import numpy as np
         from .generator import PullIndex
         name, cfg, flat = self.model.kernel_name, self.config, self.flat
@@ -611,6 +624,7 @@ class Trainer:
     def transx_step_explicit(self, ph, pr, pt, nh, nr, nt):
         """The same step on an explicit batch (positives + given negatives, neg_rate 1): gradients into the flat buffer, no
         optimiser (parity tests read them; the caller steps).  The incidence index of this one batch is built on the host."""
+        self._refuse_convkb("the owner-computes step")
         import numpy as np
         from .generator import PullIndex
         d = self.model.parameter_list[0].weight.shape[1]
@@ -650,6 +664,7 @@ class Trainer:
         return self.model.kernel_name == "rotate" and self.config.batch_size * (1 + int(self.config.neg_rate)) > self.GRAPH_MAX_ROWS
 
     def _staged_plan(self):
+        self._refuse_convkb("the staged step")
         if getattr(self, "_staged", None) is None:
             cfg, flat = self.config, self.flat
             rows = [p.weight.shape[0] for p in self.model.parameter_list]
