@@ -850,6 +850,54 @@ size_t kge_convkb_sweep_scores_side_workspace_bytes(const kge_convkb_desc* d, in
 int kge_convkb_sweep_scores_side(const kge_convkb_desc* d, const int64_t* triples, int64_t n, int side, void* workspace,
                                  size_t workspace_bytes, float* scores, void* stream);
 
+/* ---- TuckER (models/projection.py:259-344): the body in front of the 1-N head (csrc/kge_tucker.hip).  For a row
+ * with entity e and relation r:
+ *     a = normalize(ent[e]) * m0,   M = sum_k rel[r][k] W[k,:,:] * m1,   z_j = sum_i a_i M_ij,   x = normalize(z) * m2,
+ * normalize = v / max(|v|, 1e-12) (F.normalize), m0 / m1 / m2 the masks of input_dropout / hidden_dropout1 / hidden_dropout2.  The model
+ * has no kge_model id: it has its own descriptor and entry points.  W is the core [d2, d1 * d1].  Masks are never stored; every kernel
+ * recomputes them from Philox4x32-10:  key = (low, high word of seed);  counter = (elem, row >> 2, site | (offset >> 32) << 2,
+ * offset & 0xffffffff), word = row & 3;  elem = i (site 0), i * d1 + j (site 1), j (site 2);  row = position in the call's row list.
+ * An element is kept iff its word >= floor(p * 2^32) and is then scaled by 1 / (1 - p) in fp32.  train = 0 or p = 0: nothing is drawn.
+ * Gradients are accumulated into g_*; all three are sums in a fixed order (no atomics in the body: bit-identical run to run).
+ * Every entry point takes a caller-owned workspace (its own *_workspace_bytes; 0 = the descriptor is refused).  Refused before any
+ * launch, with the entry point's name in kge_last_error(): null tables, non-positive sizes, d1 > 32768, a dropout rate outside
+ * [0, 1), an offset of 2^62 or more, a workspace that is too small. */
+typedef struct kge_tucker_desc {
+    int64_t tot_entity, tot_relation;
+    int32_t d1, d2;                                        /* ent_hidden_size, rel_hidden_size */
+    float input_dropout, hidden_dropout1, hidden_dropout2; /* sites 0, 1, 2 */
+    int32_t train;                                         /* 0 = model.eval(): no dropout */
+    uint64_t seed, offset;                                 /* Philox key and step offset */
+    const float *ent, *rel, *W;                            /* [E,d1], [R,d2], [d2,d1*d1] */
+    float *g_ent, *g_rel, *g_W;                            /* dense grads, may be NULL for forward */
+} kge_tucker_desc;
+
+/* x[n, d1] of the rows (e_i, r_i).  saved: kge_tucker_saved_floats(d, n) floats that the backward of the same rows reads
+ * (a [n, d1] | z [n, d1] | |ent[e]| [n] | |z| [n]). */
+size_t kge_tucker_saved_floats(const kge_tucker_desc* d, int64_t n);
+size_t kge_tucker_body_forward_workspace_bytes(const kge_tucker_desc* d, int64_t n);
+int kge_tucker_body_forward(const kge_tucker_desc* d, const int64_t* e, const int64_t* r, int64_t n, float* x, float* saved,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* g_* += d(sum x o dx) / d tensor for the same rows, descriptor (seed, offset, train) and `saved`. */
+size_t kge_tucker_body_backward_workspace_bytes(const kge_tucker_desc* d, int64_t n);
+int kge_tucker_body_backward(const kge_tucker_desc* d, const int64_t* e, const int64_t* r, int64_t n, const float* dx, const float* saved,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* One Trainer.train_step_projection (utils/trainer.py:159-172): the body on the 2 batch rows [h; t], [r; r], kge_head_1n_bce on
+ * forward(h, r) against the hr_t label CSR and on forward(t, r) against the tr_h label CSR (off int64 [batch + 1], ids int32), body
+ * backward.  loss += mean_{batch * E} of the tail direction + mean_{batch * E} of the head direction; label_smoothing < 0 = off. */
+size_t kge_tucker_train_bce_workspace_bytes(const kge_tucker_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr);
+int kge_tucker_train_bce(const kge_tucker_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch,
+                         const int64_t* hr_off, const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids,
+                         int64_t n_tr, float label_smoothing, void* workspace, size_t workspace_bytes, float* loss, void* stream);
+
+/* Filtered and raw ranks, filter CSR arguments and `ranks` layout ([4, n]) of kge_eval_ranks: the body without dropout on (h, r) and
+ * (t, r), then kge_head_1n_rank per side.  ties: optional int32 [2, n] (head sweeps, tail sweeps) as kge_head_1n_rank counts them. */
+size_t kge_tucker_eval_ranks_workspace_bytes(const kge_tucker_desc* d, int64_t n);
+int kge_tucker_eval_ranks(const kge_tucker_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                          const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                          int32_t* ties, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

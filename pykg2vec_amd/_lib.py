@@ -135,7 +135,33 @@ class ConvKBDesc(ctypes.Structure):
 
 _CKB = ctypes.POINTER(ConvKBDesc)
 
+
+class TuckerDesc(ctypes.Structure):
+    """struct kge_tucker_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("d1", ctypes.c_int32), ("d2", ctypes.c_int32),
+                ("input_dropout", ctypes.c_float), ("hidden_dropout1", ctypes.c_float), ("hidden_dropout2", ctypes.c_float),
+                ("train", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("ent", ctypes.c_void_p), ("rel", ctypes.c_void_p), ("W", ctypes.c_void_p),
+                ("g_ent", ctypes.c_void_p), ("g_rel", ctypes.c_void_p), ("g_W", ctypes.c_void_p)]
+
+
+_TKD = ctypes.POINTER(TuckerDesc)
+
 _SIGNATURES = {
+    "kge_tucker_saved_floats": (ctypes.c_size_t, [_TKD, ctypes.c_int64]),
+    "kge_tucker_body_forward_workspace_bytes": (ctypes.c_size_t, [_TKD, ctypes.c_int64]),
+    "kge_tucker_body_forward": (ctypes.c_int, [_TKD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_tucker_body_backward_workspace_bytes": (ctypes.c_size_t, [_TKD, ctypes.c_int64]),
+    "kge_tucker_body_backward": (ctypes.c_int, [_TKD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_tucker_train_bce_workspace_bytes": (ctypes.c_size_t, [_TKD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "kge_tucker_train_bce": (ctypes.c_int, [_TKD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_tucker_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_TKD, ctypes.c_int64]),
+    "kge_tucker_eval_ranks": (ctypes.c_int, [_TKD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                              + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_convkb_collapse_workspace_bytes": (ctypes.c_size_t, [_CKB]),
     "kge_convkb_collapse": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "kge_convkb_score_forward_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),

@@ -369,6 +369,10 @@ class Evaluator:
                     ties[:, dst[a:b]] = t
             return (out, ties) if return_ties else out
         ties = new_ties(trip.shape[0])
+        if getattr(self.model, "kernel_name", None) == "tucker" and self.K is K:
+            # the projection path: body without dropout + the head's filtered rank per side (kge_tucker_eval_ranks), same [4, n] layout
+            out = K.tucker_eval_ranks(desc, trip, t_off, t_ids, h_off, h_ids, ties=ties)
+            return (out, ties) if return_ties else out
         out = self.K.eval_ranks(desc, trip, t_off, t_ids, h_off, h_ids, **kw(ties))
         return (out, ties) if return_ties else out
 

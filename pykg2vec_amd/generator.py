@@ -311,8 +311,13 @@ class Generator:
         self.model = model
         self.config = config
         self.training_strategy = model.training_strategy
-        if self.training_strategy not in (TrainingStrategy.PAIRWISE_BASED, TrainingStrategy.POINTWISE_BASED):
+        if self.training_strategy not in (TrainingStrategy.PAIRWISE_BASED, TrainingStrategy.POINTWISE_BASED,
+                                          TrainingStrategy.PROJECTION_BASED):
             raise NotImplementedError("This strategy is not supported.")
+        if self.training_strategy == TrainingStrategy.PROJECTION_BASED and int(config.neg_rate) > 0:
+            # data/generator.py:178-209 then writes -1 into the label rows of the corrupted entities: BCE targets outside [0, 1]
+            raise NotImplementedError("projection models: neg_rate > 0 is not supported (the reference then writes -1 into the BCE "
+                                      "targets); the reference's presets use neg_rate 0")
         self.device = torch.device(config.device if isinstance(config.device, str) else config.device)
         train = _triples_array(config.knowledge_graph.read_cache_data('triplets_train'))
         self.n_train = train.shape[0]
@@ -414,7 +419,18 @@ class Generator:
             offset += lo * self.neg_rate
         return start, n, offset
 
+    def _next_projection(self):
+        """[h, r, t, (hr_t off, ids), (tr_h off, ids)] of the next batch: the label rows of data/generator.py:178-209 as CSR (off int64
+        [B + 1], ids int32), built on the device from the TRAINING split alone (hr_t_train / tr_h_train); the dense [B, E] rows of the
+        reference are never formed."""
+        start, n, _ = self._next_range()
+        trip = self.triples[self.perm[start:start + n]].contiguous()
+        t_off, t_ids, h_off, h_ids = self.K.filter_csr_build(self.triples, trip, self.config.tot_entity, self.config.tot_relation)
+        return [trip[:, 0].contiguous(), trip[:, 1].contiguous(), trip[:, 2].contiguous(), (t_off, t_ids), (h_off, h_ids)]
+
     def __next__(self):
+        if self.training_strategy == TrainingStrategy.PROJECTION_BASED:
+            return self._next_projection()
         start, n, offset = self._next_range()
         return self.K.sample_batch(self.triples, self.perm, start, n, self.neg_rate, self.config.tot_entity, self.bern,
                                    self.slots, self.seed, offset,

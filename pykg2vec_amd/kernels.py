@@ -720,6 +720,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
         if ties is not None:
             ties.fill_(-1)   # not counted
         return convkb_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids)
+    if isinstance(desc, L.TuckerDesc):
+        return tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -1538,3 +1540,104 @@ def convkb_sweep_scores_side(desc, triples, side):
     L.check(L.load().kge_convkb_sweep_scores_side(ctypes.byref(desc), _ids(triples, "triples"), n, int(side), wp, wb,
                                                   _dev(out, torch.float32, "scores"), _stream()), "kge_convkb_sweep_scores_side")
     return out
+
+
+# ---------------------------------------------------------------- TuckER (csrc/kge_tucker.hip): its own descriptor and entry points
+def tucker_desc(tables, grads=None, *, tot_entity, tot_relation, d1, d2, dropouts=(0.0, 0.0, 0.0), train=False, seed=0, offset=0):
+    """kge_tucker_desc.  `tables` / `grads`: ent_embeddings.weight [E, d1], rel_embeddings.weight [R, d2], W.weight [d2, d1 * d1] (the
+    model's trainable tensors, in this order).  Shapes are checked here (the kernels index rows by id without a bounds test); the
+    dropout rates and the offset are checked by the library, which refuses bad ones loudly."""
+    E, R, d1, d2 = int(tot_entity), int(tot_relation), int(d1), int(d2)
+    if len(tables) != 3:
+        raise L.KgeHipError("tucker: 3 tensors expected (ent, rel, W), got %d" % len(tables))
+    ent, rel, W = tables
+    for name, t, rows, cols in (("ent_embeddings", ent, E, d1), ("rel_embeddings", rel, R, d2)):
+        if t.dim() != 2 or t.shape[1] != cols or t.shape[0] < rows:
+            raise L.KgeHipError("tucker: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
+                                % (name, rows, cols, tuple(t.shape)))
+    if W.numel() != d2 * d1 * d1:
+        raise L.KgeHipError("tucker: W must hold d2 * d1 * d1 = %d floats (got %d)" % (d2 * d1 * d1, W.numel()))
+    d = L.TuckerDesc()
+    d.tot_entity, d.tot_relation, d.d1, d.d2 = E, R, d1, d2
+    d.input_dropout, d.hidden_dropout1, d.hidden_dropout2 = (float(p) for p in dropouts)
+    d.train, d.seed, d.offset = int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    d.ent, d.rel, d.W = (_dev(t, torch.float32, n).value for t, n in zip(tables, ("ent_embeddings", "rel_embeddings", "W")))
+    if grads is not None:
+        for g, t in zip(grads, tables):
+            if g.shape != t.shape:
+                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
+        d.g_ent, d.g_rel, d.g_W = (_dev(g, torch.float32, "grad %d" % i).value for i, g in enumerate(grads))
+    d._keepalive = (tables, grads)
+    d._ws = None
+    return d
+
+
+def _tucker_ws(desc, query, *args):
+    """(pointer, bytes) of the descriptor's workspace, grown to what `query` asks for; kept with the descriptor, so the steps of a
+    Trainer allocate nothing once the largest label list has been seen."""
+    need = int(getattr(L.load(), query)(ctypes.byref(desc), *args))
+    if need == 0:
+        msg = L.load().kge_last_error()
+        raise L.KgeHipError("%s refused the descriptor: %s" % (query, msg.decode() if msg else "?"))
+    if desc._ws is None or desc._ws.numel() < need:
+        desc._ws = torch.empty(need + need // 8, dtype=torch.uint8, device=desc._keepalive[0][0].device)
+    return ctypes.c_void_p(desc._ws.data_ptr()), desc._ws.numel()
+
+
+def tucker_saved_floats(desc, n):
+    return int(L.load().kge_tucker_saved_floats(ctypes.byref(desc), int(n)))
+
+
+def tucker_body_forward(desc, e, r):
+    """(x float32 [n, d1], saved): the body of TuckER.forward on the rows (e_i, r_i); `saved` is what tucker_body_backward reads."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    x = torch.empty((n, desc.d1), dtype=torch.float32, device=e.device)
+    saved = torch.empty(max(1, n * (2 * desc.d1 + 2)), dtype=torch.float32, device=e.device)
+    wp, wb = _tucker_ws(desc, "kge_tucker_body_forward_workspace_bytes", n)
+    L.check(L.load().kge_tucker_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, _dev(x, torch.float32, "x"),
+                                             _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_tucker_body_forward")
+    return x, saved
+
+
+def tucker_body_backward(desc, e, r, dx, saved):
+    """g_* of the descriptor += the body's gradients given d loss / d x (same rows, seed, offset and `saved` as the forward)."""
+    n = e.numel()
+    wp, wb = _tucker_ws(desc, "kge_tucker_body_backward_workspace_bytes", n)
+    L.check(L.load().kge_tucker_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, _dev(dx, torch.float32, "dx"),
+                                              _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_tucker_body_backward")
+
+
+def tucker_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
+    """One train_step_projection: adds to loss_buf and to the descriptor's gradients.  hr_* / tr_*: the label CSRs of the batch
+    (off int64 [B + 1], ids int32); label_smoothing None = off."""
+    B = h.numel()
+    if r.numel() != B or t.numel() != B or hr_off.numel() != B + 1 or tr_off.numel() != B + 1:
+        raise ValueError("tucker_train_bce: h, r, t must have equal lengths B and the label offsets B + 1 entries")
+    n_hr, n_tr = int(hr_ids.numel()), int(tr_ids.numel())
+    wp, wb = _tucker_ws(desc, "kge_tucker_train_bce_workspace_bytes", B, n_hr, n_tr)
+    L.check(L.load().kge_tucker_train_bce(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), B,
+                                          _dev(hr_off, torch.int64, "hr_t offsets"), _dev(hr_ids, torch.int32, "hr_t ids") if n_hr else None,
+                                          n_hr, _dev(tr_off, torch.int64, "tr_h offsets"),
+                                          _dev(tr_ids, torch.int32, "tr_h ids") if n_tr else None, n_tr,
+                                          -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+                                          _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_tucker_train_bce")
+
+
+def tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks, in one kge_tucker_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
+    n = triples.shape[0]
+    ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
+    args = []
+    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
+        if off is None:
+            args += [None, None]
+        else:
+            args += [_dev(off, torch.int64, "csr offsets"), ctypes.c_void_p(ids.data_ptr()) if ids.numel() else ctypes.c_void_p(off.data_ptr())]
+    wp, wb = _tucker_ws(desc, "kge_tucker_eval_ranks_workspace_bytes", n)
+    L.check(L.load().kge_tucker_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
+                                           _dev(ranks, torch.int32, "ranks"),
+                                           _dev(ties, torch.int32, "ties") if ties is not None else None, _stream()),
+            "kge_tucker_eval_ranks")
+    return ranks

@@ -105,3 +105,15 @@ class PointwiseModel(nn.Module, Model):
         self.training_strategy = TrainingStrategy.POINTWISE_BASED
         self.database = {}
         self._register_op_handle()
+
+
+class ProjectionModel(nn.Module, Model):
+    """The base of the 1-N models (models/KGMeta.py: ProjectionModel): forward(e, r, direction) returns [B, E] predictions."""
+    __setstate__ = Model._restore
+
+    def __init__(self, model_name):
+        super().__init__()
+        self.model_name = model_name
+        self.training_strategy = TrainingStrategy.PROJECTION_BASED
+        self.database = {}
+        self._register_op_handle()

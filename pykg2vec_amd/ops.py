@@ -5,6 +5,8 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
   torch.ops.kge.score_backward(key, h, r, t, dscore, weights) -> dense gradients of `weights` (nn.Embedding(sparse=False) semantics)
   torch.ops.kge.convkb_score(key, h, r, t, weights) -> float32 [N]   ConvKB.forward (models/pointwise.py:302-318); weights = ent, rel, fc1.weight, fc1.bias
   torch.ops.kge.convkb_score_backward(key, h, r, t, dscore, weights) -> their dense gradients (the filters are fixed inputs)
+  torch.ops.kge.tucker_body(key, e, r, seed, offset, weights) -> (x float32 [N, d1], saved)   the body of TuckER.forward (models/projection.py:321-334); weights = ent, rel, W
+  torch.ops.kge.tucker_body_backward(key, e, r, seed, offset, dx, saved, weights) -> their dense gradients
   torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]   the projection models' 1-N head (models/projection.py:100-102)
   torch.ops.kge.one_to_n_scores_backward(x, ent, preds, dpreds, need_bias) -> (dx, g_ent, g_bias)
 
@@ -126,6 +128,54 @@ def _convkb_backward(ctx, dscore):
 
 
 convkb_score.register_autograd(_convkb_backward, setup_context=_score_setup)
+
+
+# TuckER's body (include/kge_hip.h: kge_tucker_body_*).  seed / offset key the dropout masks the two ops recompute; the model's
+# train / eval state is read from the model object when the forward runs and travels to the backward as offset < 0 = eval.
+@torch.library.custom_op("kge::tucker_body", mutates_args=(), device_types="cuda")
+def tucker_body(key: int, e: Tensor, r: Tensor, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
+    m = _model(key)
+    return K.tucker_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(), r.contiguous())
+
+
+@tucker_body.register_fake
+def _(key, e, r, seed, offset, weights):
+    n, d1 = e.numel(), weights[0].shape[1]
+    return weights[0].new_empty((n, d1)), weights[0].new_empty((max(1, n * (2 * d1 + 2)),))
+
+
+@tucker_body.register_kernel("cpu")
+def _(key, e, r, seed, offset, weights):
+    raise L.KgeHipError("kge::tucker_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
+
+
+@torch.library.custom_op("kge::tucker_body_backward", mutates_args=(), device_types="cuda")
+def tucker_body_backward(key: int, e: Tensor, r: Tensor, seed: int, offset: int, dx: Tensor, saved: Tensor, weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.tucker_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                           r.contiguous(), dx.contiguous(), saved)
+    return grads
+
+
+@tucker_body_backward.register_fake
+def _(key, e, r, seed, offset, dx, saved, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _tucker_setup(ctx, inputs, output):
+    key, e, r, seed, offset, weights = inputs
+    ctx.key, ctx.seed, ctx.offset = key, seed, offset
+    ctx.save_for_backward(e, r, output[1], *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _tucker_backward(ctx, dx, _dsaved):
+    e, r, saved, *weights = ctx.saved_tensors
+    return None, None, None, None, None, tucker_body_backward(ctx.key, e, r, ctx.seed, ctx.offset, dx, saved, weights)
+
+
+tucker_body.register_autograd(_tucker_backward, setup_context=_tucker_setup)
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

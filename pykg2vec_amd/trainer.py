@@ -87,7 +87,33 @@ class Trainer:
         self.distributed = self.world_size > 1 or process_group is not None
 
     # ------------------------------------------------------------------ build
+    def _projection(self):
+        return self.model.training_strategy == TrainingStrategy.PROJECTION_BASED
+
+    def _refuse_projection(self):
+        """The projection path (TuckER, csrc/kge_tucker.hip) is the fused single-GPU step: body, 1-N head with multi_class_bce per
+        direction, body backward.  What it does not serve is refused here, before anything is built."""
+        def no(what):
+            raise NotImplementedError("%s: %s is not supported on the projection path (single-GPU fused step only)"
+                                      % (type(self.model).__name__, what))
+        if self.config.optimizer == "riemannian":
+            no("the riemannian optimizer")
+        if self.distributed:
+            no("data-parallel training")
+        # (as for ConvKB: the switches that would force a step form onto this model.  KGE_PULL / KGE_TRANSX_OWN only choose between
+        # the paths of TransE / TransM / TransH / TransD, which a projection model never enters: they are process-wide A/B switches
+        # and not a request about this model)
+        for switch, what in (("pw_pull", "the owner-computes step (KGE_PW_PULL=1)"), ("staged", "the staged step (KGE_STAGED=1)")):
+            if self.switches.get(switch):
+                no(what)
+        if int(getattr(self.config, "neg_rate", 0) or 0) > 0:
+            no("neg_rate > 0 (the reference then writes -1 into the BCE targets)")
+        if self.use_graph:
+            no("hipGraph capture of the step (the label lists change length from batch to batch)")
+
     def build_model(self, monitor=Monitor.FILTERED_MEAN_RANK):
+        if self._projection():
+            self._refuse_projection()
         if self.config.optimizer not in K.OPTIMIZER_IDS:  # sgd / adam / adagrad / rms (utils/trainer.py:112-131)
             raise NotImplementedError("No support for %s optimizer" % self.config.optimizer)
         self.model.to(self.config.device)
@@ -107,6 +133,7 @@ class Trainer:
             self.early_stopper = PatienceStopper(getattr(self.config, "patience", -1), monitor)
         self.best_metric = None
         self._desc = self.K.model_desc(self.model, [v for v in self.flat.views], self.flat.grad_views)
+        self._projection_step = 0     # the Philox offset of the projection path's dropout masks: one per step
         self._selfadv_ws = None
         if self.distributed:  # replicas must start identical
             torch.distributed.broadcast(self.flat.param, src=0, group=self.process_group)
@@ -199,6 +226,9 @@ class Trainer:
         """One batch from the generator's stream into the gradient / loss buffers."""
         gen = self.generator
         self._step_cursor = cursor     # hipGraph-captured steps: the device-resident step state (element 2 = the step index)
+        if self._projection():
+            self._accumulate_projection(*next(gen))
+            return
         if self._fused_rotate_ok():
             start, n, offset = fixed_range if fixed_range is not None else gen._next_range()
             self._wait_gather()
@@ -234,6 +264,15 @@ class Trainer:
             if getattr(self, "_sparse_dp", False):
                 self._batch_entity_ids = torch.cat([data[0], data[2]])
             self._accumulate_pointwise(*data)
+
+    def _accumulate_projection(self, h, r, t, hr_t_csr, tr_h_csr):
+        """The fused projection step into the gradient / loss buffers.  The dropout masks of step s are the Philox masks of
+        (config.seed, s): a run is reproducible from the seed."""
+        d = self._desc
+        d.train, d.seed, d.offset = int(self.model.training), int(getattr(self.config, "seed", 0) or 0) & (2 ** 64 - 1), self._projection_step
+        self._projection_step += 1
+        ls = getattr(self.config, "label_smoothing", None) if hasattr(self.config, "label_smoothing") else None
+        self.K.tucker_train_bce(d, h, r, t, hr_t_csr[0], hr_t_csr[1], tr_h_csr[0], tr_h_csr[1], ls, self.loss_buf)
 
     def _accumulate_pointwise(self, h, r, t, y):
         # rows arrive as bundles [positive, its neg_rate negatives] (generator / data/generator.py:125-156)
@@ -719,6 +758,8 @@ class Trainer:
 
     def step_path(self, n=1):
         """Name of the path that serves the next n batches (STEP_PATHS)."""
+        if self._projection():
+            return "generic"
         full = n > 0 and self.generator is not None and \
             self.generator._batch_idx + n <= self.generator.n_train // int(self.config.batch_size)
         for name, pred, needs_full in self.STEP_PATHS:
@@ -1007,13 +1048,19 @@ class Trainer:
         self._accumulate_pointwise(h, r, t, target)
         return self.K.read_loss(self.loss_buf)
 
+    def train_step_projection(self, h, r, t, hr_t_csr, tr_h_csr):
+        """utils/trainer.py:159-172 with the label rows as CSR pairs (off int64 [B + 1], ids int32), as the Generator yields them."""
+        self.loss_buf.zero_()
+        self._accumulate_projection(h, r, t, hr_t_csr, tr_h_csr)
+        return self.K.read_loss(self.loss_buf)
+
     # ------------------------------------------------------------------ hipGraph replay of the whole step
     def _graph_wanted(self, num_batch=None):
         # captured steps read perm[batch_idx * B + i] for all i < B with no per-step clamp (the eager path clamps in
         # Generator._next_range): every batch of the epoch must lie inside the train permutation
         if num_batch is not None and num_batch * int(self.config.batch_size) > self.generator.n_train:
             return False
-        if self.K is not K:
+        if self.K is not K or self._projection():
             return False
         if self.switches["staged"] and self._staged_ok():   # the staged step is an eager two-launch step
             return False
