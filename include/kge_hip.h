@@ -898,6 +898,76 @@ int kge_tucker_eval_ranks(const kge_tucker_desc* d, const int64_t* triples, int6
                           const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
                           int32_t* ties, void* stream);
 
+/* ---- ProjE_pointwise (models/projection.py:128-257): a pointwise body in front of the 1-N product, trained on the LABELLED columns
+ * only (csrc/kge_proje.hip).  For a row with entity e and relation r and a side s (0 = "tail" direction: f1 with
+ * De1 / Dr1 / bc1 on (h, r); 1 = "head" direction: f2 with De2 / Dr2 / bc2 on (t, r)):
+ *     x = tanh(ent[e] o De_s + rel[r] o Dr_s + bc_s) * m,      p_c = sigmoid(<x, ent[c]>)  for a candidate entity c,
+ *     loss = - sum_{y = +1} log(clamp(p, 1e-10, 1)) - sum_{y = -1} log(clamp(1 - p, 1e-10, 1))      (a SUM, not a mean).
+ * The model has no kge_model id: it has its own descriptor and entry points.  m is the mask of hidden_dropout, never stored; every
+ * kernel recomputes it from Philox4x32-10:  key = (low, high word of seed);  counter = (elem, row >> 2, site | (offset >> 32) << 2,
+ * offset & 0xffffffff), word = row & 3;  elem = j (the column of x), site = the side s, row = position in the call's row list (in
+ * the fused step: the row's index in its own direction's list, so forward(direction) with the same (seed, offset) sees the same
+ * mask).  An element is kept iff its word >= floor(p * 2^32) and is then scaled by 1 / (1 - p) in fp32.  train = 0 or p = 0:
+ * nothing is drawn.  (The reference draws this dropout under eval() too: the caller sets train.)
+ * Gradients are accumulated into g_*.  The six [1, dim] rows (bc / De / Dr of both sides) are sums over the batch in a fixed order:
+ * bit-identical run to run.  g_ent and g_rel rows are added with float atomics, except the shares of the negative columns, which
+ * are ordered sums over the batch.  Every entry point takes a caller-owned workspace (its own *_workspace_bytes; 0 = the
+ * descriptor is refused).  Refused before any launch, with the entry point's name in kge_last_error(): null tables, non-positive
+ * sizes, dim > 2048, a dropout rate outside [0, 1), an offset of 2^62 or more, a side other than 0 / 1, a workspace that is too
+ * small. */
+typedef struct kge_proje_desc {
+    int64_t tot_entity, tot_relation;
+    int32_t dim;                                            /* hidden_size */
+    float hidden_dropout;
+    int32_t train;                                          /* 0: no dropout */
+    int32_t reserved;                                       /* 0 */
+    uint64_t seed, offset;                                  /* Philox key and step offset */
+    const float *ent, *rel, *bc1, *De1, *Dr1, *bc2, *De2, *Dr2;    /* [E,dim], [R,dim], six rows [1,dim]: parameter_list order */
+    float *g_ent, *g_rel, *g_bc1, *g_De1, *g_Dr1, *g_bc2, *g_De2, *g_Dr2; /* dense grads, may be NULL for forward */
+} kge_proje_desc;
+
+/* x[n, dim] of the rows (e_i, r_i) on side `side`.  The forward needs no scratch: its query answers a token 256 bytes, so that 0 keeps
+ * meaning `refused` as everywhere else. */
+size_t kge_proje_body_forward_workspace_bytes(const kge_proje_desc* d, int64_t n);
+int kge_proje_body_forward(const kge_proje_desc* d, const int64_t* e, const int64_t* r, int64_t n, int32_t side, float* x,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* g_* += d(sum x o dx) / d tensor for the same rows, side and descriptor (seed, offset, train): through the mask and 1 - tanh^2
+ * into g_ent, g_rel and the side's bc / De / Dr.  The body is recomputed from the tables: nothing is saved by the forward. */
+size_t kge_proje_body_backward_workspace_bytes(const kge_proje_desc* d, int64_t n);
+int kge_proje_body_backward(const kge_proje_desc* d, const int64_t* e, const int64_t* r, int64_t n, int32_t side, const float* dx,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* The loss of ONE direction over the labelled columns alone; no [batch, E] tensor and no workspace proportional to batch * E.
+ * x: float [batch, dim].  Positives (y = +1): CSR pos_off int64 [batch + 1] / pos_ids int32 [n_pos], ascending and distinct inside a
+ * row, as kge_filter_csr_* writes them.  Negatives (y = -1): neg int32 [n_neg], DISTINCT ids shared by all rows (n_neg may be 0); a
+ * negative that is one of the row's positives is skipped.  With z = <x_b, ent[c]>, s = sigmoid(z), u = 1 - s in fp32:
+ *     positive: loss += -log(max(s, 1e-10)),  dz = -(1 - s) if s > 1e-10 else 0;
+ *     negative: loss += -log(max(u, 1e-10)),  dz = s        if u > 1e-10 else 0.
+ * loss: the striped accumulators of the other train entry points (the call's total is added to one of them, summed in a fixed order
+ * in double).  dx float [batch, dim] is OVERWRITTEN with sum_c dz_c ent[c]; g_ent [E, dim] += dz_c x_b (the negative columns as an
+ * ordered sum over the batch, the positive ones with float atomics).  An id outside [0, E) contributes nothing. */
+size_t kge_proje_label_loss_workspace_bytes(int64_t batch, int32_t dim, int64_t n_pos, int64_t n_neg);
+int kge_proje_label_loss(const float* x, int64_t batch, int32_t dim, const float* ent, int64_t tot_entity, const int64_t* pos_off,
+                         const int32_t* pos_ids, int64_t n_pos, const int32_t* neg, int64_t n_neg, void* workspace,
+                         size_t workspace_bytes, float* loss, float* dx, float* g_ent, void* stream);
+
+/* One Trainer.train_step_projection (utils/trainer.py:159-174): forward(h, r, hr_t, "tail") + forward(t, r, tr_h, "head") + get_reg:
+ * both bodies, kge_proje_label_loss per direction (labels: the hr_t / tr_h CSRs of the batch plus the shared negative list), both
+ * body backwards, then ONE sweep over ent, rel, De1, Dr1, De2, Dr2 that adds lmbda * sum |w| to the loss and lmbda * sign(w)
+ * (sign(0) = 0) to their gradients; bc1 / bc2 are not regularised.  The step's whole loss reaches `loss` as one float. */
+size_t kge_proje_train_workspace_bytes(const kge_proje_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr, int64_t n_neg);
+int kge_proje_train(const kge_proje_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch,
+                    const int64_t* hr_off, const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids,
+                    int64_t n_tr, const int32_t* neg, int64_t n_neg, float lmbda, void* workspace, size_t workspace_bytes, float* loss,
+                    void* stream);
+
+/* Filtered and raw ranks, arguments and `ranks` layout ([4, n]) of kge_tucker_eval_ranks: the body WITHOUT dropout on (h, r) with side
+ * 0 and on (t, r) with side 1 (predict_tail_rank / predict_head_rank), then kge_head_1n_rank per side with no bias. */
+size_t kge_proje_eval_ranks_workspace_bytes(const kge_proje_desc* d, int64_t n);
+int kge_proje_eval_ranks(const kge_proje_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                         const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                         int32_t* ties, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

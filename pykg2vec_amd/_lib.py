@@ -147,7 +147,38 @@ class TuckerDesc(ctypes.Structure):
 
 _TKD = ctypes.POINTER(TuckerDesc)
 
+PROJE_TABLES = ("ent", "rel", "bc1", "De1", "Dr1", "bc2", "De2", "Dr2")   # parameter_list order of ProjE_pointwise
+
+
+class ProjeDesc(ctypes.Structure):
+    """struct kge_proje_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("dim", ctypes.c_int32),
+                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64)] \
+        + [(n, ctypes.c_void_p) for n in PROJE_TABLES] + [("g_" + n, ctypes.c_void_p) for n in PROJE_TABLES]
+
+
+_PJD = ctypes.POINTER(ProjeDesc)
+
 _SIGNATURES = {
+    "kge_proje_body_forward_workspace_bytes": (ctypes.c_size_t, [_PJD, ctypes.c_int64]),
+    "kge_proje_body_forward": (ctypes.c_int, [_PJD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_proje_body_backward_workspace_bytes": (ctypes.c_size_t, [_PJD, ctypes.c_int64]),
+    "kge_proje_body_backward": (ctypes.c_int, [_PJD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_proje_label_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
+    "kge_proje_label_loss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_size_t] + [ctypes.c_void_p] * 4),
+    "kge_proje_train_workspace_bytes": (ctypes.c_size_t, [_PJD] + [ctypes.c_int64] * 4),
+    "kge_proje_train": (ctypes.c_int, [_PJD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                                      ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
+                                                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_proje_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_PJD, ctypes.c_int64]),
+    "kge_proje_eval_ranks": (ctypes.c_int, [_PJD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_tucker_saved_floats": (ctypes.c_size_t, [_TKD, ctypes.c_int64]),
     "kge_tucker_body_forward_workspace_bytes": (ctypes.c_size_t, [_TKD, ctypes.c_int64]),
     "kge_tucker_body_forward": (ctypes.c_int, [_TKD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,

@@ -1,4 +1,4 @@
-"""Loss functions with the reference's signatures (pykg2vec/utils/criterion.py:13-34).
+"""Loss functions with the reference's signatures (pykg2vec/utils/criterion.py:13-54).
 
 These tensor-level forms exist so that the UNMODIFIED reference Trainer (`loss = self.model.loss(pos, neg, margin)`,
 utils/trainer.py:147-180) can drive the drop-in models; they act on [B] score vectors only.  The MI355X training
@@ -32,3 +32,7 @@ class Criterion:
             tr_h = tr_h * (1.0 - label_smoothing) + 1.0 / tot_entity
         bce = torch.nn.BCEWithLogitsLoss()  # (sic) applied to sigmoid outputs, as the reference does
         return torch.mean(bce(pred_heads, tr_h)) + torch.mean(bce(pred_tails, hr_t))
+
+    @staticmethod
+    def multi_class(pred_heads, pred_tails):  # criterion.py:52-54: ProjE_pointwise's forward already returns the direction's loss
+        return pred_heads + pred_tails

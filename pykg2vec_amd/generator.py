@@ -15,6 +15,7 @@ import torch
 
 from . import kernels as K
 from .common import TrainingStrategy
+from .criterion import Criterion
 
 
 def _triples_array(data):
@@ -314,7 +315,9 @@ class Generator:
         if self.training_strategy not in (TrainingStrategy.PAIRWISE_BASED, TrainingStrategy.POINTWISE_BASED,
                                           TrainingStrategy.PROJECTION_BASED):
             raise NotImplementedError("This strategy is not supported.")
-        if self.training_strategy == TrainingStrategy.PROJECTION_BASED and int(config.neg_rate) > 0:
+        # ProjE_pointwise (loss = Criterion.multi_class) trains on the -1 labels the reference writes for neg_rate > 0
+        self.label_negatives = getattr(model, "loss", None) is Criterion.multi_class
+        if self.training_strategy == TrainingStrategy.PROJECTION_BASED and int(config.neg_rate) > 0 and not self.label_negatives:
             # data/generator.py:178-209 then writes -1 into the label rows of the corrupted entities: BCE targets outside [0, 1]
             raise NotImplementedError("projection models: neg_rate > 0 is not supported (the reference then writes -1 into the BCE "
                                       "targets); the reference's presets use neg_rate 0")
@@ -350,6 +353,7 @@ class Generator:
         self._pending = 0
         self._batch_idx = 0
         self._draws = 0  # Philox counter offset: unique per generated negative over the whole run
+        self._label_batches = 0  # batches handed out over the whole run: with the seed, the key of a batch's negative label list
 
     def pull_index(self, groups_per_block=None, compact=None, segment=None):
         """Incidence index of every FULL batch of the permutation (built on first use).  groups_per_block: owner groups per
@@ -420,13 +424,26 @@ class Generator:
         return start, n, offset
 
     def _next_projection(self):
-        """[h, r, t, (hr_t off, ids), (tr_h off, ids)] of the next batch: the label rows of data/generator.py:178-209 as CSR (off int64
-        [B + 1], ids int32), built on the device from the TRAINING split alone (hr_t_train / tr_h_train); the dense [B, E] rows of the
-        reference are never formed."""
+        """[h, r, t, (hr_t off, ids), (tr_h off, ids)] of the next batch (ProjE_pointwise: plus the batch's negative label ids, or
+        None): the label rows of data/generator.py:178-209 as CSR (off int64 [B + 1], ids int32), built on the device from the TRAINING
+        split alone (hr_t_train / tr_h_train); the dense [B, E] rows of the reference are never formed."""
         start, n, _ = self._next_range()
         trip = self.triples[self.perm[start:start + n]].contiguous()
         t_off, t_ids, h_off, h_ids = self.K.filter_csr_build(self.triples, trip, self.config.tot_entity, self.config.tot_relation)
-        return [trip[:, 0].contiguous(), trip[:, 1].contiguous(), trip[:, 2].contiguous(), (t_off, t_ids), (h_off, h_ids)]
+        batch = [trip[:, 0].contiguous(), trip[:, 1].contiguous(), trip[:, 2].contiguous(), (t_off, t_ids), (h_off, h_ids)]
+        if self.label_negatives:
+            batch.append(self.negative_labels(self._label_batches) if self.neg_rate > 0 else None)
+            self._label_batches += 1
+        return batch
+
+    NEGATIVE_LABELS = 100   # data/generator.py:200,212: np.random.permutation(E)[0:100], whatever the positive value of neg_rate
+
+    def negative_labels(self, batch):
+        """int32 device tensor of min(100, E) DISTINCT entity ids: the columns that carry the label -1 in every row and both directions
+        of global batch number `batch` (except where a row has a +1; data/generator.py:200-217), drawn on the host from (seed, batch)."""
+        E = int(self.config.tot_entity)
+        ids = np.random.default_rng((self.seed, int(batch))).permutation(E)[:self.NEGATIVE_LABELS]
+        return torch.from_numpy(ids.astype(np.int32)).to(self.device)
 
     def __next__(self):
         if self.training_strategy == TrainingStrategy.PROJECTION_BASED:

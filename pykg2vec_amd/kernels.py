@@ -722,6 +722,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
         return convkb_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids)
     if isinstance(desc, L.TuckerDesc):
         return tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
+    if isinstance(desc, L.ProjeDesc):
+        return proje_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -1572,7 +1574,7 @@ def tucker_desc(tables, grads=None, *, tot_entity, tot_relation, d1, d2, dropout
     return d
 
 
-def _tucker_ws(desc, query, *args):
+def _desc_ws(desc, query, *args):
     """(pointer, bytes) of the descriptor's workspace, grown to what `query` asks for; kept with the descriptor, so the steps of a
     Trainer allocate nothing once the largest label list has been seen."""
     need = int(getattr(L.load(), query)(ctypes.byref(desc), *args))
@@ -1595,7 +1597,7 @@ def tucker_body_forward(desc, e, r):
         raise ValueError("e, r must have equal lengths")
     x = torch.empty((n, desc.d1), dtype=torch.float32, device=e.device)
     saved = torch.empty(max(1, n * (2 * desc.d1 + 2)), dtype=torch.float32, device=e.device)
-    wp, wb = _tucker_ws(desc, "kge_tucker_body_forward_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_tucker_body_forward_workspace_bytes", n)
     L.check(L.load().kge_tucker_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, _dev(x, torch.float32, "x"),
                                              _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_tucker_body_forward")
     return x, saved
@@ -1604,7 +1606,7 @@ def tucker_body_forward(desc, e, r):
 def tucker_body_backward(desc, e, r, dx, saved):
     """g_* of the descriptor += the body's gradients given d loss / d x (same rows, seed, offset and `saved` as the forward)."""
     n = e.numel()
-    wp, wb = _tucker_ws(desc, "kge_tucker_body_backward_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_tucker_body_backward_workspace_bytes", n)
     L.check(L.load().kge_tucker_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, _dev(dx, torch.float32, "dx"),
                                               _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_tucker_body_backward")
 
@@ -1616,7 +1618,7 @@ def tucker_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smooth
     if r.numel() != B or t.numel() != B or hr_off.numel() != B + 1 or tr_off.numel() != B + 1:
         raise ValueError("tucker_train_bce: h, r, t must have equal lengths B and the label offsets B + 1 entries")
     n_hr, n_tr = int(hr_ids.numel()), int(tr_ids.numel())
-    wp, wb = _tucker_ws(desc, "kge_tucker_train_bce_workspace_bytes", B, n_hr, n_tr)
+    wp, wb = _desc_ws(desc, "kge_tucker_train_bce_workspace_bytes", B, n_hr, n_tr)
     L.check(L.load().kge_tucker_train_bce(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), B,
                                           _dev(hr_off, torch.int64, "hr_t offsets"), _dev(hr_ids, torch.int32, "hr_t ids") if n_hr else None,
                                           n_hr, _dev(tr_off, torch.int64, "tr_h offsets"),
@@ -1635,9 +1637,120 @@ def tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, tie
             args += [None, None]
         else:
             args += [_dev(off, torch.int64, "csr offsets"), ctypes.c_void_p(ids.data_ptr()) if ids.numel() else ctypes.c_void_p(off.data_ptr())]
-    wp, wb = _tucker_ws(desc, "kge_tucker_eval_ranks_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_tucker_eval_ranks_workspace_bytes", n)
     L.check(L.load().kge_tucker_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
                                            _dev(ranks, torch.int32, "ranks"),
                                            _dev(ties, torch.int32, "ties") if ties is not None else None, _stream()),
             "kge_tucker_eval_ranks")
+    return ranks
+
+
+# ---------------------------------------------------------------- ProjE_pointwise (csrc/kge_proje.hip): its own descriptor and entry points
+def proje_desc(tables, grads=None, *, tot_entity, tot_relation, dim, hidden_dropout=0.0, train=False, seed=0, offset=0):
+    """kge_proje_desc.  `tables` / `grads`: ent_embeddings.weight [E, k], rel_embeddings.weight [R, k] and the six rows bc1, De1, Dr1, bc2,
+    De2, Dr2 [1, k] (the model's parameter_list order).  Shapes are checked here (the kernels index rows by id without a bounds
+    test); the dropout rate and the offset are checked by the library, which refuses bad ones loudly."""
+    E, R, k = int(tot_entity), int(tot_relation), int(dim)
+    if len(tables) != 8:
+        raise L.KgeHipError("proje: 8 tensors expected (ent, rel, bc1, De1, Dr1, bc2, De2, Dr2), got %d" % len(tables))
+    for name, t, rows in (("ent_embeddings", tables[0], E), ("rel_embeddings", tables[1], R)):
+        if t.dim() != 2 or t.shape[1] != k or t.shape[0] < rows:
+            raise L.KgeHipError("proje: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
+                                % (name, rows, k, tuple(t.shape)))
+    for name, t in zip(L.PROJE_TABLES[2:], tables[2:]):
+        if t.numel() != k:
+            raise L.KgeHipError("proje: %s must hold %d floats (got %s)" % (name, k, tuple(t.shape)))
+    d = L.ProjeDesc()
+    d.tot_entity, d.tot_relation, d.dim, d.hidden_dropout = E, R, k, float(hidden_dropout)
+    d.train, d.seed, d.offset = int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    for name, t in zip(L.PROJE_TABLES, tables):
+        setattr(d, name, _dev(t, torch.float32, name).value)
+    if grads is not None:
+        if len(grads) != 8:
+            raise L.KgeHipError("proje: 8 gradient tensors expected, got %d" % len(grads))
+        for name, g, t in zip(L.PROJE_TABLES, grads, tables):
+            if g.shape != t.shape:
+                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
+            setattr(d, "g_" + name, _dev(g, torch.float32, "grad of " + name).value)
+    d._keepalive = (tables, grads)
+    d._ws = None
+    return d
+
+
+def proje_body_forward(desc, e, r, side):
+    """x float32 [n, k] = tanh(ent[e] o De_s + rel[r] o Dr_s + bc_s) * mask on side s (0: the tail direction's f1, 1: the head
+    direction's f2)."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    x = torch.empty((n, desc.dim), dtype=torch.float32, device=e.device)
+    wp, wb = _desc_ws(desc, "kge_proje_body_forward_workspace_bytes", n)
+    L.check(L.load().kge_proje_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(side), _dev(x, torch.float32, "x"),
+                                            wp, wb, _stream()), "kge_proje_body_forward")
+    return x
+
+
+def proje_body_backward(desc, e, r, side, dx):
+    """g_* of the descriptor += the body's gradients given d loss / d x (same rows, side, seed and offset as the forward)."""
+    n = e.numel()
+    wp, wb = _desc_ws(desc, "kge_proje_body_backward_workspace_bytes", n)
+    L.check(L.load().kge_proje_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(side),
+                                             _dev(dx, torch.float32, "dx"), wp, wb, _stream()), "kge_proje_body_backward")
+
+
+def proje_label_loss(x, ent, pos_off, pos_ids, neg, loss_buf, g_ent):
+    """One direction of ProjE's loss over the labelled columns (kge_proje_label_loss): adds to loss_buf and g_ent, returns dx.
+    pos_off int64 [B + 1] / pos_ids int32: the rows' positives; neg: int32 ids shared by all rows, or None."""
+    B, k = x.shape
+    E = ent.shape[0]
+    if pos_off.numel() != B + 1 or ent.shape[1] != k or g_ent.shape != ent.shape:
+        raise ValueError("proje_label_loss: x [B, k], ent / g_ent [E, k] and B + 1 offsets expected")
+    n_pos, n_neg = int(pos_ids.numel()), 0 if neg is None else int(neg.numel())
+    lib = L.load()
+    need = int(lib.kge_proje_label_loss_workspace_bytes(B, k, n_pos, n_neg))
+    if need == 0:
+        L.check(-1, "kge_proje_label_loss_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    dx = torch.empty_like(x)
+    L.check(lib.kge_proje_label_loss(_dev(x, torch.float32, "x"), B, k, _dev(ent, torch.float32, "ent"), E,
+                                     _dev(pos_off, torch.int64, "positive offsets"),
+                                     _dev(pos_ids, torch.int32, "positive ids") if n_pos else None, n_pos,
+                                     _dev(neg, torch.int32, "negative ids") if n_neg else None, n_neg,
+                                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), _dev(loss_buf, torch.float32, "loss"),
+                                     _dev(dx, torch.float32, "dx"), _dev(g_ent, torch.float32, "g_ent"), _stream()),
+            "kge_proje_label_loss")
+    return dx
+
+
+def proje_train(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, neg, lmbda, loss_buf):
+    """One train_step_projection of ProjE_pointwise: adds to loss_buf and to the descriptor's gradients.  hr_* / tr_*: the label
+    CSRs of the batch (off int64 [B + 1], ids int32); neg: the batch's shared negative ids (int32) or None."""
+    B = h.numel()
+    if r.numel() != B or t.numel() != B or hr_off.numel() != B + 1 or tr_off.numel() != B + 1:
+        raise ValueError("proje_train: h, r, t must have equal lengths B and the label offsets B + 1 entries")
+    n_hr, n_tr, n_neg = int(hr_ids.numel()), int(tr_ids.numel()), 0 if neg is None else int(neg.numel())
+    wp, wb = _desc_ws(desc, "kge_proje_train_workspace_bytes", B, n_hr, n_tr, n_neg)
+    L.check(L.load().kge_proje_train(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), B,
+                                     _dev(hr_off, torch.int64, "hr_t offsets"), _dev(hr_ids, torch.int32, "hr_t ids") if n_hr else None,
+                                     n_hr, _dev(tr_off, torch.int64, "tr_h offsets"),
+                                     _dev(tr_ids, torch.int32, "tr_h ids") if n_tr else None, n_tr,
+                                     _dev(neg, torch.int32, "negative ids") if n_neg else None, n_neg, float(lmbda), wp, wb,
+                                     _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_proje_train")
+
+
+def proje_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks, in one kge_proje_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
+    n = triples.shape[0]
+    ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
+    args = []
+    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
+        if off is None:
+            args += [None, None]
+        else:
+            args += [_dev(off, torch.int64, "csr offsets"), ctypes.c_void_p(ids.data_ptr()) if ids.numel() else ctypes.c_void_p(off.data_ptr())]
+    wp, wb = _desc_ws(desc, "kge_proje_eval_ranks_workspace_bytes", n)
+    L.check(L.load().kge_proje_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
+                                          _dev(ranks, torch.int32, "ranks"),
+                                          _dev(ties, torch.int32, "ties") if ties is not None else None, _stream()),
+            "kge_proje_eval_ranks")
     return ranks

@@ -7,6 +7,8 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
   torch.ops.kge.convkb_score_backward(key, h, r, t, dscore, weights) -> their dense gradients (the filters are fixed inputs)
   torch.ops.kge.tucker_body(key, e, r, seed, offset, weights) -> (x float32 [N, d1], saved)   the body of TuckER.forward (models/projection.py:321-334); weights = ent, rel, W
   torch.ops.kge.tucker_body_backward(key, e, r, seed, offset, dx, saved, weights) -> their dense gradients
+  torch.ops.kge.proje_body(key, e, r, side, seed, offset, weights) -> x float32 [N, k]   tanh(ent[e] o De_s + rel[r] o Dr_s + bc_s) with dropout: f1 / f2 of ProjE_pointwise (models/projection.py:212-228); weights = its parameter_list
+  torch.ops.kge.proje_body_backward(key, e, r, side, seed, offset, dx, weights) -> their dense gradients
   torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]   the projection models' 1-N head (models/projection.py:100-102)
   torch.ops.kge.one_to_n_scores_backward(x, ent, preds, dpreds, need_bias) -> (dx, g_ent, g_bias)
 
@@ -176,6 +178,53 @@ def _tucker_backward(ctx, dx, _dsaved):
 
 
 tucker_body.register_autograd(_tucker_backward, setup_context=_tucker_setup)
+
+
+# ProjE_pointwise's body (include/kge_hip.h: kge_proje_body_*).  side 0 = f1 (the tail direction), 1 = f2; offset < 0 = no dropout.  The
+# backward recomputes the body from the tables: nothing but the ids is saved.
+@torch.library.custom_op("kge::proje_body", mutates_args=(), device_types="cuda")
+def proje_body(key: int, e: Tensor, r: Tensor, side: int, seed: int, offset: int, weights: List[Tensor]) -> Tensor:
+    m = _model(key)
+    return K.proje_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                                r.contiguous(), side)
+
+
+@proje_body.register_fake
+def _(key, e, r, side, seed, offset, weights):
+    return weights[0].new_empty((e.numel(), weights[0].shape[1]))
+
+
+@proje_body.register_kernel("cpu")
+def _(key, e, r, side, seed, offset, weights):
+    raise L.KgeHipError("kge::proje_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
+
+
+@torch.library.custom_op("kge::proje_body_backward", mutates_args=(), device_types="cuda")
+def proje_body_backward(key: int, e: Tensor, r: Tensor, side: int, seed: int, offset: int, dx: Tensor, weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.proje_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                          r.contiguous(), side, dx.contiguous())
+    return grads
+
+
+@proje_body_backward.register_fake
+def _(key, e, r, side, seed, offset, dx, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _proje_setup(ctx, inputs, output):
+    key, e, r, side, seed, offset, weights = inputs
+    ctx.key, ctx.side, ctx.seed, ctx.offset = key, side, seed, offset
+    ctx.save_for_backward(e, r, *weights)
+
+
+def _proje_backward(ctx, dx):
+    e, r, *weights = ctx.saved_tensors
+    return None, None, None, None, None, None, proje_body_backward(ctx.key, e, r, ctx.side, ctx.seed, ctx.offset, dx, weights)
+
+
+proje_body.register_autograd(_proje_backward, setup_context=_proje_setup)
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

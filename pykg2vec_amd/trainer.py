@@ -91,8 +91,9 @@ class Trainer:
         return self.model.training_strategy == TrainingStrategy.PROJECTION_BASED
 
     def _refuse_projection(self):
-        """The projection path (TuckER, csrc/kge_tucker.hip) is the fused single-GPU step: body, 1-N head with multi_class_bce per
-        direction, body backward.  What it does not serve is refused here, before anything is built."""
+        """The projection path is the fused single-GPU step.  TuckER (csrc/kge_tucker.hip): body, 1-N head with multi_class_bce per
+        direction, body backward.  ProjE_pointwise (csrc/kge_proje.hip): body, the loss over the labelled columns per direction, body
+        backward, regulariser.  What it does not serve is refused here, before anything is built."""
         def no(what):
             raise NotImplementedError("%s: %s is not supported on the projection path (single-GPU fused step only)"
                                       % (type(self.model).__name__, what))
@@ -106,8 +107,8 @@ class Trainer:
         for switch, what in (("pw_pull", "the owner-computes step (KGE_PW_PULL=1)"), ("staged", "the staged step (KGE_STAGED=1)")):
             if self.switches.get(switch):
                 no(what)
-        if int(getattr(self.config, "neg_rate", 0) or 0) > 0:
-            no("neg_rate > 0 (the reference then writes -1 into the BCE targets)")
+        if int(getattr(self.config, "neg_rate", 0) or 0) > 0 and getattr(self.model, "kernel_name", None) != "proje":
+            no("neg_rate > 0 (the reference then writes -1 into the BCE targets)")   # (for ProjE_pointwise the -1 labels are the model)
         if self.use_graph:
             no("hipGraph capture of the step (the label lists change length from batch to batch)")
 
@@ -265,12 +266,16 @@ class Trainer:
                 self._batch_entity_ids = torch.cat([data[0], data[2]])
             self._accumulate_pointwise(*data)
 
-    def _accumulate_projection(self, h, r, t, hr_t_csr, tr_h_csr):
+    def _accumulate_projection(self, h, r, t, hr_t_csr, tr_h_csr, neg=None):
         """The fused projection step into the gradient / loss buffers.  The dropout masks of step s are the Philox masks of
-        (config.seed, s): a run is reproducible from the seed."""
+        (config.seed, s): a run is reproducible from the seed.  neg: ProjE_pointwise's negative label ids of the batch, or None."""
         d = self._desc
         d.train, d.seed, d.offset = int(self.model.training), int(getattr(self.config, "seed", 0) or 0) & (2 ** 64 - 1), self._projection_step
         self._projection_step += 1
+        if self.model.kernel_name == "proje":
+            d.train = 1   # the reference's torch.dropout(..., train=True): drawn whatever the module's mode
+            self.K.proje_train(d, h, r, t, hr_t_csr[0], hr_t_csr[1], tr_h_csr[0], tr_h_csr[1], neg, self.model.lmbda, self.loss_buf)
+            return
         ls = getattr(self.config, "label_smoothing", None) if hasattr(self.config, "label_smoothing") else None
         self.K.tucker_train_bce(d, h, r, t, hr_t_csr[0], hr_t_csr[1], tr_h_csr[0], tr_h_csr[1], ls, self.loss_buf)
 
@@ -1048,10 +1053,11 @@ class Trainer:
         self._accumulate_pointwise(h, r, t, target)
         return self.K.read_loss(self.loss_buf)
 
-    def train_step_projection(self, h, r, t, hr_t_csr, tr_h_csr):
-        """utils/trainer.py:159-172 with the label rows as CSR pairs (off int64 [B + 1], ids int32), as the Generator yields them."""
+    def train_step_projection(self, h, r, t, hr_t_csr, tr_h_csr, neg=None):
+        """utils/trainer.py:159-174 with the label rows as CSR pairs (off int64 [B + 1], ids int32) and, for ProjE_pointwise, the batch's
+        negative label ids (int32) or None, as the Generator yields them."""
         self.loss_buf.zero_()
-        self._accumulate_projection(h, r, t, hr_t_csr, tr_h_csr)
+        self._accumulate_projection(h, r, t, hr_t_csr, tr_h_csr, neg)
         return self.K.read_loss(self.loss_buf)
 
     # ------------------------------------------------------------------ hipGraph replay of the whole step

@@ -1,0 +1,32 @@
+"""CPU-only check of the resources of every ProjE kernel (csrc/kge_proje.hip), read from the AMDGPU metadata of the built library with
+the helpers of test_pull_occupancy.py: no scratch, no spills, and the VGPR and LDS figures of the table in DESIGN.md section 16."""
+import pytest
+
+from test_pull_occupancy import metadata  # noqa: F401  (module fixture: {kernel name: metadata} of the gfx950 code objects)
+
+# prefix -> (VGPRs, static LDS bytes): DESIGN.md section 16
+KERNELS = {
+    "_ZN3kge12k_proje_bodyE": (28, 0), "_ZN3kge16k_proje_body_bwdE": (34, 0), "_ZN3kge12k_proje_rowsE": (28, 12288),
+    "_ZN3kge14k_proje_logitsE": (16, 0), "_ZN3kge10k_proje_dxE": (18, 0), "_ZN3kge12k_proje_gnegE": (14, 0),
+    "_ZN3kge12k_proje_gposE": (16, 0), "_ZN3kge11k_proje_regE": (35, 2048), "_ZN3kge14k_proje_finishE": (12, 8192),
+    "_ZN3kge16k_proje_eval_idsE": (15, 0), "_ZN3kge18k_proje_pack_ranksE": (12, 0),
+}
+
+
+@pytest.mark.parametrize("prefix", sorted(KERNELS))
+def test_proje_kernel_resources(metadata, prefix):   # noqa: F811
+    found = [k for k in metadata if k.startswith(prefix)]
+    assert len(found) == 1, (prefix, found)
+    md = metadata[found[0]]
+    vgpr, lds = KERNELS[prefix]
+    print(prefix, "vgpr", md["vgpr_count"], "lds", md["group_segment_fixed_size"], "scratch", md["private_segment_fixed_size"])
+    assert int(md["private_segment_fixed_size"]) == 0, (prefix, md["private_segment_fixed_size"])
+    assert int(md["vgpr_spill_count"]) == 0 and int(md["sgpr_spill_count"]) == 0, (prefix, md["vgpr_spill_count"], md["sgpr_spill_count"])
+    assert md.get("uses_dynamic_stack", "false") == "false", prefix
+    assert int(md["vgpr_count"]) == vgpr, (prefix, md["vgpr_count"])
+    assert int(md["group_segment_fixed_size"]) == lds, (prefix, md["group_segment_fixed_size"])
+
+
+def test_every_proje_kernel_is_checked(metadata):   # noqa: F811
+    kernels = [k for k in metadata if "k_proje_" in k]
+    assert len(kernels) == len(KERNELS), kernels
