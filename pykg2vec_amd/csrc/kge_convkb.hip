@@ -21,6 +21,7 @@
 //   rank                 P_h[e] = <A_h, ent[e]>, P_t[e] = <A_t, ent[e]>, P_r[r] = <A_r, rel[r]> in one pass over the tables; the energy of
 //                        candidate e is the fp32 sum q + P[e] with q the query's constant; the sweep stores it, the rank counts on it
 #include "kge_row_kernels.h"
+#include "kge_projection.h"   // ws_check
 
 namespace kge {
 
@@ -397,11 +398,6 @@ static size_t ckb_eval_bytes(const kge_convkb_desc* d) {
     return ckb_vec_bytes(d) + align256((size_t)(2 * d->tot_entity + d->tot_relation) * sizeof(float));
 }
 
-static int ckb_ws_check(const char* who, const void* ws, size_t have, size_t need) {
-    if (!ws || have < need) { set_error("%s: workspace too small (%zu < %zu bytes)", who, ws ? have : (size_t)0, need); return -1; }
-    return 0;
-}
-
 static int ckb_collapse(const kge_convkb_desc* d, float* out, hipStream_t s) {
     const CkbGeom g = ckb_geom(d);
     const unsigned blocks = (unsigned)((3 * g.k + kBlock - 1) / kBlock) + 1;
@@ -472,7 +468,7 @@ int kge_convkb_score_forward(const kge_convkb_desc* d, const int64_t* h, const i
     const char* who = "kge_convkb_score_forward";
     if (ckb_check(d, who, false)) return -1;
     if (n < 0 || (n > 0 && (!h || !r || !t || !scores))) { set_error("%s: bad arguments", who); return -1; }
-    if (ckb_ws_check(who, workspace, workspace_bytes, ckb_vec_bytes(d))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ckb_vec_bytes(d))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const kge_model_desc bounds = ckb_id_bounds(d);
@@ -496,7 +492,7 @@ int kge_convkb_score_backward(const kge_convkb_desc* d, const int64_t* h, const 
     const char* who = "kge_convkb_score_backward";
     if (ckb_check(d, who, true)) return -1;
     if (n < 0 || (n > 0 && (!h || !r || !t || !dscore))) { set_error("%s: bad arguments", who); return -1; }
-    if (ckb_ws_check(who, workspace, workspace_bytes, ckb_step_bytes(d, n))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ckb_step_bytes(d, n))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const kge_model_desc bounds = ckb_id_bounds(d);
@@ -513,7 +509,7 @@ int kge_convkb_train_logistic(const kge_convkb_desc* d, const int64_t* h, const 
     const char* who = "kge_convkb_train_logistic";
     if (ckb_check(d, who, true)) return -1;
     if (n < 0 || !loss || (n > 0 && (!h || !r || !t || !y))) { set_error("%s: bad arguments", who); return -1; }
-    if (ckb_ws_check(who, workspace, workspace_bytes, ckb_step_bytes(d, n))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ckb_step_bytes(d, n))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const kge_model_desc bounds = ckb_id_bounds(d);
@@ -545,7 +541,7 @@ int kge_convkb_train_logistic_sampled(const kge_convkb_desc* d, const int64_t* t
         set_error("%s: ConvKB with hidden size %d takes neg_rate <= %d", who, d->dim, ckb_group(d->dim) - 1);
         return -1;
     }
-    if (ckb_ws_check(who, workspace, workspace_bytes, ckb_step_bytes(d, n_pos))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ckb_step_bytes(d, n_pos))) return -1;
     if (n_pos == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (!dev_cursor)
@@ -592,7 +588,7 @@ int kge_convkb_eval_ranks(const kge_convkb_desc* d, const int64_t* triples, int6
         set_error("%s: bad arguments", who);
         return -1;
     }
-    if (ckb_ws_check(who, workspace, workspace_bytes, ckb_eval_bytes(d))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ckb_eval_bytes(d))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = debug_check_triples(who, d->tot_entity, d->tot_relation, triples, n, s)) return rc;
@@ -611,7 +607,7 @@ int kge_convkb_sweep_scores_side(const kge_convkb_desc* d, const int64_t* triple
         set_error("%s: bad arguments (side is 0 = tail sweep or 1 = head sweep)", who);
         return -1;
     }
-    if (ckb_ws_check(who, workspace, workspace_bytes, ckb_eval_bytes(d))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ckb_eval_bytes(d))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = debug_check_triples(who, d->tot_entity, d->tot_relation, triples, n, s)) return rc;

@@ -19,14 +19,9 @@
 // The product with the negative block is 2 B n_neg dim flops (8 MFLOP at the preset's shape): the step is bound by its launches and
 // by the regulariser's sweep over the tables, so the products stay on the vector ALUs in the simplest shape that is coalesced.
 //
-// Dropout masks are never stored: forward and backward recompute them from Philox4x32-10 (kge_sampler_device.h), TuckER's scheme:
-//     key     = (low 32 bits of seed, high 32 bits of seed)
-//     counter = (elem, row >> 2, site | (offset >> 32) << 2, offset & 0xffffffff),   word = row & 3
+// The dropout draw is the shared one (kge_projection.h spells the Philox counters out), with
 //     elem    = the column j of x;   site = the side s;   row = position in the call's row list
-// An element is KEPT iff its 32-bit word >= thr = floor(p * 2^32) (p the float dropout rate), and is then scaled by 1 / (1 - p) in fp32.
-// With train = 0 or p = 0 nothing is drawn.
-#include "kge_internal.h"
-#include "kge_sampler_device.h"
+#include "kge_projection.h"
 
 namespace kge {
 
@@ -36,7 +31,8 @@ constexpr int kPjRegBlocks = 512;     // workgroups (and double partials) of the
 constexpr int kPjPhases = 16;         // row phases of k_proje_rows: 64 columns x 16 phases per workgroup
 
 struct PjRng {
-    uint32_t k0, k1, hi, lo, thr;
+    DropKey key;
+    uint32_t thr;
     float scale;
     int drop;
 };
@@ -48,18 +44,6 @@ struct PjBody {
     PjRng g;
 };
 
-__device__ __forceinline__ float pj_factor(const PjRng& g, int side, int elem, int64_t row) {
-    const Philox x = philox4x32_10((uint32_t)elem, (uint32_t)(row >> 2), (uint32_t)side | (g.hi << 2), g.lo, g.k0, g.k1);
-    const int w = (int)(row & 3);
-    const uint32_t word = w == 0 ? x.c[0] : w == 1 ? x.c[1] : w == 2 ? x.c[2] : x.c[3];
-    return word >= g.thr ? g.scale : 0.0f;
-}
-__device__ __forceinline__ float pj_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // one wave per row: x[row] = tanh(ent[e] De + rel[r] Dr + bc) * m
 __global__ void __launch_bounds__(256) k_proje_body(PjBody a, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
                                                     float* __restrict__ x) {
@@ -70,7 +54,7 @@ __global__ void __launch_bounds__(256) k_proje_body(PjBody a, const int64_t* __r
     const float* __restrict__ rr = a.rel + r[row] * a.dim;
     for (int j = lane; j < a.dim; j += 64) {
         float v = tanhf(er[j] * a.De[j] + rr[j] * a.Dr[j] + a.bc[j]);
-        if (a.g.drop) v *= pj_factor(a.g, a.side, j, row);
+        if (a.g.drop) v *= drop_row_factor(a.g.key, a.side, j, row, a.g.thr, a.g.scale);
         x[row * a.dim + j] = v;
     }
 }
@@ -86,7 +70,7 @@ __global__ void __launch_bounds__(256) k_proje_body_bwd(PjBody a, const int64_t*
         const float De = a.De[j], Dr = a.Dr[j];
         const float y = tanhf(a.ent[eo + j] * De + a.rel[ro + j] * Dr + a.bc[j]);
         float g = dx[row * a.dim + j];
-        if (a.g.drop) g *= pj_factor(a.g, a.side, j, row);
+        if (a.g.drop) g *= drop_row_factor(a.g.key, a.side, j, row, a.g.thr, a.g.scale);
         g *= 1.0f - y * y;
         dpre[row * a.dim + j] = g;
         unsafeAtomicAdd(a.g_ent + eo + j, g * De);
@@ -170,7 +154,7 @@ __global__ void __launch_bounds__(256) k_proje_logits(PjLabels a, float* __restr
         const float* __restrict__ er = a.ent + (int64_t)c * a.dim;
         float z = 0.0f;
         for (int j = lane; j < a.dim; j += 64) z += xr[j] * er[j];
-        z = pj_wave_sum(z);
+        z = wave_sum_xor(z);
         const float s = 1.0f / (1.0f + expf(-z));
         const float u = 1.0f - s;
         if (negative) {
@@ -286,25 +270,6 @@ __global__ void __launch_bounds__(1024) k_proje_finish(const double* __restrict_
     if (threadIdx.x == 0) unsafeAtomicAdd(loss, (float)tot);
 }
 
-// the rank pass's glue: triples with the true entity of the head sweep in column 2, and the [4, n] layout of kge_eval_ranks
-__global__ void k_proje_eval_ids(const int64_t* __restrict__ triples, int64_t n, int64_t* __restrict__ e, int64_t* __restrict__ r,
-                                 int64_t* __restrict__ swapped) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t h = triples[3 * i], rel = triples[3 * i + 1], t = triples[3 * i + 2];
-    e[i] = h; e[n + i] = t;
-    r[i] = rel;
-    swapped[3 * i] = t; swapped[3 * i + 1] = rel; swapped[3 * i + 2] = h;
-}
-__global__ void k_proje_pack_ranks(const int32_t* __restrict__ tail, const int32_t* __restrict__ head, int64_t n, int32_t* __restrict__ ranks) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ranks[i] = head[i];
-    ranks[n + i] = tail[i];
-    ranks[2 * n + i] = head[n + i];
-    ranks[3 * n + i] = tail[n + i];
-}
-
 // ------------------------------------------------------------------------------------------------------------------ host side
 static int pj_check(const kge_proje_desc* d, const char* who, bool grads) {
     if (!d) { set_error("%s: null descriptor", who); return -1; }
@@ -319,11 +284,7 @@ static int pj_check(const kge_proje_desc* d, const char* who, bool grads) {
     }
     if (d->dim > kPjMaxDim) { set_error("%s: dim = %d exceeds %d", who, d->dim, kPjMaxDim); return -1; }
     if (d->tot_entity > 2147483647LL) { set_error("%s: tot_entity = %lld: label ids are int32", who, (long long)d->tot_entity); return -1; }
-    if (!(d->hidden_dropout >= 0.0f && d->hidden_dropout < 1.0f)) {
-        set_error("%s: the dropout rate must be in [0, 1) (got %g)", who, (double)d->hidden_dropout);
-        return -1;
-    }
-    if (d->offset >> 62) { set_error("%s: the Philox offset must be below 2^62", who); return -1; }
+    if (drop_check(who, &d->hidden_dropout, 1, d->offset)) return -1;
     if (grads && (!d->g_ent || !d->g_rel || !d->g_bc1 || !d->g_De1 || !d->g_Dr1 || !d->g_bc2 || !d->g_De2 || !d->g_Dr2)) {
         set_error("%s: null gradient buffers (all eight are required)", who);
         return -1;
@@ -334,10 +295,6 @@ static int pj_side_check(const char* who, int side) {
     if (side != 0 && side != 1) { set_error("%s: side must be 0 (tail direction) or 1 (head direction), got %d", who, side); return -1; }
     return 0;
 }
-static int pj_ws_check(const char* who, const void* ws, size_t have, size_t need) {
-    if (!ws || have < need) { set_error("%s: workspace too small (%zu < %zu bytes)", who, ws ? have : (size_t)0, need); return -1; }
-    return 0;
-}
 
 static PjBody pj_body(const kge_proje_desc* d, int side, int64_t n) {
     PjBody a{};
@@ -346,10 +303,9 @@ static PjBody pj_body(const kge_proje_desc* d, int side, int64_t n) {
     a.g_ent = d->g_ent; a.g_rel = d->g_rel;
     a.g_bc = side ? d->g_bc2 : d->g_bc1; a.g_De = side ? d->g_De2 : d->g_De1; a.g_Dr = side ? d->g_Dr2 : d->g_Dr1;
     a.dim = d->dim; a.side = side; a.n = n;
-    a.g.k0 = (uint32_t)d->seed; a.g.k1 = (uint32_t)(d->seed >> 32);
-    a.g.hi = (uint32_t)(d->offset >> 32); a.g.lo = (uint32_t)d->offset;
-    a.g.thr = (uint32_t)((double)d->hidden_dropout * 4294967296.0);
-    a.g.scale = 1.0f / (1.0f - d->hidden_dropout);
+    a.g.key = drop_key(d->seed, d->offset);
+    a.g.thr = drop_thr(d->hidden_dropout);
+    a.g.scale = drop_scale(d->hidden_dropout);
     a.g.drop = d->train != 0 && d->hidden_dropout > 0.0f;
     return a;
 }
@@ -366,10 +322,6 @@ static int pj_backward(const kge_proje_desc* d, const int64_t* e, const int64_t*
     hipLaunchKernelGGL(k_proje_body_bwd, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, a, e, r, dx, dpre);
     hipLaunchKernelGGL(k_proje_rows, dim3((unsigned)((d->dim + 63) / 64)), dim3(64 * kPjPhases), 0, s, a, e, r, dpre);
     return check_launch("k_proje_body_bwd / k_proje_rows");
-}
-static int pj_check_ids(const char* who, const kge_proje_desc* d, const int64_t* e, const int64_t* r, int64_t n, hipStream_t s) {
-    if (int rc = debug_check_ids(who, "entity", e, n, 1, 0, d->tot_entity, s)) return rc;
-    return debug_check_ids(who, "relation", r, n, 1, 0, d->tot_relation, s);
 }
 
 // one direction's labelled entries: dz float [B * n_neg + n_pos] and as many double terms
@@ -418,19 +370,15 @@ static PjStepPlan pj_step_plan(const kge_proje_desc* d, int64_t B, int64_t n_hr,
     return p;
 }
 
-// rank: ids e [2n] r [n] | swapped triples [3n int64] | x [2n, dim] | ranks of the two sweeps [2 x 2n int32] | head rank
-struct PjEvalPlan {
-    size_t ids, swapped, x, ranks, rest, total;
-};
-static PjEvalPlan pj_eval_plan(const kge_proje_desc* d, int64_t n) {
-    PjEvalPlan p{};
-    p.ids = 0;
-    p.swapped = align256((size_t)3 * n * sizeof(int64_t));
-    p.x = p.swapped + align256((size_t)3 * n * sizeof(int64_t));
-    p.ranks = p.x + align256((size_t)2 * n * d->dim * sizeof(float));
-    p.rest = p.ranks + align256((size_t)4 * n * sizeof(int32_t));
-    p.total = p.rest + align256(kge_head_1n_rank_workspace_bytes(n, d->dim, d->tot_entity, 0));
-    return p;
+// the rank pass's body (kge_projection.hip): predict_tail_rank / predict_head_rank, so no dropout; f1 on the h rows, f2 on the t rows
+static int pj_eval_body(const void* desc, const int64_t* e, const int64_t* r, int64_t n, float* x, void*, size_t, hipStream_t s) {
+    kge_proje_desc ev = *(const kge_proje_desc*)desc;
+    ev.train = 0;
+    if (int rc = pj_forward(&ev, e, r, n, 0, x, s)) return rc;
+    return pj_forward(&ev, e + n, r + n, n, 1, x + n * ev.dim, s);
+}
+static ProjectionEval pj_eval(const kge_proje_desc* d) {
+    return ProjectionEval{d->dim, d->tot_entity, d->tot_relation, d->ent, 0, pj_eval_body};
 }
 
 }  // namespace kge
@@ -448,10 +396,10 @@ int kge_proje_body_forward(const kge_proje_desc* d, const int64_t* e, const int6
     const char* who = "kge_proje_body_forward";
     if (pj_check(d, who, false) || pj_side_check(who, side)) return -1;
     if (n < 0 || n > (1LL << 33) || (n > 0 && (!e || !r || !x))) { set_error("%s: bad arguments", who); return -1; }
-    if (pj_ws_check(who, workspace, workspace_bytes, 256)) return -1;
+    if (ws_check(who, workspace, workspace_bytes, 256)) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = pj_check_ids(who, d, e, r, n, s)) return rc;
+    if (int rc = check_er_ids(who, d->tot_entity, d->tot_relation, e, r, n, s)) return rc;
     return pj_forward(d, e, r, n, side, x, s);
 }
 
@@ -464,10 +412,10 @@ int kge_proje_body_backward(const kge_proje_desc* d, const int64_t* e, const int
     const char* who = "kge_proje_body_backward";
     if (pj_check(d, who, true) || pj_side_check(who, side)) return -1;
     if (n < 0 || n > (1LL << 33) || (n > 0 && (!e || !r || !dx))) { set_error("%s: bad arguments", who); return -1; }
-    if (pj_ws_check(who, workspace, workspace_bytes, pj_bwd_bytes(d, n > 0 ? n : 1))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, pj_bwd_bytes(d, n > 0 ? n : 1))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = pj_check_ids(who, d, e, r, n, s)) return rc;
+    if (int rc = check_er_ids(who, d->tot_entity, d->tot_relation, e, r, n, s)) return rc;
     return pj_backward(d, e, r, n, side, dx, workspace, s);
 }
 
@@ -490,7 +438,7 @@ int kge_proje_label_loss(const float* x, int64_t batch, int32_t dim, const float
         set_error("%s: bad arguments", who);
         return -1;
     }
-    if (pj_ws_check(who, workspace, workspace_bytes, pj_dz_bytes(batch, n_pos, n_neg) + pj_term_bytes(batch, n_pos, n_neg))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, pj_dz_bytes(batch, n_pos, n_neg) + pj_term_bytes(batch, n_pos, n_neg))) return -1;
     if (batch == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (n_pos > 0)
@@ -523,13 +471,13 @@ int kge_proje_train(const kge_proje_desc* d, const int64_t* h, const int64_t* r,
         return -1;
     }
     const PjStepPlan p = pj_step_plan(d, batch > 0 ? batch : 1, n_hr, n_tr, n_neg);
-    if (pj_ws_check(who, workspace, workspace_bytes, p.total)) return -1;
+    if (ws_check(who, workspace, workspace_bytes, p.total)) return -1;
     if (batch == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int64_t B = batch;
     const int dim = d->dim;
     const int64_t E = d->tot_entity;
-    if (int rc = pj_check_ids(who, d, h, r, B, s)) return rc;
+    if (int rc = check_er_ids(who, d->tot_entity, d->tot_relation, h, r, B, s)) return rc;
     if (int rc = debug_check_ids(who, "entity", t, B, 1, 0, E, s)) return rc;
     if (n_hr > 0)
         if (int rc = debug_check_ids32(who, "hr_t label", hr_ids, n_hr, 1, 0, E, s)) return rc;
@@ -565,7 +513,7 @@ int kge_proje_train(const kge_proje_desc* d, const int64_t* h, const int64_t* r,
 }
 
 size_t kge_proje_eval_ranks_workspace_bytes(const kge_proje_desc* d, int64_t n) {
-    return pj_check(d, "kge_proje_eval_ranks_workspace_bytes", false) || n < 0 ? 0 : pj_eval_plan(d, n > 0 ? n : 1).total;
+    return pj_check(d, "kge_proje_eval_ranks_workspace_bytes", false) || n < 0 ? 0 : projection_eval_workspace_bytes(pj_eval(d), n);
 }
 
 int kge_proje_eval_ranks(const kge_proje_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
@@ -573,37 +521,8 @@ int kge_proje_eval_ranks(const kge_proje_desc* d, const int64_t* triples, int64_
                          int32_t* ties, void* stream) {
     const char* who = "kge_proje_eval_ranks";
     if (pj_check(d, who, false)) return -1;
-    if (n < 0 || (n > 0 && (!triples || !ranks)) || (tail_off && !tail_ids) || (head_off && !head_ids)) {
-        set_error("%s: bad arguments", who);
-        return -1;
-    }
-    const PjEvalPlan p = pj_eval_plan(d, n > 0 ? n : 1);
-    if (pj_ws_check(who, workspace, workspace_bytes, p.total)) return -1;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = debug_check_triples(who, d->tot_entity, d->tot_relation, triples, n, s)) return rc;
-    char* ws = (char*)workspace;
-    int64_t* e = (int64_t*)(ws + p.ids);
-    int64_t* rr = e + 2 * n;
-    int64_t* swapped = (int64_t*)(ws + p.swapped);
-    float* x = (float*)(ws + p.x);
-    int32_t* tmp = (int32_t*)(ws + p.ranks);
-    void* rest = ws + p.rest;
-    const size_t rest_bytes = p.total - p.rest;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_proje_eval_ids, dim3(blocks), dim3(256), 0, s, triples, n, e, rr, swapped);
-    if (int rc = check_launch("k_proje_eval_ids")) return rc;
-    kge_proje_desc ev = *d;
-    ev.train = 0;   // predict_tail_rank / predict_head_rank: no dropout
-    if (int rc = pj_forward(&ev, e, rr, n, 0, x, s)) return rc;
-    if (int rc = pj_forward(&ev, e + n, rr, n, 1, x + n * d->dim, s)) return rc;
-    // tail sweep: f1(h, r), true entity t, filter hr_t; head sweep: f2(t, r), true entity h, filter tr_h
-    if (int rc = kge_head_1n_rank(x, n, d->dim, d->ent, d->tot_entity, nullptr, triples, tail_off, tail_ids, rest, rest_bytes, tmp,
-                                  ties ? ties + n : nullptr, nullptr, stream)) return rc;
-    if (int rc = kge_head_1n_rank(x + n * d->dim, n, d->dim, d->ent, d->tot_entity, nullptr, swapped, head_off, head_ids, rest, rest_bytes,
-                                  tmp + 2 * n, ties, nullptr, stream)) return rc;
-    hipLaunchKernelGGL(k_proje_pack_ranks, dim3(blocks), dim3(256), 0, s, tmp, tmp + 2 * n, n, ranks);
-    return check_launch("k_proje_pack_ranks");
+    return projection_eval_ranks(who, pj_eval(d), d, triples, n, tail_off, tail_ids, head_off, head_ids, workspace, workspace_bytes, ranks,
+                                 ties, stream);
 }
 
 }  // extern "C"

@@ -17,16 +17,12 @@
 //     g_ent[e_b]    += g_a through m0 and the first normalisation (k_tucker_gent), added in row order (k_tucker_scatter)
 // No kernel of this file uses atomics: with the head's ordered split-K sums the whole step is bit-identical run to run.
 //
-// Dropout masks are never stored: forward and backward recompute them from Philox4x32-10 (kge_sampler_device.h).
-//     key     = (low 32 bits of seed, high 32 bits of seed)
-//     counter = (elem, row >> 2, site | (offset >> 32) << 2, offset & 0xffffffff),   word = row & 3
+// The dropout draw is the shared one (kge_projection.h spells the Philox counters out), with
 //     elem    = i (site 0), i * d1 + j (site 1), j (site 2);   row = position in the call's row list (the fused step: h rows, then t rows)
-// An element is KEPT iff its 32-bit word >= thr = floor(p * 2^32) (p the float dropout rate), and is then scaled by 1 / (1 - p) in fp32.
 // Four consecutive rows share one Philox call: the accumulator layout of the matrix cores holds four consecutive rows of one column
 // per lane, so the forward draws once per lane and 16 x 16 tile.  With train = 0 or p = 0 a site draws nothing (compile-time for site 1).
-#include "kge_internal.h"
+#include "kge_projection.h"
 #include "kge_mfma_blocks.h"
-#include "kge_sampler_device.h"
 
 namespace kge {
 
@@ -37,8 +33,8 @@ constexpr int kTkGwStride = 132;   // LDS row stride of its rel tile: rows 4 apa
 constexpr float kTkEps = 1e-12f;   // F.normalize
 
 struct TkRng {
-    uint32_t k0, k1, hi, lo;       // key, and the two offset words of the counter
-    uint32_t thr[3];
+    DropKey key;
+    uint32_t thr[3];               // per site; thr == 0 and scale == 1 draw nothing
     float scale[3];
 };
 struct TkArgs {
@@ -48,21 +44,8 @@ struct TkArgs {
     TkRng g;
 };
 
-__device__ __forceinline__ Philox tk_draw(const TkRng& g, uint32_t site, uint32_t elem, uint32_t rowgrp) {
-    return philox4x32_10(elem, rowgrp, site | (g.hi << 2), g.lo, g.k0, g.k1);
-}
-__device__ __forceinline__ uint32_t tk_word(const Philox& x, int w) {   // selects: a dynamic index would put the words in memory
-    return w == 0 ? x.c[0] : w == 1 ? x.c[1] : w == 2 ? x.c[2] : x.c[3];
-}
-// factor of element `elem` of row `row` at a row-wise site (0 or 2): 0 or scale; thr == 0 and scale == 1 draw nothing
-__device__ __forceinline__ float tk_row_factor(const TkRng& g, int site, int elem, int64_t row) {
-    const Philox x = tk_draw(g, (uint32_t)site, (uint32_t)elem, (uint32_t)(row >> 2));
-    return tk_word(x, (int)(row & 3)) >= g.thr[site] ? g.scale[site] : 0.0f;
-}
-__device__ __forceinline__ float tk_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+__device__ __forceinline__ float tk_row_factor(const TkRng& g, int site, int elem, int64_t row) {   // the row-wise sites 0 and 2
+    return drop_row_factor(g.key, site, elem, row, g.thr[site], g.scale[site]);
 }
 
 // one wave per row: a = normalize(ent[e]) * m0 -> a_out[n, d1], |ent[e]| -> na_out[n]
@@ -74,7 +57,7 @@ __global__ void __launch_bounds__(256) k_tucker_prep(TkArgs a, const int64_t* __
     const float* __restrict__ src = a.ent + e[row] * a.d1;
     float ss = 0.0f;
     for (int i = lane; i < a.d1; i += 64) ss += src[i] * src[i];
-    const float na = sqrtf(tk_wave_sum(ss));
+    const float na = sqrtf(wave_sum_xor(ss));
     const float den = fmaxf(na, kTkEps);
     for (int i = lane; i < a.d1; i += 64) {
         float v = src[i] / den;
@@ -145,7 +128,7 @@ __global__ void __launch_bounds__(256) k_tucker_core(TkArgs a, const int64_t* __
                 for (int mb = 0; mb < 4; ++mb) {
                     float f[4] = {1.0f, 1.0f, 1.0f, 1.0f};
                     if constexpr (DROP) {
-                        const Philox x = tk_draw(a.g, 1u, (uint32_t)(i * d1 + jc), rowgrp0 + 4u * mb);
+                        const Philox x = drop_draw(a.g.key, 1u, (uint32_t)(i * d1 + jc), rowgrp0 + 4u * mb);
 #pragma unroll
                         for (int q = 0; q < 4; ++q) f[q] = x.c[q] >= a.g.thr[1] ? a.g.scale[1] : 0.0f;
                     }
@@ -199,7 +182,7 @@ __global__ void __launch_bounds__(256) k_tucker_finish(TkArgs a, const float* __
         z_out[row * a.d1 + j] = z;
         ss += z * z;
     }
-    const float nz = sqrtf(tk_wave_sum(ss));
+    const float nz = sqrtf(wave_sum_xor(ss));
     const float den = fmaxf(nz, kTkEps);
     for (int j = lane; j < a.d1; j += 64) {
         float v = z_out[row * a.d1 + j] / den;   // (written by this lane above)
@@ -222,7 +205,7 @@ __global__ void __launch_bounds__(256) k_tucker_bwd_prep(TkArgs a, const float* 
         if (drop) g *= tk_row_factor(a.g, 2, j, row);
         dot += (z[row * a.d1 + j] / den) * g;
     }
-    dot = norm >= kTkEps ? tk_wave_sum(dot) : 0.0f;   // below eps the divisor is the constant eps
+    dot = norm >= kTkEps ? wave_sum_xor(dot) : 0.0f;   // below eps the divisor is the constant eps
     for (int j = lane; j < a.d1; j += 64) {
         float g = dx[row * a.d1 + j];
         if (drop) g *= tk_row_factor(a.g, 2, j, row);
@@ -244,7 +227,7 @@ __global__ void __launch_bounds__(256) k_tucker_gent(TkArgs a, const int64_t* __
         if (drop) g *= tk_row_factor(a.g, 0, i, row);
         dot += (src[i] / den) * g;
     }
-    dot = norm >= kTkEps ? tk_wave_sum(dot) : 0.0f;
+    dot = norm >= kTkEps ? wave_sum_xor(dot) : 0.0f;
     for (int i = lane; i < a.d1; i += 64) {
         float g = ga[row * a.d1 + i];
         if (drop) g *= tk_row_factor(a.g, 0, i, row);
@@ -317,7 +300,7 @@ __global__ void __launch_bounds__(256) k_tucker_gw(TkArgs a, const int64_t* __re
             float G[4];
             float f[4] = {1.0f, 1.0f, 1.0f, 1.0f};
             if constexpr (DROP) {
-                const Philox x = tk_draw(a.g, 1u, (uint32_t)(i * d1 + jc), (uint32_t)((b0 >> 2) + 4 * q + g));
+                const Philox x = drop_draw(a.g.key, 1u, (uint32_t)(i * d1 + jc), (uint32_t)((b0 >> 2) + 4 * q + g));
 #pragma unroll
                 for (int w = 0; w < 4; ++w) f[w] = x.c[w] >= a.g.thr[1] ? a.g.scale[1] : 0.0f;
             }
@@ -381,8 +364,8 @@ __global__ void __launch_bounds__(256) k_tucker_grel(TkArgs a, const int64_t* __
             for (int mb = 0; mb < 4; ++mb) {
                 float G = ai[mb] * dz[rows[mb] * d1 + jc];
                 if constexpr (DROP) {
-                    const Philox x = tk_draw(a.g, 1u, (uint32_t)(i * d1 + jc), (uint32_t)(rows[mb] >> 2));
-                    G *= tk_word(x, (int)(rows[mb] & 3)) >= a.g.thr[1] ? a.g.scale[1] : 0.0f;
+                    const Philox x = drop_draw(a.g.key, 1u, (uint32_t)(i * d1 + jc), (uint32_t)(rows[mb] >> 2));
+                    G *= drop_word(x, (int)(rows[mb] & 3)) >= a.g.thr[1] ? a.g.scale[1] : 0.0f;
                 }
                 acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(G, b, acc[mb], 0, 0, 0);
             }
@@ -399,25 +382,6 @@ __global__ void __launch_bounds__(256) k_tucker_grel(TkArgs a, const int64_t* __
         }
 }
 
-// the rank pass's glue: triples with the true entity of the head sweep in column 2, and the [4, n] layout of kge_eval_ranks
-__global__ void k_tucker_eval_ids(const int64_t* __restrict__ triples, int64_t n, int64_t* __restrict__ e, int64_t* __restrict__ r,
-                                  int64_t* __restrict__ swapped) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t h = triples[3 * i], rel = triples[3 * i + 1], t = triples[3 * i + 2];
-    e[i] = h; e[n + i] = t;
-    r[i] = rel; r[n + i] = rel;
-    swapped[3 * i] = t; swapped[3 * i + 1] = rel; swapped[3 * i + 2] = h;
-}
-__global__ void k_tucker_pack_ranks(const int32_t* __restrict__ tail, const int32_t* __restrict__ head, int64_t n, int32_t* __restrict__ ranks) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ranks[i] = head[i];
-    ranks[n + i] = tail[i];
-    ranks[2 * n + i] = head[n + i];
-    ranks[3 * n + i] = tail[n + i];
-}
-
 // ------------------------------------------------------------------------------------------------------------------ host side
 static int tk_check(const kge_tucker_desc* d, const char* who, bool grads) {
     if (!d) { set_error("%s: null descriptor", who); return -1; }
@@ -429,9 +393,7 @@ static int tk_check(const kge_tucker_desc* d, const char* who, bool grads) {
     }
     if (d->d1 > 32768) { set_error("%s: d1 = %d: a core slice has more than 2^30 elements", who, d->d1); return -1; }
     const float p[3] = {d->input_dropout, d->hidden_dropout1, d->hidden_dropout2};
-    for (int s = 0; s < 3; ++s)
-        if (!(p[s] >= 0.0f && p[s] < 1.0f)) { set_error("%s: dropout rate %d must be in [0, 1) (got %g)", who, s, (double)p[s]); return -1; }
-    if (d->offset >> 62) { set_error("%s: the Philox offset must be below 2^62", who); return -1; }
+    if (drop_check(who, p, 3, d->offset)) return -1;
     if (grads && (!d->g_ent || !d->g_rel || !d->g_W)) {
         set_error("%s: null gradient buffers (g_ent, g_rel and g_W are all required)", who);
         return -1;
@@ -448,12 +410,11 @@ static TkArgs tk_args(const kge_tucker_desc* d, int64_t n) {
     TkArgs a{};
     a.ent = d->ent; a.rel = d->rel; a.W = d->W;
     a.d1 = d->d1; a.d2 = d->d2; a.n = n;
-    a.g.k0 = (uint32_t)d->seed; a.g.k1 = (uint32_t)(d->seed >> 32);
-    a.g.hi = (uint32_t)(d->offset >> 32); a.g.lo = (uint32_t)d->offset;
+    a.g.key = drop_key(d->seed, d->offset);
     const float p[3] = {d->input_dropout, d->hidden_dropout1, d->hidden_dropout2};
     for (int s = 0; s < 3; ++s) {
-        a.g.thr[s] = (uint32_t)((double)p[s] * 4294967296.0);
-        a.g.scale[s] = 1.0f / (1.0f - p[s]);
+        a.g.thr[s] = drop_thr(p[s]);
+        a.g.scale[s] = drop_scale(p[s]);
     }
     return a;
 }
@@ -482,11 +443,6 @@ static size_t tk_bwd_bytes(const kge_tucker_desc* d, int64_t n) {
            align256((size_t)tk_splits(d->d1, tk_rel_i_per(d, n)) * (size_t)n * d->d2 * sizeof(float));
 }
 static size_t tk_saved_floats(const kge_tucker_desc* d, int64_t n) { return (size_t)n * (2 * (size_t)d->d1 + 2); }
-
-static int tk_ws_check(const char* who, const void* ws, size_t have, size_t need) {
-    if (!ws || have < need) { set_error("%s: workspace too small (%zu < %zu bytes)", who, ws ? have : (size_t)0, need); return -1; }
-    return 0;
-}
 
 static int tk_forward(const kge_tucker_desc* d, const int64_t* e, const int64_t* r, int64_t n, float* x, float* saved, void* ws,
                       hipStream_t s) {
@@ -534,11 +490,6 @@ static int tk_backward(const kge_tucker_desc* d, const int64_t* e, const int64_t
     return check_launch("k_tucker_gent / k_tucker_scatter");
 }
 
-static int tk_check_ids(const char* who, const kge_tucker_desc* d, const int64_t* e, const int64_t* r, int64_t n, hipStream_t s) {
-    if (int rc = debug_check_ids(who, "entity", e, n, 1, 0, d->tot_entity, s)) return rc;
-    return debug_check_ids(who, "relation", r, n, 1, 0, d->tot_relation, s);
-}
-
 // fused step: ids [4B int64] | x [2B, d1] | dx [2B, d1] | saved | max(forward, backward, head)
 struct TkStepPlan {
     size_t ids, x, dx, saved, rest, total;
@@ -561,23 +512,17 @@ static TkStepPlan tk_step_plan(const kge_tucker_desc* d, int64_t B, int64_t n_hr
     return p;
 }
 
-// rank: ids [2n int64 x 2] | swapped triples [3n int64] | x [2n, d1] | saved | ranks of the two sweeps [2 x 2n int32] | max(forward, head rank)
-struct TkEvalPlan {
-    size_t ids, swapped, x, saved, ranks, rest, total;
-};
-static TkEvalPlan tk_eval_plan(const kge_tucker_desc* d, int64_t n) {
-    TkEvalPlan p{};
-    p.ids = 0;
-    p.swapped = align256((size_t)4 * n * sizeof(int64_t));
-    p.x = p.swapped + align256((size_t)3 * n * sizeof(int64_t));
-    p.saved = p.x + align256((size_t)2 * n * d->d1 * sizeof(float));
-    p.ranks = p.saved + align256(tk_saved_floats(d, 2 * n) * sizeof(float));
-    p.rest = p.ranks + align256((size_t)4 * n * sizeof(int32_t));
-    size_t rest = tk_fwd_bytes(d, 2 * n);
-    const size_t hr = kge_head_1n_rank_workspace_bytes(n, d->d1, d->tot_entity, 0);
-    if (hr > rest) rest = hr;
-    p.total = p.rest + align256(rest);
-    return p;
+// the rank pass's body (kge_projection.hip): model.eval(), so no dropout; ws = saved | the forward's partial rows
+static int tk_eval_body(const void* desc, const int64_t* e, const int64_t* r, int64_t n, float* x, void* ws, size_t, hipStream_t s) {
+    kge_tucker_desc ev = *(const kge_tucker_desc*)desc;
+    ev.train = 0;
+    const size_t saved = align256(tk_saved_floats(&ev, 2 * n) * sizeof(float));
+    return tk_forward(&ev, e, r, 2 * n, x, (float*)ws, (char*)ws + saved, s);
+}
+static ProjectionEval tk_eval(const kge_tucker_desc* d, int64_t n) {
+    const int64_t rows = 2 * (n > 0 ? n : 1);
+    return ProjectionEval{d->d1, d->tot_entity, d->tot_relation, d->ent,
+                          align256(tk_saved_floats(d, rows) * sizeof(float)) + tk_fwd_bytes(d, rows), tk_eval_body};
 }
 
 }  // namespace kge
@@ -599,10 +544,10 @@ int kge_tucker_body_forward(const kge_tucker_desc* d, const int64_t* e, const in
     const char* who = "kge_tucker_body_forward";
     if (tk_check(d, who, false)) return -1;
     if (n < 0 || (n > 0 && (!e || !r || !x || !saved))) { set_error("%s: bad arguments", who); return -1; }
-    if (tk_ws_check(who, workspace, workspace_bytes, tk_fwd_bytes(d, n > 0 ? n : 1))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, tk_fwd_bytes(d, n > 0 ? n : 1))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = tk_check_ids(who, d, e, r, n, s)) return rc;
+    if (int rc = check_er_ids(who, d->tot_entity, d->tot_relation, e, r, n, s)) return rc;
     return tk_forward(d, e, r, n, x, saved, workspace, s);
 }
 
@@ -615,10 +560,10 @@ int kge_tucker_body_backward(const kge_tucker_desc* d, const int64_t* e, const i
     const char* who = "kge_tucker_body_backward";
     if (tk_check(d, who, true)) return -1;
     if (n < 0 || (n > 0 && (!e || !r || !dx || !saved))) { set_error("%s: bad arguments", who); return -1; }
-    if (tk_ws_check(who, workspace, workspace_bytes, tk_bwd_bytes(d, n > 0 ? n : 1))) return -1;
+    if (ws_check(who, workspace, workspace_bytes, tk_bwd_bytes(d, n > 0 ? n : 1))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = tk_check_ids(who, d, e, r, n, s)) return rc;
+    if (int rc = check_er_ids(who, d->tot_entity, d->tot_relation, e, r, n, s)) return rc;
     return tk_backward(d, e, r, n, dx, saved, workspace, s);
 }
 
@@ -638,7 +583,7 @@ int kge_tucker_train_bce(const kge_tucker_desc* d, const int64_t* h, const int64
         return -1;
     }
     const TkStepPlan p = tk_step_plan(d, batch > 0 ? batch : 1, n_hr, n_tr);
-    if (tk_ws_check(who, workspace, workspace_bytes, p.total)) return -1;
+    if (ws_check(who, workspace, workspace_bytes, p.total)) return -1;
     if (batch == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int64_t B = batch, n = 2 * B;
@@ -654,7 +599,7 @@ int kge_tucker_train_bce(const kge_tucker_desc* d, const int64_t* h, const int64
         set_error("%s: copying the row ids failed: %s", who, hipGetErrorString(hipGetLastError()));
         return -2;
     }
-    if (int rc = tk_check_ids(who, d, e, rr, n, s)) return rc;
+    if (int rc = check_er_ids(who, d->tot_entity, d->tot_relation, e, rr, n, s)) return rc;
     if (int rc = tk_forward(d, e, rr, n, x, saved, rest, s)) return rc;
     // pred_tails = forward(h, r) against hr_t, pred_heads = forward(t, r) against tr_h: a mean over B * E each, added (utils/trainer.py:159-172)
     if (int rc = kge_head_1n_bce(x, B, d->d1, d->ent, d->tot_entity, nullptr, hr_off, hr_ids, n_hr, label_smoothing, rest, rest_bytes, loss,
@@ -665,7 +610,7 @@ int kge_tucker_train_bce(const kge_tucker_desc* d, const int64_t* h, const int64
 }
 
 size_t kge_tucker_eval_ranks_workspace_bytes(const kge_tucker_desc* d, int64_t n) {
-    return tk_check(d, "kge_tucker_eval_ranks_workspace_bytes", false) || n < 0 ? 0 : tk_eval_plan(d, n > 0 ? n : 1).total;
+    return tk_check(d, "kge_tucker_eval_ranks_workspace_bytes", false) || n < 0 ? 0 : projection_eval_workspace_bytes(tk_eval(d, n), n);
 }
 
 int kge_tucker_eval_ranks(const kge_tucker_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
@@ -673,36 +618,8 @@ int kge_tucker_eval_ranks(const kge_tucker_desc* d, const int64_t* triples, int6
                           int32_t* ties, void* stream) {
     const char* who = "kge_tucker_eval_ranks";
     if (tk_check(d, who, false)) return -1;
-    if (n < 0 || (n > 0 && (!triples || !ranks)) || (tail_off && !tail_ids) || (head_off && !head_ids)) {
-        set_error("%s: bad arguments", who);
-        return -1;
-    }
-    const TkEvalPlan p = tk_eval_plan(d, n > 0 ? n : 1);
-    if (tk_ws_check(who, workspace, workspace_bytes, p.total)) return -1;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = debug_check_triples(who, d->tot_entity, d->tot_relation, triples, n, s)) return rc;
-    char* ws = (char*)workspace;
-    int64_t* e = (int64_t*)(ws + p.ids);
-    int64_t* rr = e + 2 * n;
-    int64_t* swapped = (int64_t*)(ws + p.swapped);
-    float *x = (float*)(ws + p.x), *saved = (float*)(ws + p.saved);
-    int32_t* tmp = (int32_t*)(ws + p.ranks);
-    void* rest = ws + p.rest;
-    const size_t rest_bytes = p.total - p.rest;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_tucker_eval_ids, dim3(blocks), dim3(256), 0, s, triples, n, e, rr, swapped);
-    if (int rc = check_launch("k_tucker_eval_ids")) return rc;
-    kge_tucker_desc ev = *d;
-    ev.train = 0;   // model.eval(): no dropout
-    if (int rc = tk_forward(&ev, e, rr, 2 * n, x, saved, rest, s)) return rc;
-    // tail sweep: forward(h, r), true entity t, filter hr_t; head sweep: forward(t, r), true entity h, filter tr_h
-    if (int rc = kge_head_1n_rank(x, n, d->d1, d->ent, d->tot_entity, nullptr, triples, tail_off, tail_ids, rest, rest_bytes, tmp,
-                                  ties ? ties + n : nullptr, nullptr, stream)) return rc;
-    if (int rc = kge_head_1n_rank(x + n * d->d1, n, d->d1, d->ent, d->tot_entity, nullptr, swapped, head_off, head_ids, rest, rest_bytes,
-                                  tmp + 2 * n, ties, nullptr, stream)) return rc;
-    hipLaunchKernelGGL(k_tucker_pack_ranks, dim3(blocks), dim3(256), 0, s, tmp, tmp + 2 * n, n, ranks);
-    return check_launch("k_tucker_pack_ranks");
+    return projection_eval_ranks(who, tk_eval(d, n), d, triples, n, tail_off, tail_ids, head_off, head_ids, workspace, workspace_bytes, ranks,
+                                 ties, stream);
 }
 
 }  // extern "C"

@@ -369,14 +369,7 @@ class Evaluator:
                     ties[:, dst[a:b]] = t
             return (out, ties) if return_ties else out
         ties = new_ties(trip.shape[0])
-        if getattr(self.model, "kernel_name", None) == "tucker" and self.K is K:
-            # the projection path: body without dropout + the head's filtered rank per side (kge_tucker_eval_ranks), same [4, n] layout
-            out = K.tucker_eval_ranks(desc, trip, t_off, t_ids, h_off, h_ids, ties=ties)
-            return (out, ties) if return_ties else out
-        if getattr(self.model, "kernel_name", None) == "proje" and self.K is K:
-            # the same path for ProjE_pointwise: f1 / f2 without dropout + the head's filtered rank per side (kge_proje_eval_ranks)
-            out = K.proje_eval_ranks(desc, trip, t_off, t_ids, h_off, h_ids, ties=ties)
-            return (out, ties) if return_ties else out
+        # (the models with their own descriptor -- ConvKB, TuckER, ProjE_pointwise -- are told apart by K.eval_ranks)
         out = self.K.eval_ranks(desc, trip, t_off, t_ids, h_off, h_ids, **kw(ties))
         return (out, ties) if return_ties else out
 

@@ -15,7 +15,6 @@ import torch
 
 from . import kernels as K
 from .common import TrainingStrategy
-from .criterion import Criterion
 
 
 def _triples_array(data):
@@ -315,8 +314,8 @@ class Generator:
         if self.training_strategy not in (TrainingStrategy.PAIRWISE_BASED, TrainingStrategy.POINTWISE_BASED,
                                           TrainingStrategy.PROJECTION_BASED):
             raise NotImplementedError("This strategy is not supported.")
-        # ProjE_pointwise (loss = Criterion.multi_class) trains on the -1 labels the reference writes for neg_rate > 0
-        self.label_negatives = getattr(model, "loss", None) is Criterion.multi_class
+        # ProjE_pointwise trains on the -1 labels the reference writes for neg_rate > 0
+        self.label_negatives = getattr(model, "label_negatives", False)
         if self.training_strategy == TrainingStrategy.PROJECTION_BASED and int(config.neg_rate) > 0 and not self.label_negatives:
             # data/generator.py:178-209 then writes -1 into the label rows of the corrupted entities: BCE targets outside [0, 1]
             raise NotImplementedError("projection models: neg_rate > 0 is not supported (the reference then writes -1 into the BCE "

@@ -1420,6 +1420,75 @@ def head_1n_bce(x, ent, bias, label_off, label_ids, label_smoothing, loss_buf, g
     return dx
 
 
+# ---------------------------------------------------------------- shared by the models with their own descriptor (ConvKB, TuckER, ProjE)
+def _check_embeddings(model, *specs):
+    """specs: (name, tensor, rows indexed by id, columns)."""
+    for name, t, rows, cols in specs:
+        if t.dim() != 2 or t.shape[1] != cols or t.shape[0] < rows:
+            raise L.KgeHipError("%s: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
+                                % (model, name, rows, cols, tuple(t.shape)))
+
+
+def _bind_grads(d, fields, names, grads, tables):
+    """d.<field> = the gradient tensor's pointer, each gradient shaped like its table."""
+    for field, name, g, t in zip(fields, names, grads, tables):
+        if g.shape != t.shape:
+            raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
+        setattr(d, field, _dev(g, torch.float32, name).value)
+
+
+def _set_rng(d, train, seed, offset):
+    d.train, d.seed, d.offset = int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+
+
+def _desc_ws(desc, query, *args):
+    """(pointer, bytes) of the descriptor's workspace, grown to what `query` asks for; kept with the descriptor, so the steps of a
+    Trainer (captured ones included) allocate nothing once the largest request has been seen."""
+    need = int(getattr(L.load(), query)(ctypes.byref(desc), *args))
+    if need == 0:
+        msg = L.load().kge_last_error()
+        raise L.KgeHipError("%s refused the descriptor: %s" % (query, msg.decode() if msg else "?"))
+    if desc._ws is None or desc._ws.numel() < need:
+        desc._ws = torch.empty(need + need // 8, dtype=torch.uint8, device=desc._keepalive[0][0].device)
+    return ctypes.c_void_p(desc._ws.data_ptr()), desc._ws.numel()
+
+
+def _filter_csr_args(tail_off, tail_ids, head_off, head_ids):
+    """The four filter-list pointers of a rank entry point; None = that side unfiltered.  An empty id list has no storage: the
+    offsets pointer stands in for it (never read: every list is empty)."""
+    args = []
+    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
+        if off is None:
+            args += [None, None]
+        else:
+            po, pi = _dev(off, torch.int64, "csr offsets"), _dev(ids, torch.int32, "csr ids")
+            args += [po, pi if ids.numel() else po]
+    return args
+
+
+def _label_csr_args(who, h, r, t, hr_off, hr_ids, tr_off, tr_ids):
+    """(B, n_hr, n_tr, the arguments h .. n_tr of a fused 1-N step).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1],
+    ids int32)."""
+    B = h.numel()
+    if r.numel() != B or t.numel() != B or hr_off.numel() != B + 1 or tr_off.numel() != B + 1:
+        raise ValueError("%s: h, r, t must have equal lengths B and the label offsets B + 1 entries" % who)
+    n_hr, n_tr = int(hr_ids.numel()), int(tr_ids.numel())
+    return B, n_hr, n_tr, [_ids(h, "h"), _ids(r, "r"), _ids(t, "t"), B,
+                           _dev(hr_off, torch.int64, "hr_t offsets"), _dev(hr_ids, torch.int32, "hr_t ids") if n_hr else None, n_hr,
+                           _dev(tr_off, torch.int64, "tr_h offsets"), _dev(tr_ids, torch.int32, "tr_h ids") if n_tr else None, n_tr]
+
+
+def _projection_eval_ranks(symbol, desc, triples, tail_off, tail_ids, head_off, head_ids, ties):
+    n = triples.shape[0]
+    ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
+    wp, wb = _desc_ws(desc, symbol + "_workspace_bytes", n)
+    L.check(getattr(L.load(), symbol)(ctypes.byref(desc), _ids(triples, "triples"), n,
+                                      *_filter_csr_args(tail_off, tail_ids, head_off, head_ids), wp, wb,
+                                      _dev(ranks, torch.int32, "ranks"),
+                                      _dev(ties, torch.int32, "ties") if ties is not None else None, _stream()), symbol)
+    return ranks
+
+
 # ---------------------------------------------------------------- ConvKB (csrc/kge_convkb.hip): its own descriptor and entry points
 def _convkb_no_reg(lmbda, reg_type):
     if float(lmbda) != 0.0 and int(reg_type) != L.REG_NONE:
@@ -1436,10 +1505,7 @@ def convkb_desc(tables, grads=None, *, tot_entity, tot_relation, dim, num_filter
     if len(tables) != 4:
         raise L.KgeHipError("convkb: 4 tensors expected (ent, rel, fc1.weight, fc1.bias), got %d" % len(tables))
     ent, rel, fc_w, fc_b = tables
-    for name, t, rows in (("ent_embeddings", ent, E), ("rel_embeddings", rel, R)):
-        if t.dim() != 2 or t.shape[1] != k or t.shape[0] < rows:
-            raise L.KgeHipError("convkb: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
-                                % (name, rows, k, tuple(t.shape)))
+    _check_embeddings("convkb", ("ent_embeddings", ent, E, k), ("rel_embeddings", rel, R, k))
     W = sum(k - s + 1 for s in sizes)
     for name, t, numel in (("fc1.weight", fc_w, F * W), ("fc1.bias", fc_b, 1), ("conv_w", conv_w, F * 3 * sum(sizes)),
                            ("conv_b", conv_b, F * len(sizes))):
@@ -1453,22 +1519,10 @@ def convkb_desc(tables, grads=None, *, tot_entity, tot_relation, dim, num_filter
     d.fc_w, d.fc_b = _dev(fc_w, torch.float32, "fc1.weight").value, _dev(fc_b, torch.float32, "fc1.bias").value
     d.conv_w, d.conv_b = _dev(conv_w, torch.float32, "conv_w").value, _dev(conv_b, torch.float32, "conv_b").value
     if grads is not None:
-        for g, t in zip(grads, tables):
-            if g.shape != t.shape:
-                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
-        d.g_ent, d.g_rel, d.g_fc_w, d.g_fc_b = (_dev(g, torch.float32, "grad %d" % i).value for i, g in enumerate(grads))
+        _bind_grads(d, ("g_ent", "g_rel", "g_fc_w", "g_fc_b"), ["grad %d" % i for i in range(4)], grads, tables)
     d._keepalive = (tables, grads, conv_w, conv_b)
     d._ws = None
     return d
-
-
-def _convkb_ws(desc, query, *args):
-    """(pointer, bytes) of the descriptor's workspace, grown to what `query` asks for; kept with the descriptor, so the captured steps
-    of a Trainer allocate nothing."""
-    need = int(getattr(L.load(), query)(ctypes.byref(desc), *args))
-    if desc._ws is None or desc._ws.numel() < need:
-        desc._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=desc._keepalive[0][0].device)
-    return ctypes.c_void_p(desc._ws.data_ptr()), desc._ws.numel()
 
 
 def convkb_collapse(desc):
@@ -1483,7 +1537,7 @@ def convkb_score_forward(desc, h, r, t):
     if r.numel() != n or t.numel() != n:
         raise ValueError("h, r, t must have equal lengths")
     out = torch.empty(n, dtype=torch.float32, device=h.device)
-    wp, wb = _convkb_ws(desc, "kge_convkb_score_forward_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_convkb_score_forward_workspace_bytes", n)
     L.check(L.load().kge_convkb_score_forward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
                                               _dev(out, torch.float32, "scores"), wp, wb, _stream()), "kge_convkb_score_forward")
     return out
@@ -1491,14 +1545,14 @@ def convkb_score_forward(desc, h, r, t):
 
 def convkb_score_backward(desc, h, r, t, dscore):
     n = h.numel()
-    wp, wb = _convkb_ws(desc, "kge_convkb_score_backward_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_convkb_score_backward_workspace_bytes", n)
     L.check(L.load().kge_convkb_score_backward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
                                                _dev(dscore, torch.float32, "dscore"), wp, wb, _stream()), "kge_convkb_score_backward")
 
 
 def convkb_train_logistic(desc, h, r, t, y, loss_buf, bundle=1):
     n = h.numel()
-    wp, wb = _convkb_ws(desc, "kge_convkb_train_logistic_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_convkb_train_logistic_workspace_bytes", n)
     L.check(L.load().kge_convkb_train_logistic(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), _ids(y, "y"), n,
                                                int(bundle), wp, wb, _dev(loss_buf, torch.float32, "loss"), _stream()),
             "kge_convkb_train_logistic")
@@ -1510,7 +1564,7 @@ def convkb_train_logistic_sampled(desc, triples, perm, start, n_pos, neg_rate, b
     bp = _dev(bern_prob, torch.float32, "bern_prob") if bern_prob is not None else None
     sp = ctypes.c_void_p(slots.data_ptr()) if slots is not None else None
     pc = _dev(cursor, torch.int64, "cursor") if cursor is not None else None
-    wp, wb = _convkb_ws(desc, "kge_convkb_train_logistic_sampled_workspace_bytes", int(n_pos), int(neg_rate))
+    wp, wb = _desc_ws(desc, "kge_convkb_train_logistic_sampled_workspace_bytes", int(n_pos), int(neg_rate))
     L.check(L.load().kge_convkb_train_logistic_sampled(ctypes.byref(desc), _ids(triples, "triples"), _ids(perm, "perm"), int(start),
                                                        int(n_pos), int(neg_rate), bp, sp, slots.numel() if slots is not None else 0,
                                                        int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), pc, wp, wb,
@@ -1522,14 +1576,9 @@ def convkb_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids):
     """int32 [4, n] as eval_ranks, in one kge_convkb_eval_ranks call."""
     n = triples.shape[0]
     ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
-    args = []
-    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
-        if off is None:
-            args += [None, None]
-        else:
-            args += [_dev(off, torch.int64, "csr offsets"), _dev(ids, torch.int32, "csr ids")]
-    wp, wb = _convkb_ws(desc, "kge_convkb_eval_ranks_workspace_bytes", n)
-    L.check(L.load().kge_convkb_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
+    wp, wb = _desc_ws(desc, "kge_convkb_eval_ranks_workspace_bytes", n)
+    L.check(L.load().kge_convkb_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n,
+                                           *_filter_csr_args(tail_off, tail_ids, head_off, head_ids), wp, wb,
                                            _dev(ranks, torch.int32, "ranks"), _stream()), "kge_convkb_eval_ranks")
     return ranks
 
@@ -1538,7 +1587,7 @@ def convkb_sweep_scores_side(desc, triples, side):
     """float32 [n, E]: side 0 = preds of (h_i, r_i, e) for all e, side 1 = preds of (e, r_i, t_i)."""
     n = triples.shape[0]
     out = torch.empty((n, desc.tot_entity), dtype=torch.float32, device=triples.device)
-    wp, wb = _convkb_ws(desc, "kge_convkb_sweep_scores_side_workspace_bytes", n)
+    wp, wb = _desc_ws(desc, "kge_convkb_sweep_scores_side_workspace_bytes", n)
     L.check(L.load().kge_convkb_sweep_scores_side(ctypes.byref(desc), _ids(triples, "triples"), n, int(side), wp, wb,
                                                   _dev(out, torch.float32, "scores"), _stream()), "kge_convkb_sweep_scores_side")
     return out
@@ -1553,37 +1602,19 @@ def tucker_desc(tables, grads=None, *, tot_entity, tot_relation, d1, d2, dropout
     if len(tables) != 3:
         raise L.KgeHipError("tucker: 3 tensors expected (ent, rel, W), got %d" % len(tables))
     ent, rel, W = tables
-    for name, t, rows, cols in (("ent_embeddings", ent, E, d1), ("rel_embeddings", rel, R, d2)):
-        if t.dim() != 2 or t.shape[1] != cols or t.shape[0] < rows:
-            raise L.KgeHipError("tucker: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
-                                % (name, rows, cols, tuple(t.shape)))
+    _check_embeddings("tucker", ("ent_embeddings", ent, E, d1), ("rel_embeddings", rel, R, d2))
     if W.numel() != d2 * d1 * d1:
         raise L.KgeHipError("tucker: W must hold d2 * d1 * d1 = %d floats (got %d)" % (d2 * d1 * d1, W.numel()))
     d = L.TuckerDesc()
     d.tot_entity, d.tot_relation, d.d1, d.d2 = E, R, d1, d2
     d.input_dropout, d.hidden_dropout1, d.hidden_dropout2 = (float(p) for p in dropouts)
-    d.train, d.seed, d.offset = int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    _set_rng(d, train, seed, offset)
     d.ent, d.rel, d.W = (_dev(t, torch.float32, n).value for t, n in zip(tables, ("ent_embeddings", "rel_embeddings", "W")))
     if grads is not None:
-        for g, t in zip(grads, tables):
-            if g.shape != t.shape:
-                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
-        d.g_ent, d.g_rel, d.g_W = (_dev(g, torch.float32, "grad %d" % i).value for i, g in enumerate(grads))
+        _bind_grads(d, ("g_ent", "g_rel", "g_W"), ["grad %d" % i for i in range(3)], grads, tables)
     d._keepalive = (tables, grads)
     d._ws = None
     return d
-
-
-def _desc_ws(desc, query, *args):
-    """(pointer, bytes) of the descriptor's workspace, grown to what `query` asks for; kept with the descriptor, so the steps of a
-    Trainer allocate nothing once the largest label list has been seen."""
-    need = int(getattr(L.load(), query)(ctypes.byref(desc), *args))
-    if need == 0:
-        msg = L.load().kge_last_error()
-        raise L.KgeHipError("%s refused the descriptor: %s" % (query, msg.decode() if msg else "?"))
-    if desc._ws is None or desc._ws.numel() < need:
-        desc._ws = torch.empty(need + need // 8, dtype=torch.uint8, device=desc._keepalive[0][0].device)
-    return ctypes.c_void_p(desc._ws.data_ptr()), desc._ws.numel()
 
 
 def tucker_saved_floats(desc, n):
@@ -1614,35 +1645,15 @@ def tucker_body_backward(desc, e, r, dx, saved):
 def tucker_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
     """One train_step_projection: adds to loss_buf and to the descriptor's gradients.  hr_* / tr_*: the label CSRs of the batch
     (off int64 [B + 1], ids int32); label_smoothing None = off."""
-    B = h.numel()
-    if r.numel() != B or t.numel() != B or hr_off.numel() != B + 1 or tr_off.numel() != B + 1:
-        raise ValueError("tucker_train_bce: h, r, t must have equal lengths B and the label offsets B + 1 entries")
-    n_hr, n_tr = int(hr_ids.numel()), int(tr_ids.numel())
+    B, n_hr, n_tr, args = _label_csr_args("tucker_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
     wp, wb = _desc_ws(desc, "kge_tucker_train_bce_workspace_bytes", B, n_hr, n_tr)
-    L.check(L.load().kge_tucker_train_bce(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), B,
-                                          _dev(hr_off, torch.int64, "hr_t offsets"), _dev(hr_ids, torch.int32, "hr_t ids") if n_hr else None,
-                                          n_hr, _dev(tr_off, torch.int64, "tr_h offsets"),
-                                          _dev(tr_ids, torch.int32, "tr_h ids") if n_tr else None, n_tr,
-                                          -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+    L.check(L.load().kge_tucker_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
                                           _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_tucker_train_bce")
 
 
 def tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
     """int32 [4, n] as eval_ranks, in one kge_tucker_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
-    n = triples.shape[0]
-    ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
-    args = []
-    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
-        if off is None:
-            args += [None, None]
-        else:
-            args += [_dev(off, torch.int64, "csr offsets"), ctypes.c_void_p(ids.data_ptr()) if ids.numel() else ctypes.c_void_p(off.data_ptr())]
-    wp, wb = _desc_ws(desc, "kge_tucker_eval_ranks_workspace_bytes", n)
-    L.check(L.load().kge_tucker_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
-                                           _dev(ranks, torch.int32, "ranks"),
-                                           _dev(ties, torch.int32, "ties") if ties is not None else None, _stream()),
-            "kge_tucker_eval_ranks")
-    return ranks
+    return _projection_eval_ranks("kge_tucker_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)
 
 
 # ---------------------------------------------------------------- ProjE_pointwise (csrc/kge_proje.hip): its own descriptor and entry points
@@ -1653,25 +1664,19 @@ def proje_desc(tables, grads=None, *, tot_entity, tot_relation, dim, hidden_drop
     E, R, k = int(tot_entity), int(tot_relation), int(dim)
     if len(tables) != 8:
         raise L.KgeHipError("proje: 8 tensors expected (ent, rel, bc1, De1, Dr1, bc2, De2, Dr2), got %d" % len(tables))
-    for name, t, rows in (("ent_embeddings", tables[0], E), ("rel_embeddings", tables[1], R)):
-        if t.dim() != 2 or t.shape[1] != k or t.shape[0] < rows:
-            raise L.KgeHipError("proje: %s must be [>= %d, %d] (got %s): an nn.Embedding lookup would raise IndexError"
-                                % (name, rows, k, tuple(t.shape)))
+    _check_embeddings("proje", ("ent_embeddings", tables[0], E, k), ("rel_embeddings", tables[1], R, k))
     for name, t in zip(L.PROJE_TABLES[2:], tables[2:]):
         if t.numel() != k:
             raise L.KgeHipError("proje: %s must hold %d floats (got %s)" % (name, k, tuple(t.shape)))
     d = L.ProjeDesc()
     d.tot_entity, d.tot_relation, d.dim, d.hidden_dropout = E, R, k, float(hidden_dropout)
-    d.train, d.seed, d.offset = int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    _set_rng(d, train, seed, offset)
     for name, t in zip(L.PROJE_TABLES, tables):
         setattr(d, name, _dev(t, torch.float32, name).value)
     if grads is not None:
         if len(grads) != 8:
             raise L.KgeHipError("proje: 8 gradient tensors expected, got %d" % len(grads))
-        for name, g, t in zip(L.PROJE_TABLES, grads, tables):
-            if g.shape != t.shape:
-                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
-            setattr(d, "g_" + name, _dev(g, torch.float32, "grad of " + name).value)
+        _bind_grads(d, ["g_" + name for name in L.PROJE_TABLES], ["grad of " + name for name in L.PROJE_TABLES], grads, tables)
     d._keepalive = (tables, grads)
     d._ws = None
     return d
@@ -1725,32 +1730,13 @@ def proje_label_loss(x, ent, pos_off, pos_ids, neg, loss_buf, g_ent):
 def proje_train(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, neg, lmbda, loss_buf):
     """One train_step_projection of ProjE_pointwise: adds to loss_buf and to the descriptor's gradients.  hr_* / tr_*: the label
     CSRs of the batch (off int64 [B + 1], ids int32); neg: the batch's shared negative ids (int32) or None."""
-    B = h.numel()
-    if r.numel() != B or t.numel() != B or hr_off.numel() != B + 1 or tr_off.numel() != B + 1:
-        raise ValueError("proje_train: h, r, t must have equal lengths B and the label offsets B + 1 entries")
-    n_hr, n_tr, n_neg = int(hr_ids.numel()), int(tr_ids.numel()), 0 if neg is None else int(neg.numel())
+    B, n_hr, n_tr, args = _label_csr_args("proje_train", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
+    n_neg = 0 if neg is None else int(neg.numel())
     wp, wb = _desc_ws(desc, "kge_proje_train_workspace_bytes", B, n_hr, n_tr, n_neg)
-    L.check(L.load().kge_proje_train(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), B,
-                                     _dev(hr_off, torch.int64, "hr_t offsets"), _dev(hr_ids, torch.int32, "hr_t ids") if n_hr else None,
-                                     n_hr, _dev(tr_off, torch.int64, "tr_h offsets"),
-                                     _dev(tr_ids, torch.int32, "tr_h ids") if n_tr else None, n_tr,
-                                     _dev(neg, torch.int32, "negative ids") if n_neg else None, n_neg, float(lmbda), wp, wb,
-                                     _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_proje_train")
+    L.check(L.load().kge_proje_train(ctypes.byref(desc), *args, _dev(neg, torch.int32, "negative ids") if n_neg else None, n_neg,
+                                     float(lmbda), wp, wb, _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_proje_train")
 
 
 def proje_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
     """int32 [4, n] as eval_ranks, in one kge_proje_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
-    n = triples.shape[0]
-    ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
-    args = []
-    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
-        if off is None:
-            args += [None, None]
-        else:
-            args += [_dev(off, torch.int64, "csr offsets"), ctypes.c_void_p(ids.data_ptr()) if ids.numel() else ctypes.c_void_p(off.data_ptr())]
-    wp, wb = _desc_ws(desc, "kge_proje_eval_ranks_workspace_bytes", n)
-    L.check(L.load().kge_proje_eval_ranks(ctypes.byref(desc), _ids(triples, "triples"), n, *args, wp, wb,
-                                          _dev(ranks, torch.int32, "ranks"),
-                                          _dev(ties, torch.int32, "ties") if ties is not None else None, _stream()),
-            "kge_proje_eval_ranks")
-    return ranks
+    return _projection_eval_ranks("kge_proje_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)

@@ -110,6 +110,13 @@ class PointwiseModel(nn.Module, Model):
 class ProjectionModel(nn.Module, Model):
     """The base of the 1-N models (models/KGMeta.py: ProjectionModel): forward(e, r, direction) returns [B, E] predictions."""
     __setstate__ = Model._restore
+    dropout_in_eval = False   # True: the model draws its dropout masks whatever the module's mode
+    label_negatives = False   # True: the loss reads sampled negatives as -1 labels (the generator draws them); else neg_rate > 0 is refused
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        """One training step in ONE library call: adds to loss_buf and to the descriptor's gradients.  hr_t_csr / tr_h_csr: the
+        label CSRs of the batch; neg: the batch's negative label ids where label_negatives, else None."""
+        raise NotImplementedError("%s has no fused projection step" % type(self).__name__)
 
     def __init__(self, model_name):
         super().__init__()

@@ -45,6 +45,9 @@ class TuckER(ProjectionModel):
                              train=self.training if train is None else train, seed=self.dropout_seed if seed is None else seed,
                              offset=self.dropout_offset if offset is None else offset)
 
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        K.tucker_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
+
     def forward(self, e1, r, direction="head"):
         assert direction in ("head", "tail"), "Unknown forward direction"
         offset = -1   # eval(): no dropout
@@ -71,6 +74,8 @@ class ProjE_pointwise(ProjectionModel):
     dropout_offset) (include/kge_hip.h spells the counters out) and advances dropout_offset by one.  The ranking calls draw nothing.
     The Trainer does not go through forward(): its fused step (kge_proje_train) reads the labelled columns only."""
     kernel_name = "proje"
+    dropout_in_eval = True   # the reference's torch.dropout(..., train=True)
+    label_negatives = True   # the -1 labels the reference writes for neg_rate > 0 are the model (loss = Criterion.multi_class)
 
     def __init__(self, **kwargs):
         super().__init__(self.__class__.__name__.lower())
@@ -104,6 +109,9 @@ class ProjE_pointwise(ProjectionModel):
                             tot_relation=self.tot_relation, dim=int(self.hidden_size), hidden_dropout=float(self.hidden_dropout),
                             train=True if train is None else train, seed=self.dropout_seed if seed is None else seed,
                             offset=self.dropout_offset if offset is None else offset)
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        K.proje_train(desc, h, r, t, *hr_t_csr, *tr_h_csr, neg, self.lmbda, loss_buf)
 
     def get_reg(self, h, r, t):
         return self.lmbda * (torch.sum(torch.abs(self.De1.weight) + torch.abs(self.Dr1.weight)) +

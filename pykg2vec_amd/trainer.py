@@ -107,7 +107,7 @@ class Trainer:
         for switch, what in (("pw_pull", "the owner-computes step (KGE_PW_PULL=1)"), ("staged", "the staged step (KGE_STAGED=1)")):
             if self.switches.get(switch):
                 no(what)
-        if int(getattr(self.config, "neg_rate", 0) or 0) > 0 and getattr(self.model, "kernel_name", None) != "proje":
+        if int(getattr(self.config, "neg_rate", 0) or 0) > 0 and not self.model.label_negatives:
             no("neg_rate > 0 (the reference then writes -1 into the BCE targets)")   # (for ProjE_pointwise the -1 labels are the model)
         if self.use_graph:
             no("hipGraph capture of the step (the label lists change length from batch to batch)")
@@ -270,14 +270,10 @@ class Trainer:
         """The fused projection step into the gradient / loss buffers.  The dropout masks of step s are the Philox masks of
         (config.seed, s): a run is reproducible from the seed.  neg: ProjE_pointwise's negative label ids of the batch, or None."""
         d = self._desc
-        d.train, d.seed, d.offset = int(self.model.training), int(getattr(self.config, "seed", 0) or 0) & (2 ** 64 - 1), self._projection_step
+        d.train = int(self.model.training or self.model.dropout_in_eval)
+        d.seed, d.offset = int(getattr(self.config, "seed", 0) or 0) & (2 ** 64 - 1), self._projection_step
         self._projection_step += 1
-        if self.model.kernel_name == "proje":
-            d.train = 1   # the reference's torch.dropout(..., train=True): drawn whatever the module's mode
-            self.K.proje_train(d, h, r, t, hr_t_csr[0], hr_t_csr[1], tr_h_csr[0], tr_h_csr[1], neg, self.model.lmbda, self.loss_buf)
-            return
-        ls = getattr(self.config, "label_smoothing", None) if hasattr(self.config, "label_smoothing") else None
-        self.K.tucker_train_bce(d, h, r, t, hr_t_csr[0], hr_t_csr[1], tr_h_csr[0], tr_h_csr[1], ls, self.loss_buf)
+        self.model.fused_projection_step(self.K, d, h, r, t, hr_t_csr, tr_h_csr, neg, self.config, self.loss_buf)
 
     def _accumulate_pointwise(self, h, r, t, y):
         # rows arrive as bundles [positive, its neg_rate negatives] (generator / data/generator.py:125-156)

@@ -122,6 +122,26 @@ def test_fixture_parity(hip, name):
     assert int(ties.sum()) == 0
 
 
+@pytest.mark.parametrize("name", NAMES)
+def test_rank_pass_with_one_side_unfiltered_and_with_one_triple(hip, name):
+    """The shared rank pass (csrc/kge_projection.hip) with an absent filter on either side and with n = 1: exact against the ranks
+    the reference recorded."""
+    from pykg2vec_amd import kernels as K
+    z = fixture(name)
+    desc = model_for(tables(z)).make_desc()
+    known = hip.dev(np.concatenate([z["train"], z["valid"], z["test"]]))
+    trip = hip.dev(z["test"])
+    t_off, t_ids, h_off, h_ids = K.filter_csr_build(known, trip, int(z["E"]), int(z["R"]))
+    want = z["ranks"]      # rows: head, tail, filtered head, filtered tail
+    got = K.eval_ranks(desc, trip, None, None, h_off, h_ids).cpu().numpy()
+    assert np.array_equal(got[0:2], want[0:2]) and np.array_equal(got[3], got[1]) and np.array_equal(got[2], want[2]), (got, want)
+    got = K.eval_ranks(desc, trip, t_off, t_ids, None, None).cpu().numpy()
+    assert np.array_equal(got[0:2], want[0:2]) and np.array_equal(got[2], got[0]) and np.array_equal(got[3], want[3]), (got, want)
+    one = trip[:1].contiguous()
+    got = K.eval_ranks(desc, one, *K.filter_csr_build(known, one, int(z["E"]), int(z["R"]))).cpu().numpy()
+    assert got.shape == (4, 1) and np.array_equal(got[:, 0], want[:, 0]), (got, want[:, 0])
+
+
 def test_evaluator_ranks_equal_the_restatement(hip):
     from pykg2vec_amd.evaluator import Evaluator
     z = fixture("proje_neg")

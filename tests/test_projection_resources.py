@@ -1,20 +1,16 @@
-"""CPU-only check of the resources of every ProjE kernel (csrc/kge_proje.hip), read from the AMDGPU metadata of the built library with
-the helpers of test_pull_occupancy.py: no scratch, no spills, and the VGPR and LDS figures of the table in DESIGN.md section 16.  The rank pass's two glue kernels are
-shared with TuckER: tests/test_projection_resources.py."""
+"""CPU-only check of the resources of the two glue kernels of the shared 1-N rank pass (csrc/kge_projection.hip), read from the AMDGPU
+metadata of the built library with the helpers of test_pull_occupancy.py: no scratch, no spills, and the VGPR and LDS figures of the
+tables in DESIGN.md sections 15 and 16."""
 import pytest
 
 from test_pull_occupancy import metadata  # noqa: F401  (module fixture: {kernel name: metadata} of the gfx950 code objects)
 
-# prefix -> (VGPRs, static LDS bytes): DESIGN.md section 16
-KERNELS = {
-    "_ZN3kge12k_proje_bodyE": (28, 0), "_ZN3kge16k_proje_body_bwdE": (34, 0), "_ZN3kge12k_proje_rowsE": (28, 12288),
-    "_ZN3kge14k_proje_logitsE": (16, 0), "_ZN3kge10k_proje_dxE": (18, 0), "_ZN3kge12k_proje_gnegE": (14, 0),
-    "_ZN3kge12k_proje_gposE": (16, 0), "_ZN3kge11k_proje_regE": (35, 2048), "_ZN3kge14k_proje_finishE": (12, 8192),
-}
+# prefix -> (VGPRs, static LDS bytes)
+KERNELS = {"_ZN3kge21k_projection_eval_idsE": (15, 0), "_ZN3kge23k_projection_pack_ranksE": (12, 0)}
 
 
 @pytest.mark.parametrize("prefix", sorted(KERNELS))
-def test_proje_kernel_resources(metadata, prefix):   # noqa: F811
+def test_projection_kernel_resources(metadata, prefix):   # noqa: F811
     found = [k for k in metadata if k.startswith(prefix)]
     assert len(found) == 1, (prefix, found)
     md = metadata[found[0]]
@@ -27,6 +23,6 @@ def test_proje_kernel_resources(metadata, prefix):   # noqa: F811
     assert int(md["group_segment_fixed_size"]) == lds, (prefix, md["group_segment_fixed_size"])
 
 
-def test_every_proje_kernel_is_checked(metadata):   # noqa: F811
-    kernels = [k for k in metadata if "k_proje_" in k]
+def test_every_projection_kernel_is_checked(metadata):   # noqa: F811
+    kernels = [k for k in metadata if "k_projection_" in k]
     assert len(kernels) == len(KERNELS), kernels

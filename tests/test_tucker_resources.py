@@ -1,6 +1,7 @@
 """CPU-only check of the resources of every TuckER kernel (csrc/kge_tucker.hip), read from the AMDGPU metadata of the built library
 with the helpers of test_pull_occupancy.py: no scratch, no vector-register spills, and LDS within the figures DESIGN.md section 15
-records (the matrix-core kernels take their rel tile as dynamic LDS, which the metadata does not count)."""
+records (the matrix-core kernels take their rel tile as dynamic LDS, which the metadata does not count).  The rank pass's two glue
+kernels are shared with ProjE_pointwise: tests/test_projection_resources.py."""
 import pytest
 
 from test_pull_occupancy import metadata  # noqa: F401  (module fixture: {kernel name: metadata} of the gfx950 code objects)
@@ -8,7 +9,7 @@ from test_pull_occupancy import metadata  # noqa: F401  (module fixture: {kernel
 # prefix -> (most VGPRs, most static LDS bytes)
 KERNELS = {
     "_ZN3kge13k_tucker_prep": (64, 0), "_ZN3kge15k_tucker_finish": (64, 0), "_ZN3kge17k_tucker_bwd_prep": (64, 0),
-    "_ZN3kge13k_tucker_gent": (64, 0), "_ZN3kge16k_tucker_scatter": (64, 0), "_ZN3kge17k_tucker_eval_ids": (64, 0), "_ZN3kge19k_tucker_pack_ranks": (64, 0),
+    "_ZN3kge13k_tucker_gent": (64, 0), "_ZN3kge16k_tucker_scatter": (64, 0),
     "_ZN3kge13k_tucker_coreILi0ELb0E": (128, 0), "_ZN3kge13k_tucker_coreILi0ELb1E": (128, 0),
     "_ZN3kge13k_tucker_coreILi1ELb0E": (128, 0), "_ZN3kge13k_tucker_coreILi1ELb1E": (128, 0),
     "_ZN3kge11k_tucker_gwILb0E": (512, 33792), "_ZN3kge11k_tucker_gwILb1E": (512, 33792),
