@@ -738,7 +738,7 @@ int kge_optimizer_step_staged(int32_t optimizer, const kge_staged_step* st, floa
 
 /* ---- 1-N scoring head of the projection models (ConvE / TuckER / InteractE / HypER / AcrE:
  * projection.py:100-102, 335-336, 444-447, 606-609, 734-737):  preds[B,E] = sigmoid(x[B,dim] @ ent[E,dim]^T + bias[E]).
- * bias may be NULL (TuckER).  fp32 on the matrix cores. */
+ * bias may be NULL (TuckER); ConvE passes its b.  fp32 on the matrix cores. */
 int kge_head_1n_forward(const float* x, int64_t batch, int32_t dim, const float* ent, int64_t tot_entity,
                         const float* bias, float* preds, void* stream);
 /* The same forward with the operands rounded to bfloat16 (round to nearest even) on their way into LDS and the products
@@ -965,6 +965,74 @@ int kge_proje_train(const kge_proje_desc* d, const int64_t* h, const int64_t* r,
  * 0 and on (t, r) with side 1 (predict_tail_rank / predict_head_rank), then kge_head_1n_rank per side with no bias. */
 size_t kge_proje_eval_ranks_workspace_bytes(const kge_proje_desc* d, int64_t n);
 int kge_proje_eval_ranks(const kge_proje_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                         const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                         int32_t* ties, void* stream);
+
+/* ---- ConvE (models/projection.py:12-125): the body in front of the 1-N head (csrc/kge_conve.hip).  For a row with
+ * entity e and relation r on side s (0 = "tail" direction; 1 = "head": the relation row is r + tot_relation of the [2R, k] table),
+ * k = hidden_size, h1 = hidden_size_1, h2 = k / h1, F = 32 (2 h2 - 2) (h1 - 2):
+ *     img = [ent[e] viewed h2 x h1 ; rel[r'] viewed h2 x h1],   y0 = bn0(img) * m0,   c = conv3x3(y0) + conv_b   (32 channels),
+ *     A = relu(bn1(c)) * m1,   u = A fc_w^T + fc_b,   x = relu(bn2(u * m2))   (training form);   x = relu(u)   (eval form: NO bn2).
+ * Batch norm as torch.nn.BatchNorm: the training form (train = 1) normalises with the mean and the biased variance of the call's rows
+ * and then updates running = (1 - momentum) running + momentum (mean, unbiased variance); the eval form (train = 0) normalises bn0 and
+ * bn1 with the running buffers, skips bn2 and draws nothing.  num_batches_tracked is the caller's.  The model has no kge_model id: it
+ * has its own descriptor and entry points.  Masks are never stored; every kernel recomputes them from Philox4x32-10:  key = (low,
+ * high word of seed);  counter = (elem, row >> 2, site | (offset >> 32) << 2, offset & 0xffffffff), word = row & 3;
+ *     site 0 (input_dropout):       elem = pixel in [0, 2k) of the stacked image, row-major, the entity half first
+ *     site 1 (feature_map_dropout): elem = channel in [0, 32): one draw per row and channel (Dropout2d)
+ *     site 2 (hidden_dropout):      elem = j in [0, k)
+ *     row = row0 + position in the call's row list.  The fused step numbers the h rows 0 .. B-1 and the t rows B .. 2B-1.
+ * An element is kept iff its word >= floor(p * 2^32) and is then scaled by 1 / (1 - p) in fp32.  train = 0 or p = 0: nothing is drawn.
+ * Gradients are accumulated into g_*; all 13 are sums in a fixed order (no atomics in the body: with the head's ordered split-K sums
+ * the 13 gradients and the six running buffers of a step are bit-identical run to run.  The loss is the head's: it is bit-identical
+ * too while each of the head's workgroups has a striped loss accumulator to itself, and can differ in its last bits from about
+ * batch = 150 on, where several workgroups add to one accumulator with float atomics).  Every entry point takes a caller-owned workspace (its own
+ * *_workspace_bytes; 0 = the descriptor is refused).  Refused before any launch, with the entry point's name in kge_last_error(): null
+ * tables or running buffers, non-positive sizes, hidden_size % hidden_size_1 != 0 (the reference floors silently and then fails in
+ * view), an image smaller than the 3 x 3 filter (hidden_size_1 < 3 or 2 h2 < 3), hidden_size > KGE_CONVE_MAX_HIDDEN (the image and
+ * four channels of the conv gradient are held in 48 KB of LDS), a momentum outside (0, 1] (the cumulative average is not built), a
+ * negative eps, n = 1 with train = 1 (torch raises too), a dropout rate outside [0, 1), an offset of 2^62 or more, a workspace that
+ * is too small; the backward and the fused step also refuse train = 0. */
+#define KGE_CONVE_MAX_HIDDEN 1024
+typedef struct kge_conve_desc {
+    int64_t tot_entity, tot_relation;
+    int32_t hidden_size, hidden_size_1;
+    float input_dropout, feature_map_dropout, hidden_dropout; /* sites 0, 1, 2 */
+    int32_t train;                                            /* 0 = model.eval() */
+    uint64_t seed, offset;                                    /* Philox key and step offset */
+    float eps[3], momentum[3];                                /* bn0, bn1, bn2 */
+    /* the 13 parameters in state-dict order: [E,k], [2R,k], [1,E], [1], [1], [32,1,3,3], [32], [32], [32], [k,F], [k], [k], [k] */
+    const float *ent, *rel, *b, *bn0_w, *bn0_b, *conv_w, *conv_b, *bn1_w, *bn1_b, *fc_w, *fc_b, *bn2_w, *bn2_b;
+    float *bn0_mean, *bn0_var, *bn1_mean, *bn1_var, *bn2_mean, *bn2_var; /* running buffers [1], [1], [32], [32], [k], [k] */
+    /* dense grads, may be NULL for forward */
+    float *g_ent, *g_rel, *g_b, *g_bn0_w, *g_bn0_b, *g_conv_w, *g_conv_b, *g_bn1_w, *g_bn1_b, *g_fc_w, *g_fc_b, *g_bn2_w, *g_bn2_b;
+} kge_conve_desc;
+
+/* x[n, k] of the rows (e_i, r_i) on side `side` (one direction: the batch statistics are those of the n rows); row0: the mask row
+ * number of the call's first row.  The training form updates the six running buffers once.  saved: kge_conve_saved_floats(d, n)
+ * floats that the backward of the same rows reads (conv output [n, F] | u [n, k] | the statistics used). */
+size_t kge_conve_saved_floats(const kge_conve_desc* d, int64_t n);
+size_t kge_conve_body_forward_workspace_bytes(const kge_conve_desc* d, int64_t n);
+int kge_conve_body_forward(const kge_conve_desc* d, const int64_t* e, const int64_t* r, int64_t n, int32_t side, int64_t row0, float* x,
+                           float* saved, void* workspace, size_t workspace_bytes, void* stream);
+/* g_* += d(sum x o dx) / d tensor for the same rows, side, row0, descriptor (seed, offset) and `saved`; training form only.  g_b is
+ * the head's and is not touched. */
+size_t kge_conve_body_backward_workspace_bytes(const kge_conve_desc* d, int64_t n);
+int kge_conve_body_backward(const kge_conve_desc* d, const int64_t* e, const int64_t* r, int64_t n, int32_t side, int64_t row0, const float* dx,
+                            const float* saved, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One Trainer.train_step_projection (utils/trainer.py:159-174), arguments of kge_tucker_train_bce: the tail-direction body on (h, r)
+ * and the head-direction body on (t, r) in the same launches (each with its own batch statistics; every running buffer is updated
+ * twice, tail first), kge_head_1n_bce per direction with the bias b (g_ent and g_b accumulated), both backwards. */
+size_t kge_conve_train_bce_workspace_bytes(const kge_conve_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr);
+int kge_conve_train_bce(const kge_conve_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch, const int64_t* hr_off,
+                        const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids, int64_t n_tr, float label_smoothing,
+                        void* workspace, size_t workspace_bytes, float* loss, void* stream);
+
+/* Filtered and raw ranks, arguments and `ranks` layout ([4, n]) of kge_tucker_eval_ranks: the eval-form body on (h, r) with side 0
+ * and on (t, r) with side 1, then kge_head_1n_rank per side with the bias b.  Writes no running buffer. */
+size_t kge_conve_eval_ranks_workspace_bytes(const kge_conve_desc* d, int64_t n);
+int kge_conve_eval_ranks(const kge_conve_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
                          const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
                          int32_t* ties, void* stream);
 

@@ -17,7 +17,7 @@ MODEL_MAP = {  # lower-case name -> "module.Class", same keys as Importer.modelM
     "slm": "pairwise.SLM", "sme": "pairwise.SME", "sme_bl": "pairwise.SME_BL",
     "kg2e": "pairwise.KG2E", "hole": "pairwise.HoLE", "octonione": "pointwise.OctonionE",
     "convkb": "pointwise.ConvKB", "tucker": "projection.TuckER",
-    "proje_pointwise": "projection.ProjE_pointwise",
+    "proje_pointwise": "projection.ProjE_pointwise", "conve": "projection.ConvE",
 }
 
 

@@ -160,7 +160,39 @@ class ProjeDesc(ctypes.Structure):
 
 _PJD = ctypes.POINTER(ProjeDesc)
 
+# ConvE's 13 parameters in state-dict (= descriptor) order, and its six running buffers
+CONVE_TABLES = ("ent", "rel", "b", "bn0_w", "bn0_b", "conv_w", "conv_b", "bn1_w", "bn1_b", "fc_w", "fc_b", "bn2_w", "bn2_b")
+CONVE_BUFFERS = ("bn0_mean", "bn0_var", "bn1_mean", "bn1_var", "bn2_mean", "bn2_var")
+CONVE_MAX_HIDDEN = 1024
+
+
+class ConveDesc(ctypes.Structure):
+    """struct kge_conve_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("hidden_size", ctypes.c_int32),
+                ("hidden_size_1", ctypes.c_int32), ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float),
+                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
+        + [(n, ctypes.c_void_p) for n in CONVE_TABLES] + [(n, ctypes.c_void_p) for n in CONVE_BUFFERS] \
+        + [("g_" + n, ctypes.c_void_p) for n in CONVE_TABLES]
+
+
+_CVD = ctypes.POINTER(ConveDesc)
+
 _SIGNATURES = {
+    "kge_conve_saved_floats": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
+    "kge_conve_body_forward_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
+    "kge_conve_body_forward": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_conve_body_backward_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
+    "kge_conve_body_backward": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_conve_train_bce_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "kge_conve_train_bce": (ctypes.c_int, [_CVD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_conve_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
+    "kge_conve_eval_ranks": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_proje_body_forward_workspace_bytes": (ctypes.c_size_t, [_PJD, ctypes.c_int64]),
     "kge_proje_body_forward": (ctypes.c_int, [_PJD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -1,4 +1,4 @@
-// kge_projection.h -- what the 1-N ("projection") models with their own descriptor share (kge_tucker.hip, kge_proje.hip; DESIGN.md
+// kge_projection.h -- what the 1-N ("projection") models with their own descriptor share (kge_tucker.hip, kge_proje.hip, kge_conve.hip; DESIGN.md
 // section 17): the dropout draw, the wave sum of their row kernels, the small host checks and the rank pass of kge_projection.hip.
 //
 // Dropout masks are never stored: forward and backward recompute them from Philox4x32-10 (kge_sampler_device.h).
@@ -67,6 +67,7 @@ struct ProjectionEval {
     const float* ent;
     size_t body_bytes;             // what `body` needs for the 2n rows of the call
     ProjectionBodyFn* body;
+    const float* bias = nullptr;   // the head's bias [tot_entity] (ConvE's b); NULL = none (TuckER, ProjE_pointwise)
 };
 size_t projection_eval_workspace_bytes(const ProjectionEval& m, int64_t n);
 int projection_eval_ranks(const char* who, const ProjectionEval& m, const void* desc, const int64_t* triples, int64_t n,

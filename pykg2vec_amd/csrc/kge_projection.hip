@@ -48,7 +48,7 @@ static ProjectionEvalPlan projection_eval_plan(const ProjectionEval& m, int64_t 
     p.ranks = p.x + align256((size_t)2 * n * m.dim * sizeof(float));
     p.rest = p.ranks + align256((size_t)4 * n * sizeof(int32_t));
     size_t rest = m.body_bytes;
-    const size_t hr = kge_head_1n_rank_workspace_bytes(n, m.dim, m.tot_entity, 0);
+    const size_t hr = kge_head_1n_rank_workspace_bytes(n, m.dim, m.tot_entity, m.bias ? 1 : 0);
     if (hr > rest) rest = hr;
     p.total = p.rest + align256(rest);
     return p;
@@ -81,9 +81,9 @@ int projection_eval_ranks(const char* who, const ProjectionEval& m, const void* 
     if (int rc = check_launch("k_projection_eval_ids")) return rc;
     if (int rc = m.body(desc, e, rr, n, x, rest, rest_bytes, s)) return rc;
     // tail sweep: body(h, r), true entity t, filter hr_t; head sweep: body(t, r), true entity h, filter tr_h
-    if (int rc = kge_head_1n_rank(x, n, m.dim, m.ent, m.tot_entity, nullptr, triples, tail_off, tail_ids, rest, rest_bytes, tmp,
+    if (int rc = kge_head_1n_rank(x, n, m.dim, m.ent, m.tot_entity, m.bias, triples, tail_off, tail_ids, rest, rest_bytes, tmp,
                                   ties ? ties + n : nullptr, nullptr, stream)) return rc;
-    if (int rc = kge_head_1n_rank(x + n * m.dim, n, m.dim, m.ent, m.tot_entity, nullptr, swapped, head_off, head_ids, rest, rest_bytes,
+    if (int rc = kge_head_1n_rank(x + n * m.dim, n, m.dim, m.ent, m.tot_entity, m.bias, swapped, head_off, head_ids, rest, rest_bytes,
                                   tmp + 2 * n, ties, nullptr, stream)) return rc;
     hipLaunchKernelGGL(k_projection_pack_ranks, dim3(blocks), dim3(256), 0, s, tmp, tmp + 2 * n, n, ranks);
     return check_launch("k_projection_pack_ranks");

@@ -724,6 +724,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
         return tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     if isinstance(desc, L.ProjeDesc):
         return proje_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
+    if isinstance(desc, L.ConveDesc):
+        return conve_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -1420,7 +1422,7 @@ def head_1n_bce(x, ent, bias, label_off, label_ids, label_smoothing, loss_buf, g
     return dx
 
 
-# ---------------------------------------------------------------- shared by the models with their own descriptor (ConvKB, TuckER, ProjE)
+# ---------------------------------------------------------------- shared by the models with their own descriptor (ConvKB, TuckER, ProjE, ConvE)
 def _check_embeddings(model, *specs):
     """specs: (name, tensor, rows indexed by id, columns)."""
     for name, t, rows, cols in specs:
@@ -1740,3 +1742,85 @@ def proje_train(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, neg, lmbda, loss_
 def proje_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
     """int32 [4, n] as eval_ranks, in one kge_proje_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
     return _projection_eval_ranks("kge_proje_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)
+
+
+# ---------------------------------------------------------------- ConvE (csrc/kge_conve.hip): its own descriptor and entry points
+def conve_shapes(tot_entity, tot_relation, hidden_size, hidden_size_1):
+    """The shapes of the 13 parameters (state-dict order) and of the six running buffers."""
+    E, R, k, h1 = int(tot_entity), int(tot_relation), int(hidden_size), int(hidden_size_1)
+    F = 32 * (2 * (k // h1) - 2) * (h1 - 2)
+    return ([(E, k), (2 * R, k), (1, E), (1,), (1,), (32, 1, 3, 3), (32,), (32,), (32,), (k, F), (k,), (k,), (k,)],
+            [(1,), (1,), (32,), (32,), (k,), (k,)])
+
+
+def conve_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, hidden_size, hidden_size_1, dropouts=(0.0, 0.0, 0.0),
+               eps=(1e-5, 1e-5, 1e-5), momentum=(0.1, 0.1, 0.1), train=False, seed=0, offset=0):
+    """kge_conve_desc.  `tables` / `grads`: the 13 parameters in state-dict order (ent_embeddings.weight, rel_embeddings.weight, b.weight,
+    bn0.weight, bn0.bias, conv2d_1.weight, conv2d_1.bias, bn1.weight, bn1.bias, fc.weight, fc.bias, bn2.weight, bn2.bias); `buffers`:
+    the running mean / variance of bn0, bn1, bn2, which the training form updates in place.  Shapes are checked here (the kernels index
+    by id and by shape without a bounds test) whenever the geometry is one the library accepts; the geometry, the rates, the momenta and
+    the offset are checked by the library, which refuses bad ones loudly."""
+    E, R, k, h1 = int(tot_entity), int(tot_relation), int(hidden_size), int(hidden_size_1)
+    if len(tables) != 13 or len(buffers) != 6:
+        raise L.KgeHipError("conve: 13 tensors and 6 running buffers expected, got %d and %d" % (len(tables), len(buffers)))
+    if any(m is None for m in momentum):
+        raise L.KgeHipError("conve: momentum None (the cumulative moving average) is not built")
+    if h1 >= 3 and k % h1 == 0 and 2 * (k // h1) >= 3:
+        _check_embeddings("conve", ("ent_embeddings", tables[0], E, k), ("rel_embeddings", tables[1], 2 * R, k))
+        want_t, want_b = conve_shapes(E, R, k, h1)
+        for name, t, shape in zip(L.CONVE_TABLES[2:] + L.CONVE_BUFFERS, list(tables[2:]) + list(buffers), want_t[2:] + want_b):
+            if tuple(t.shape) != shape:
+                raise L.KgeHipError("conve: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
+    d = L.ConveDesc()
+    d.tot_entity, d.tot_relation, d.hidden_size, d.hidden_size_1 = E, R, k, h1
+    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
+    _set_rng(d, train, seed, offset)
+    for i in range(3):
+        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
+    for name, t in zip(L.CONVE_TABLES + L.CONVE_BUFFERS, list(tables) + list(buffers)):
+        setattr(d, name, _dev(t, torch.float32, name).value)
+    if grads is not None:
+        if len(grads) != 13:
+            raise L.KgeHipError("conve: 13 gradient tensors expected, got %d" % len(grads))
+        _bind_grads(d, ["g_" + n for n in L.CONVE_TABLES], ["grad of " + n for n in L.CONVE_TABLES], grads, tables)
+    d._keepalive = (tables, buffers, grads)
+    d._ws = None
+    return d
+
+
+def conve_body_forward(desc, e, r, side, row0=0):
+    """(x float32 [n, k], saved): the body of ConvE.forward on the rows (e_i, r_i) of one direction (side 0 = tail, 1 = head); the
+    training form updates the descriptor's running buffers once.  `saved` is what conve_body_backward reads."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    lib = L.load()
+    x = torch.empty((n, desc.hidden_size), dtype=torch.float32, device=e.device)
+    wp, wb = _desc_ws(desc, "kge_conve_body_forward_workspace_bytes", n)
+    saved = torch.empty(max(1, int(lib.kge_conve_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
+    L.check(lib.kge_conve_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(side), int(row0), _dev(x, torch.float32, "x"),
+                                       _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_conve_body_forward")
+    return x, saved
+
+
+def conve_body_backward(desc, e, r, side, dx, saved, row0=0):
+    """g_* of the descriptor += the body's gradients given d loss / d x (same rows, side, row0, seed, offset and `saved` as the forward)."""
+    n = e.numel()
+    wp, wb = _desc_ws(desc, "kge_conve_body_backward_workspace_bytes", n)
+    L.check(L.load().kge_conve_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(side), int(row0),
+                                             _dev(dx, torch.float32, "dx"), _dev(saved, torch.float32, "saved"), wp, wb, _stream()),
+            "kge_conve_body_backward")
+
+
+def conve_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
+    """One train_step_projection of ConvE: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice (tail
+    direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
+    B, n_hr, n_tr, args = _label_csr_args("conve_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
+    wp, wb = _desc_ws(desc, "kge_conve_train_bce_workspace_bytes", B, n_hr, n_tr)
+    L.check(L.load().kge_conve_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+                                         _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_conve_train_bce")
+
+
+def conve_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks, in one kge_conve_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
+    return _projection_eval_ranks("kge_conve_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)

@@ -9,6 +9,8 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
   torch.ops.kge.tucker_body_backward(key, e, r, seed, offset, dx, saved, weights) -> their dense gradients
   torch.ops.kge.proje_body(key, e, r, side, seed, offset, weights) -> x float32 [N, k]   tanh(ent[e] o De_s + rel[r] o Dr_s + bc_s) with dropout: f1 / f2 of ProjE_pointwise (models/projection.py:212-228); weights = its parameter_list
   torch.ops.kge.proje_body_backward(key, e, r, side, seed, offset, dx, weights) -> their dense gradients
+  torch.ops.kge.conve_body(key, e, r, side, seed, offset, weights) -> (x float32 [N, k], saved)   the body of ConvE.forward (models/projection.py:86-99, 104-113) up to the head; weights = its 13 tensors in state-dict order; the training form updates the model's running buffers, a write outside the op's schema: eager execution only
+  torch.ops.kge.conve_body_backward(key, e, r, side, seed, offset, dx, saved, weights) -> their dense gradients (b's is the head's: zero here)
   torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]   the projection models' 1-N head (models/projection.py:100-102)
   torch.ops.kge.one_to_n_scores_backward(x, ent, preds, dpreds, need_bias) -> (dx, g_ent, g_bias)
 
@@ -225,6 +227,60 @@ def _proje_backward(ctx, dx):
 
 
 proje_body.register_autograd(_proje_backward, setup_context=_proje_setup)
+
+
+# ConvE's body (include/kge_hip.h: kge_conve_body_*).  side 0 = the tail direction, 1 = the head direction; offset < 0 = the eval form
+# (running statistics, no bn2, no draws).  The mask rows of a call start at side * n: the head direction's rows follow the tail
+# direction's, as in the fused step, so that the two forward calls of a training step under one (seed, offset) draw the step's masks.
+# The training form updates the model's running buffers (found through the model handle, not passed as tensors).  That write is not
+# in the op's schema (mutates_args is empty), so the op is for eager execution only: under torch.compile or functionalisation the
+# update is invisible, and a training-form call whose outputs are unused could be dropped together with it.
+@torch.library.custom_op("kge::conve_body", mutates_args=(), device_types="cuda")
+def conve_body(key: int, e: Tensor, r: Tensor, side: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
+    m = _model(key)
+    return K.conve_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                                r.contiguous(), side, row0=side * e.numel())
+
+
+@conve_body.register_fake
+def _(key, e, r, side, seed, offset, weights):
+    n, k = e.numel(), weights[0].shape[1]
+    return weights[0].new_empty((n, k)), weights[0].new_empty((n * (weights[9].shape[1] + k) + 66 + 2 * k,))
+
+
+@conve_body.register_kernel("cpu")
+def _(key, e, r, side, seed, offset, weights):
+    raise L.KgeHipError("kge::conve_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
+
+
+@torch.library.custom_op("kge::conve_body_backward", mutates_args=(), device_types="cuda")
+def conve_body_backward(key: int, e: Tensor, r: Tensor, side: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
+                        weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.conve_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                          r.contiguous(), side, dx.contiguous(), saved, row0=side * e.numel())
+    return grads
+
+
+@conve_body_backward.register_fake
+def _(key, e, r, side, seed, offset, dx, saved, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _conve_setup(ctx, inputs, output):
+    key, e, r, side, seed, offset, weights = inputs
+    ctx.key, ctx.side, ctx.seed, ctx.offset = key, side, seed, offset
+    ctx.save_for_backward(e, r, output[1], *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _conve_backward(ctx, dx, _dsaved):
+    e, r, saved, *weights = ctx.saved_tensors
+    return None, None, None, None, None, None, conve_body_backward(ctx.key, e, r, ctx.side, ctx.seed, ctx.offset, dx, saved, weights)
+
+
+conve_body.register_autograd(_conve_backward, setup_context=_conve_setup)
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

@@ -1,8 +1,9 @@
-"""Drop-in projection (1-N) models mirroring pykg2vec/models/projection.py, scored by HIP kernels.  TuckER and ProjE_pointwise are the
-models of that family whose body is no convolution stack.  TuckER: two L2 normalisations and a contraction with the shared core
+"""Drop-in projection (1-N) models mirroring pykg2vec/models/projection.py, scored by HIP kernels.  TuckER: two L2 normalisations and a contraction with the shared core
 (csrc/kge_tucker.hip) in front of the 1-N head (csrc/kge_head.hip).  ProjE_pointwise: a pointwise tanh body whose loss reads only the
 labelled columns of the 1-N product (csrc/kge_proje.hip); it is the one model here that trains with sampled negatives on this path.
-ConvE, InteractE, HypER and AcrE keep their PyTorch layers and call the head themselves."""
+ConvE: batch norm, a 3 x 3 convolution, a fully connected layer on the matrix cores and two more batch norms (csrc/kge_conve.hip) in
+front of the head with its bias b; its torch layers are holders of parameters and buffers only.  InteractE, HypER and AcrE keep their
+PyTorch layers and call the head themselves."""
 import torch
 
 from . import _lib as L  # noqa: F401
@@ -56,6 +57,98 @@ class TuckER(ProjectionModel):
             self.dropout_offset += 1
         x, _saved = torch.ops.kge.tucker_body(self._kge_op_key, e1, r, self.dropout_seed, offset, self.trainable_tensors())
         return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, None, False)
+
+    def predict_tail_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
+        return rank
+
+    def predict_head_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
+        return rank
+
+
+class ConvE(ProjectionModel):
+    """projection.py:12-125.  forward(e, r, direction) = sigmoid(x @ ent.T + b) with x = relu(bn2(hdrop(fc(flatten(fdrop(relu(bn1(conv(
+    idrop(bn0(img)))))))))) and img the [h2, h1] view of ent[e] stacked on that of rel[r] ("tail") or rel[r + tot_relation] ("head").  The
+    torch layers (bn0, conv2d_1, bn1, fc, bn2) hold parameters and buffers only, so state_dict() has the reference's keys and shapes and
+    loads a reference checkpoint; the arithmetic is csrc/kge_conve.hip.  Under train() a forward normalises with the statistics of its
+    own rows, updates the six running buffers and the three num_batches_tracked counters as torch does (under no_grad too), and draws the
+    Philox masks of (dropout_seed, dropout_offset) instead of torch's generator (include/kge_hip.h spells the counters out), the mask
+    rows of the "head" direction following those of the "tail" direction; with any rate > 0 it then advances dropout_offset by one, as
+    TuckER does.  Under eval() bn0 and bn1 use the running buffers, bn2 is skipped (the reference's `if self.training`), nothing is drawn
+    and nothing is written."""
+    kernel_name = "conve"
+    TENSORS = ("ent_embeddings.weight", "rel_embeddings.weight", "b.weight", "bn0.weight", "bn0.bias", "conv2d_1.weight", "conv2d_1.bias",
+               "bn1.weight", "bn1.bias", "fc.weight", "fc.bias", "bn2.weight", "bn2.bias")   # descriptor order = state-dict order
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        param_list = ["tot_entity", "tot_relation", "hidden_size", "hidden_size_1", "lmbda", "input_dropout", "feature_map_dropout",
+                      "hidden_dropout"]
+        self.__dict__.update(self.load_params(param_list, kwargs))
+        k, h1 = int(self.hidden_size), int(self.hidden_size_1)
+        self.hidden_size_2 = k // h1
+        # (the reference replaces the three rates by nn.Dropout modules inp_drop / feat_drop / hidden_drop; here the rates stay numbers)
+        self.dropouts = (float(self.input_dropout), float(self.feature_map_dropout), float(self.hidden_dropout))
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, k)       # N(0, 1), as the reference leaves them
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation * 2, k)  # every relation and its reciprocal
+        self.b = NamedEmbedding("b", 1, self.tot_entity)
+        self.bn0 = torch.nn.BatchNorm2d(1)
+        self.conv2d_1 = torch.nn.Conv2d(1, 32, (3, 3), stride=(1, 1))
+        self.bn1 = torch.nn.BatchNorm2d(32)
+        # (max(..., 1): a geometry the library refuses must still construct, so that the refusal is the library's sentence)
+        self.fc = torch.nn.Linear(max((2 * self.hidden_size_2 - 2) * (h1 - 2) * 32, 1), k)
+        self.bn2 = torch.nn.BatchNorm1d(k)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings, self.b]
+        self.loss = Criterion.multi_class_bce
+        self.dropout_seed = int(kwargs.get("seed", 0) or 0)
+        self.dropout_offset = 0
+
+    def _norms(self):
+        return (self.bn0, self.bn1, self.bn2)
+
+    def trainable_tensors(self):
+        return [self.ent_embeddings.weight, self.rel_embeddings.weight, self.b.weight, self.bn0.weight, self.bn0.bias, self.conv2d_1.weight,
+                self.conv2d_1.bias, self.bn1.weight, self.bn1.bias, self.fc.weight, self.fc.bias, self.bn2.weight, self.bn2.bias]
+
+    def running_buffers(self):
+        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+
+    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        return K.conve_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
+                            tot_relation=self.tot_relation, hidden_size=int(self.hidden_size), hidden_size_1=int(self.hidden_size_1),
+                            dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()], momentum=[bn.momentum for bn in self._norms()],
+                            train=self.training if train is None else train, seed=self.dropout_seed if seed is None else seed,
+                            offset=self.dropout_offset if offset is None else offset)
+
+    def _count_batches(self, calls):
+        for bn in self._norms():
+            bn.num_batches_tracked += calls
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        K.conve_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
+        self._count_batches(2)   # the step is two training forwards
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def embed2(self, e, r):
+        return self.ent_embeddings(e), self.rel_embeddings(r)
+
+    def forward(self, e, r, direction="tail"):
+        assert direction in ("head", "tail"), "Unknown forward direction"
+        offset = -1   # eval(): running statistics, no bn2, no dropout
+        if self.training:
+            offset = self.dropout_offset
+            if any(p > 0.0 for p in self.dropouts):
+                self.dropout_offset += 1
+        x, _saved = torch.ops.kge.conve_body(self._kge_op_key, e, r, 0 if direction == "tail" else 1, self.dropout_seed, offset,
+                                             self.trainable_tensors())
+        if self.training:
+            self._count_batches(1)
+        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.b.weight, False)
 
     def predict_tail_rank(self, e, r, topk=-1):
         _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)

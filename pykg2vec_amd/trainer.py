@@ -93,7 +93,8 @@ class Trainer:
     def _refuse_projection(self):
         """The projection path is the fused single-GPU step.  TuckER (csrc/kge_tucker.hip): body, 1-N head with multi_class_bce per
         direction, body backward.  ProjE_pointwise (csrc/kge_proje.hip): body, the loss over the labelled columns per direction, body
-        backward, regulariser.  What it does not serve is refused here, before anything is built."""
+        backward, regulariser.  ConvE (csrc/kge_conve.hip): both directions' bodies with their own batch statistics, the head with its
+        bias per direction, both backwards.  What it does not serve is refused here, before anything is built."""
         def no(what):
             raise NotImplementedError("%s: %s is not supported on the projection path (single-GPU fused step only)"
                                       % (type(self.model).__name__, what))
