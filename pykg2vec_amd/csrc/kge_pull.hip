@@ -64,6 +64,7 @@ struct PullArgs {
     void* codes;               // [n_pairs][G * NV] 16 bits per lane: the signs of its four elements of the positive residual (2 bits each,
                                // low byte) and of the negative residual (high byte) -- one 16-bit load per visit
     int64_t n_pairs;
+    unsigned wt;               // kWt* bits: the output streams stored write-through (store16_wt) instead of left dirty in the XCD's L2
 };
 
 #define KGE_F4_EACH(expr_x, expr_y, expr_z, expr_w) expr_x; expr_y; expr_z; expr_w;
@@ -141,16 +142,24 @@ __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const 
     n2 = gsum<G>(n2);
     const float nn = sqrtf(n2);
     const float inn = 1.0f / fmaxf(nn, kEpsNormalize);
-    store_row4<G, NV>(t_out + off, P, nvec, gl);
-    if constexpr (OPT != KGE_OPT_SGD) store_row4<G, NV>(st1 + off, M1, nvec, gl);
-    if constexpr (OPT == KGE_OPT_ADAM) store_row4<G, NV>(st2 + off, M2, nvec, gl);
+    // Per stream: a plain store stays dirty in this XCD's L2 and is written back at the launch boundary, in front of k_pull_eval; a
+    // write-through store leaves while the other owners still work (profiles/r14_experiments.md).  The flavours are
+    // kernel-uniform.  All four on (what ships) and all four off are straight-line blocks; a mixed choice (A/B runs) pays a scalar
+    // branch per stream, which is measurable in this VALU-bound kernel.
     float4* const hrow = reinterpret_cast<float4*>(reinterpret_cast<char*>(h_out) + (int64_t)(is_rel ? g - a.E : g) * a.hat_row_bytes);
     const int hvec = (int)(a.hat_row_bytes >> 4);   // float4 slots of a hat row: G * NV (padded: lanes beyond the row store their zeros) or d / 4
+    auto store_streams = [&](bool wt_tab, bool wt_s1, bool wt_s2, bool wt_hat) {
+        store_row4<G, NV>(t_out + off, P, nvec, gl, wt_tab);
+        if constexpr (OPT != KGE_OPT_SGD) store_row4<G, NV>(st1 + off, M1, nvec, gl, wt_s1);
+        if constexpr (OPT == KGE_OPT_ADAM) store_row4<G, NV>(st2 + off, M2, nvec, gl, wt_s2);
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        P[v].x *= inn; P[v].y *= inn; P[v].z *= inn; P[v].w *= inn;
-        if (v * G + gl < hvec) hrow[v * G + gl] = P[v];
-    }
+        for (int v = 0; v < NV; ++v) { P[v].x *= inn; P[v].y *= inn; P[v].z *= inn; P[v].w *= inn; }
+        store_row4<G, NV>(reinterpret_cast<float*>(hrow), P, hvec, gl, wt_hat);
+    };
+    const unsigned wt = a.wt & kWtFinish;
+    if (wt == kWtFinish) store_streams(true, true, true, true);
+    else if (wt == 0u) store_streams(false, false, false, false);
+    else store_streams((wt & kWtTab) != 0, (wt & kWtS1) != 0, (wt & kWtS2) != 0, (wt & kWtHat) != 0);
     if (gl == 0) a.norm_out[g] = nn;
 }
 
@@ -173,8 +182,10 @@ struct PullRows {
 constexpr int kEvalPP = 2;
 constexpr bool kHatCompactDefault = true;   // hat rows: padded to 4 * G * NV floats (rounds 2-5) or compact (KGE_HAT_COMPACT=1)
 // (C1, NV = 1: 62 VGPRs -- 8 waves per SIMD, the launch's 2 048 workgroups are one residency round; tests/test_pull_occupancy.py checks it)
-template <bool L1, int G, int NV>
-__global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restrict__ loss) {
+// (WT: records and codes stored write-through, switch WT_EVAL -- a kernel of its own, k_pull_eval_wt, so that the shipped kernel carries
+//  none of its code: the flavour as a run-time branch cost k_pull_eval 0.18 us, profiles/r14_experiments.md section 4)
+template <bool L1, int G, int NV, bool WT>
+__device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restrict__ loss) {
     constexpr int GPB = kBlock / G, PP = kEvalPP;
     KGE_TS_BEGIN(1)
     const int gl = threadIdx.x % G;
@@ -241,7 +252,11 @@ __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restr
         if (!on[q]) continue;   // (group-uniform)
         acc += fmaxf(vv, 0.f);
         const float coef = (vv > 0.f ? 1.f : (vv == 0.f ? 0.5f : 0.f)) * th[q];
-        if (gl == 0) a.recs[i] = make_float4(tail ? -coef : coef, sp, sn, 0.f);   // (coef >= 0: its sign carries `tail`)
+        constexpr bool wt = WT;
+        if (gl == 0) {   // (coef >= 0: its sign carries `tail`)
+            const float4 rec = make_float4(tail ? -coef : coef, sp, sn, 0.f);
+            if (wt) store16_wt(a.recs + i, rec); else a.recs[i] = rec;
+        }
         if (coef != 0.f) {
             if constexpr (L1) {
                 unsigned short* cp = reinterpret_cast<unsigned short*>(a.codes) + i * (int64_t)(G * NV);
@@ -257,7 +272,13 @@ __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restr
                       bn |= (s2 > 0.f ? 1u : (s2 < 0.f ? 3u : 0u)) << sh; }
                     KGE_CODE(x, 0) KGE_CODE(y, 2) KGE_CODE(z, 4) KGE_CODE(w, 6)
 #undef KGE_CODE
-                    cp[v * G + gl] = (unsigned short)(bp | bn << 8);
+                    const unsigned code = bp | bn << 8;
+                    if (wt) {   // 16-byte stores only (a 2-byte write-through store is a fabric write of its own): eight lanes' codes per store
+                        const unsigned d0 = code | (unsigned)__shfl_down((int)code, 1, G) << 16;
+                        const unsigned d1 = (unsigned)__shfl_down((int)d0, 2, G), d2 = (unsigned)__shfl_down((int)d0, 4, G), d3 = (unsigned)__shfl_down((int)d0, 6, G);
+                        if ((gl & 7) == 0)
+                            store16_wt(reinterpret_cast<float4*>(cp + v * G + gl), make_float4(__uint_as_float(d0), __uint_as_float(d1), __uint_as_float(d2), __uint_as_float(d3)));
+                    } else cp[v * G + gl] = (unsigned short)code;
                 }
             }
         }
@@ -265,6 +286,10 @@ __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restr
     block_accumulate_loss<G>(acc, gl, loss);
     KGE_TS_END(1, 1)
 }
+template <bool L1, int G, int NV>
+__global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restrict__ loss) { pull_eval_body<L1, G, NV, false>(a, loss); }
+template <bool L1, int G, int NV>
+__global__ __launch_bounds__(kBlock) void k_pull_eval_wt(PullArgs a, float* __restrict__ loss) { pull_eval_body<L1, G, NV, true>(a, loss); }
 
 // (two-phase form with NV = 1: 8 waves per SIMD, 2 048 workgroup slots instead of 1 792 for the C1 launch's 2 045 owner and 128 sampler
 //  workgroups.  The attribute is a guard: the code fits without it; an edit that needs more registers now spills, which
@@ -712,8 +737,15 @@ static int launch_pull_geo(PullArgs& a, const PullSampleArgs& sa, float* loss, h
     a.sample_blocks = sa.n > 0 ? (int)((sa.n + kBlock - 1) / kBlock) : 0;
     if (a.recs) {   // two-phase form (L1 only): evaluate every pair once, then let the owners sum the records
         const unsigned eb = (unsigned)((a.n_pairs + GPB * kEvalPP - 1) / (GPB * kEvalPP));
-        hipLaunchKernelGGL((k_pull_eval<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
+        if (a.wt & kWtEval) hipLaunchKernelGGL((k_pull_eval_wt<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
+        else hipLaunchKernelGGL((k_pull_eval<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
         hipLaunchKernelGGL((k_pull_step<OPT, true, G, NV, true>), dim3((unsigned)(item_blocks + a.sample_blocks)), dim3(kBlock), 0, s, a, sa, loss);
+#ifdef KGE_TS_DEBUG
+        // timeline study of the boundary BEHIND the owner launch (tools/wg_timeline.py c1gap): KGE_TS_EVAL_AFTER=1 repeats the evaluation
+        // after it -- same inputs, same records and codes; the loss counts twice -- so that the last records of the two slots are
+        // neighbours in this order as well
+        if (switch_value("TS_EVAL_AFTER") == 1) hipLaunchKernelGGL((k_pull_eval<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
+#endif
     } else if (a.l1)
         hipLaunchKernelGGL((k_pull_step<OPT, true, G, NV>), dim3((unsigned)(item_blocks + a.sample_blocks)), dim3(kBlock), 0, s, a, sa, loss);
     else
@@ -744,6 +776,18 @@ int pull_partial_stride(int dim) { const PullGeo g = pull_geo(dim); return 4 * g
 static unsigned hat_row_bytes(const PullGeo& g, int dim) {
     const int sw = switch_value("HAT_COMPACT");
     return (sw >= 0 ? sw == 1 : kHatCompactDefault) ? 4u * (unsigned)dim : 16u * (unsigned)g.G * (unsigned)g.NV;
+}
+// Which output streams of the step are stored write-through (each A/B-tested alone, profiles/r14_experiments.md).
+// Kernel-uniform: read here once per launch, not per lane.
+static unsigned write_through_mask() {
+    static const struct { const char* name; unsigned bit; bool on; } kStreams[] = {
+        {"WT_S1", kWtS1, true}, {"WT_S2", kWtS2, true}, {"WT_TAB", kWtTab, true}, {"WT_HAT", kWtHat, true}, {"WT_EVAL", kWtEval, false}};
+    unsigned m = 0;
+    for (const auto& st : kStreams) {
+        const int sw = switch_value(st.name);
+        if (sw >= 0 ? sw != 0 : st.on) m |= st.bit;
+    }
+    return m;
 }
 int pull_hat_stride(int dim) { const PullGeo g = pull_geo(dim); return g.G ? (int)(hat_row_bytes(g, dim) / 4) : 0; }
 int pull_groups_per_block(int dim) { const PullGeo g = pull_geo(dim); return g.G ? kBlock / g.G : 0; }
@@ -795,6 +839,7 @@ int launch_pull_step(const kge_model_desc* m, float* const tables_out[2], const 
     a.recs = two_phase ? reinterpret_cast<float4*>(dir->recs) : nullptr;
     a.codes = two_phase ? dir->codes : nullptr;
     a.n_pairs = two_phase ? dir->n_pairs : 0;
+    a.wt = write_through_mask();
     PullSampleArgs sa = make_sample_args(next_pairs, next_inv, next_pairs && next_lists ? next_n : 0, m->tot_entity, bern, slots,
                                          n_slots, seed, next_offset, nullptr, next_lists);
     sa.no_desc = two_phase && dir->lists_without_descriptors ? 1 : 0;

@@ -148,6 +148,30 @@ __device__ __forceinline__ void store_row4(float* __restrict__ row, const float4
         if (i < nvec) reinterpret_cast<float4*>(row)[i] = x[v];
     }
 }
+// One 16-byte WRITE-THROUGH store (vector global_store_dwordx4 ... sc1): the bytes leave for memory as the store executes and the line is
+// dropped from the writing XCD's L2, where a plain store leaves it dirty until the launch boundary writes it back in front of the
+// dependent kernel (nontemporal stores keep the line dirty too).  The compiler does not count an asm store in its s_waitcnt bookkeeping --
+// nothing ever waits for one, and an uncounted older operation only makes its waits stricter -- and pads nothing inside the string: the
+// s_nop keeps the next instruction off the data registers until the store has read them.
+typedef float pull_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store16_wt(float4* p, const float4& x) {
+    const pull_f32x4 v = {x.x, x.y, x.z, x.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+}
+// store_row4 with the flavour chosen at run time (wt is kernel-uniform: one scalar branch): same lanes, same predicate, one 16-byte
+// store per lane
+template <int G, int NV>
+__device__ __forceinline__ void store_row4(float* __restrict__ row, const float4 (&x)[NV], int nvec, int gl, bool wt) {
+    if (!wt) { store_row4<G, NV>(row, x, nvec, gl); return; }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int i = v * G + gl;
+        if (i < nvec) store16_wt(reinterpret_cast<float4*>(row) + i, x[v]);
+    }
+}
+// PullArgs::wt, one bit per output stream of the owner-computes TransE step (switches WT_S1, WT_S2, WT_TAB, WT_HAT, WT_EVAL)
+constexpr unsigned kWtS1 = 1u, kWtS2 = 2u, kWtTab = 4u, kWtHat = 8u, kWtEval = 16u, kWtFinish = kWtS1 | kWtS2 | kWtTab | kWtHat;
+
 static inline PullLists to_lists(const kge_pull_lists* l) {
     PullLists o;
     o.pc = l->pc; o.count = l->count; o.bucket = l->bucket; o.head = l->head; o.next = l->next;

@@ -4,6 +4,9 @@ of interest (the records are those of the LAST launch of a slot).
 
   KGE_HIP_LIB=tools/_libs/ts.so python tools/wg_timeline.py c1       # k_pull_step (slot 0) and k_pull_eval (slot 1) of the C1 step
   KGE_HIP_LIB=tools/_libs/ts.so python tools/wg_timeline.py transr   # k_transr_g2 of the TransR FB15k 100 / 100 B = 32 768 step
+  KGE_HIP_LIB=tools/_libs/ts.so python tools/wg_timeline.py c1gap    # C1: idle time at the boundary between the two kernels' last launches:
+                                                                     # behind k_pull_eval (eval -> step); with KGE_TS_EVAL_AFTER=1 in the
+                                                                     # environment behind k_pull_step (step -> a repeated eval)
 
 Prints: kernel span, workgroup lifetimes (mean / quantiles), start- and end-time quantiles, the maximum number of concurrently
 resident workgroups per CU (from HW_REG_HW_ID / HW_REG_XCC_ID), live workgroups in flight over time.  Tags: 1 = worker, 2 = the
@@ -71,7 +74,25 @@ def analyse(name, t, live_tags=None):
     print("  in flight (tag > 0):", ", ".join("t=%dus %d" % (q, int((((t0 - base) <= q * 100) & ((t1 - base) > q * 100) & live).sum())) for q in pts))
 
 
-def run_c1():
+def boundary_gap(step, ev):
+    """Last workgroup exit of the earlier launch -> first workgroup entry of the later one (both slots hold their LAST launch; one
+    100 MHz clock).  Records of older launches (block ids the last launch did not have) are dropped: nearly all records are the last
+    launch's, its workgroups enter within a few us of each other, and the launch before it began a whole step (> 25 us) earlier."""
+    def last(t):
+        t0 = t[:, 0].astype(np.int64)
+        return t[t0 >= np.median(t0) - 1200]
+    step, ev = last(step), last(ev)
+    s0, s1 = step[:, 0].astype(np.int64), step[:, 1].astype(np.int64)
+    e0, e1 = ev[:, 0].astype(np.int64), ev[:, 1].astype(np.int64)
+    first, a0, a1, b0, b1 = ("k_pull_eval -> k_pull_step", e0, e1, s0, s1) if e0.min() < s0.min() else ("k_pull_step -> k_pull_eval", s0, s1, e0, e1)
+    us = lambda x: x / 100.0
+    print("== boundary %s: gap %.2f us (last exit -> first entry) | earlier launch: span %.2f us, exits p50 %.2f p90 %.2f p99 %.2f before its last | "
+          "later launch: entries p50 %.2f p90 %.2f after its first, span %.2f us"
+          % (first, us(b0.min() - a1.max()), us(a1.max() - a0.min()), us(a1.max() - np.percentile(a1, 50)), us(a1.max() - np.percentile(a1, 90)),
+             us(a1.max() - np.percentile(a1, 99)), us(np.percentile(b0, 50) - b0.min()), us(np.percentile(b0, 90) - b0.min()), us(b1.max() - b0.min())))
+
+
+def run_c1(gap=False):
     E, R, NTR, B = 14951, 1345, 483142, 32768
     rng = np.random.default_rng(1234)
     hp = dict(hidden_size=100, l1_flag=True, margin=1.0)
@@ -83,8 +104,12 @@ def run_c1():
     tr.generator = tr._new_generator()
     tr.train_model_epoch(0); tr.train_model_epoch(1)
     torch.cuda.synchronize()
-    analyse("k_pull_step (C1, B = 32768)", dump("pull", 0))
-    analyse("k_pull_eval (C1, B = 32768)", dump("pull", 1))
+    step, ev = dump("pull", 0), dump("pull", 1)
+    if gap:
+        boundary_gap(step, ev)
+        return
+    analyse("k_pull_step (C1, B = 32768)", step)
+    analyse("k_pull_eval (C1, B = 32768)", ev)
 
 
 def run_transr():
@@ -105,4 +130,4 @@ def run_transr():
 
 
 if __name__ == "__main__":
-    {"c1": run_c1, "transr": run_transr}[sys.argv[1] if len(sys.argv) > 1 else "c1"]()
+    {"c1": run_c1, "c1gap": lambda: run_c1(gap=True), "transr": run_transr}[sys.argv[1] if len(sys.argv) > 1 else "c1"]()
