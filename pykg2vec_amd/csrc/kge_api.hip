@@ -87,6 +87,52 @@ static int validate_packed_key(const kge_model_desc* m, const char* who) {
 
 using namespace kge;
 
+namespace {
+// What the run loop needs of a plan: the fields the three plan structs share by name.
+struct RunView {
+    const kge_pull_lists* lists;
+    const kge_pull_batch* batches;
+    int64_t n_batches, tot_entity;
+    const float* bern_prob;
+    const uint64_t* slots;
+    int64_t n_slots;
+    uint64_t seed, draws_per_batch;
+};
+template <class Plan>
+RunView run_view(const Plan* p, const kge_model_desc& m) {
+    return {p->lists, p->batches, p->n_batches, m.tot_entity, p->bern_prob, p->slots, p->n_slots, p->seed, (uint64_t)p->draws_per_batch};
+}
+
+// The loop of kge_pull_run / kge_transx_run / kge_own_run.  step(k, b, nb, cl, next_offset) enqueues step k on batch b, which
+// consumes list set cl; nb != NULL: its launch also carries the sampler of batch nb, at Philox offset next_offset, into list
+// set 1 - cl.  Returns the first non-zero result.
+template <class Step>
+int run_steps(const RunView& v, int64_t first_batch, int64_t n_steps, int cl, int32_t lists_ready, uint64_t offset,
+              int32_t sample_after_last, void* stream, Step step) {
+    for (int64_t k = 0; k < n_steps; ++k) {
+        const kge_pull_batch* b = v.batches + first_batch + k;
+        int rc;
+        if (k == 0 && !lists_ready) {
+            rc = kge_pull_sample(b->pairs, b->inv, b->n_pairs, v.tot_entity, v.bern_prob, v.slots, v.n_slots, v.seed, offset, nullptr,
+                                 &v.lists[cl], stream);
+            if (rc) return rc;
+        }
+        // the sampler of the following batch rides in this step's launch: the next step of this run, or -- after the last step --
+        // the batch that follows (sample_after_last == 1) or batch 0 of the next epoch (== 2: the same permutation is walked again,
+        // the Philox counters just keep counting)
+        const bool last = k + 1 == n_steps;
+        const bool wrap = last && sample_after_last == 2;
+        const bool has_next = wrap || ((!last || sample_after_last == 1) && first_batch + k + 1 < v.n_batches);
+        const kge_pull_batch* nb = wrap ? v.batches : (has_next ? b + 1 : nullptr);
+        offset += v.draws_per_batch;
+        rc = step(k, b, nb, cl, offset);
+        if (rc) return rc;
+        if (has_next) cl ^= 1;
+    }
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int kge_abi_version(void) { return KGE_ABI_VERSION; }
@@ -496,6 +542,16 @@ int kge_row_norms(const float* table, int64_t rows, int32_t dim, float* norms, f
 
 static int lists_ok(const kge_pull_lists* l) { return l && l->pc && l->count && l->bucket && l->head && l->next && l->sdesc && l->dbucket; }
 
+// the ride-along sampler's arguments (next_pairs != NULL) of the three owner-computes steps
+static int check_next_sampler(const char* who, const kge_model_desc* m, const kge_pull_lists* lists, const int32_t* next_inv,
+                              int64_t next_n, const uint64_t* slots, int64_t n_slots, const kge_pull_lists* next_lists) {
+    if (next_n < 0 || !next_inv || !lists_ok(next_lists) || next_lists->count == lists->count || (slots && (n_slots & (n_slots - 1)))) {
+        set_error("%s: the next batch's sampler needs its inverse incidence map and its own list set", who);
+        return -1;
+    }
+    return validate_packed_key(m, who);
+}
+
 int kge_pull_sample(const int32_t* pairs, const int32_t* inv, int64_t n, int64_t tot_entity, const float* bern_prob,
                     const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t offset, const int64_t* dev_cursor,
                     const kge_pull_lists* out, void* stream) {
@@ -543,13 +599,7 @@ int kge_pull_step(const kge_model_desc* m, float* const tables_out[2], const flo
     }
     if (optimizer != KGE_OPT_SGD && !grad_only && (!state1 || !state1[0] || !state1[1])) { set_error("kge_pull_step: optimizer state missing"); return -1; }
     if (optimizer == KGE_OPT_ADAM && (!state2 || !state2[0] || !state2[1])) { set_error("kge_pull_step: adam needs two state buffers"); return -1; }
-    if (next_pairs) {
-        if (next_n < 0 || !next_inv || !lists_ok(next_lists) || next_lists->count == lists->count || (slots && (n_slots & (n_slots - 1)))) {
-            set_error("kge_pull_step: the next batch's sampler needs its inverse incidence map and its own list set");
-            return -1;
-        }
-        if (validate_packed_key(m, "kge_pull_step")) return -1;
-    }
+    if (next_pairs && check_next_sampler("kge_pull_step", m, lists, next_inv, next_n, slots, n_slots, next_lists)) return -1;
     return launch_pull_step(m, tables_out, hat_in, hat_out, norm_in, norm_out, state1, state2, pairs, lists, items, n_items, dense_skip, inc, partials, multi,
                             n_multi, margin, optimizer, lr, step, dev_hyper, reset_lists, next_pairs, next_inv, next_n, bern_prob, slots,
                             n_slots, seed, next_offset, next_lists, loss, direction, (hipStream_t)stream);
@@ -571,40 +621,21 @@ int kge_pull_run(const kge_pull_plan* p, int64_t first_batch, int64_t n_steps, i
         set_error("kge_pull_run: bad arguments");
         return -1;
     }
-    int src = src_half, cl = cur_list;
-    uint64_t offset = first_offset;
-    for (int64_t k = 0; k < n_steps; ++k) {
-        const kge_pull_batch* b = p->batches + first_batch + k;
-        int rc;
-        if (k == 0 && !lists_ready) {
-            rc = kge_pull_sample(b->pairs, b->inv, b->n_pairs, p->model[0].tot_entity, p->bern_prob, p->slots, p->n_slots, p->seed, offset,
-                                 nullptr, &p->lists[cl], stream);
-            if (rc) return rc;
-        }
-        // the sampler of the following batch rides in this step's launch: the next step of this run, or -- after the last step --
-        // the batch that follows (sample_after_last == 1) or batch 0 of the next epoch (== 2: the same permutation is walked again,
-        // the Philox counters just keep counting)
-        const bool last = k + 1 == n_steps;
-        const bool wrap = last && sample_after_last == 2;
-        const bool has_next = wrap || ((!last || sample_after_last == 1) && first_batch + k + 1 < p->n_batches);
-        const kge_pull_batch* nb = wrap ? p->batches : (has_next ? b + 1 : nullptr);
+    return run_steps(run_view(p, p->model[0]), first_batch, n_steps, cur_list, lists_ready, first_offset, sample_after_last, stream,
+                     [=](int64_t k, const kge_pull_batch* b, const kge_pull_batch* nb, int cl, uint64_t next_offset) {
+        const int src = src_half ^ (int)(k & 1);   // the table halves alternate
         float* const tables_out[2] = {const_cast<float*>(p->model[1 - src].tables[0]), const_cast<float*>(p->model[1 - src].tables[1])};
         const float* const hat_in[2] = {p->hat[src][0], p->hat[src][1]};
         float* const hat_out[2] = {p->hat[1 - src][0], p->hat[1 - src][1]};
         kge_pull_direction dir = p->direction;
         dir.n_pairs = b->n_pairs;
         dir.lists_without_descriptors = 1;
-        rc = kge_pull_step(&p->model[src], tables_out, hat_in, hat_out, p->norm[src], p->norm[1 - src], p->state1, p->state2,
-                           b->pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc, p->partials, b->multi, b->n_multi, p->margin,
-                           p->optimizer, p->lr, first_opt_step + k, nullptr, 1, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr, nb ? nb->n_pairs : 0,
-                           p->bern_prob, p->slots, p->n_slots, p->seed, offset + (uint64_t)p->draws_per_batch,
-                           nb ? &p->lists[1 - cl] : nullptr, p->loss, dir.codes ? &dir : nullptr, stream);
-        if (rc) return rc;
-        src ^= 1;
-        if (has_next) cl ^= 1;
-        offset += (uint64_t)p->draws_per_batch;
-    }
-    return 0;
+        return kge_pull_step(&p->model[src], tables_out, hat_in, hat_out, p->norm[src], p->norm[1 - src], p->state1, p->state2,
+                             b->pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc, p->partials, b->multi, b->n_multi, p->margin,
+                             p->optimizer, p->lr, first_opt_step + k, nullptr, 1, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr,
+                             nb ? nb->n_pairs : 0, p->bern_prob, p->slots, p->n_slots, p->seed, next_offset,
+                             nb ? &p->lists[1 - cl] : nullptr, p->loss, dir.codes ? &dir : nullptr, stream);
+    });
 }
 
 /* ---- TransH / TransD gradients in the two-launch owner-computes form, kge_pullx.hip */
@@ -632,13 +663,7 @@ int kge_transx_grad_step(const kge_model_desc* m, const int32_t* pairs, int64_t 
         set_error("kge_transx_grad_step: bad arguments");
         return -1;
     }
-    if (next_pairs) {
-        if (next_n < 0 || !next_inv || !lists_ok(next_lists) || next_lists->count == lists->count || (slots && (n_slots & (n_slots - 1)))) {
-            set_error("kge_transx_grad_step: the next batch's sampler needs its inverse incidence map and its own list set");
-            return -1;
-        }
-        if (validate_packed_key(m, "kge_transx_grad_step")) return -1;
-    }
+    if (next_pairs && check_next_sampler("kge_transx_grad_step", m, lists, next_inv, next_n, slots, n_slots, next_lists)) return -1;
     return launch_transx_grad_step(m, pairs, n_pairs, lists, items, n_items, listed, inc, partials, multi, n_multi, margin, stage, recs,
                                    reset_lists, next_pairs, next_inv, next_n, bern_prob, slots, n_slots, seed, next_offset, next_lists, loss,
                                    (hipStream_t)stream);
@@ -653,32 +678,16 @@ int kge_transx_run(const kge_transx_plan* p, int64_t first_batch, int64_t n_step
         set_error("kge_transx_run: bad arguments");
         return -1;
     }
-    int cl = cur_list;
-    uint64_t offset = first_offset;
-    for (int64_t k = 0; k < n_steps; ++k) {
-        const kge_pull_batch* b = p->batches + first_batch + k;
-        int rc;
-        if (k == 0 && !lists_ready) {
-            rc = kge_pull_sample(b->pairs, b->inv, b->n_pairs, p->model.tot_entity, p->bern_prob, p->slots, p->n_slots, p->seed, offset,
-                                 nullptr, &p->lists[cl], stream);
-            if (rc) return rc;
-        }
-        const bool last = k + 1 == n_steps;      // (sample_after_last: as kge_pull_run)
-        const bool wrap = last && sample_after_last == 2;
-        const bool has_next = wrap || ((!last || sample_after_last == 1) && first_batch + k + 1 < p->n_batches);
-        const kge_pull_batch* nb = wrap ? p->batches : (has_next ? b + 1 : nullptr);
-        rc = kge_transx_grad_step(&p->model, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc, p->partials,
-                                  b->multi, b->n_multi, p->margin, p->stage, p->recs, 1, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr,
-                                  nb ? nb->n_pairs : 0, p->bern_prob, p->slots, p->n_slots, p->seed, offset + (uint64_t)p->draws_per_batch,
-                                  nb ? &p->lists[1 - cl] : nullptr, p->loss, stream);
+    return run_steps(run_view(p, p->model), first_batch, n_steps, cur_list, lists_ready, first_offset, sample_after_last, stream,
+                     [=](int64_t k, const kge_pull_batch* b, const kge_pull_batch* nb, int cl, uint64_t next_offset) {
+        int rc = kge_transx_grad_step(&p->model, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc,
+                                      p->partials, b->multi, b->n_multi, p->margin, p->stage, p->recs, 1, nb ? nb->pairs : nullptr,
+                                      nb ? nb->inv : nullptr, nb ? nb->n_pairs : 0, p->bern_prob, p->slots, p->n_slots, p->seed, next_offset,
+                                      nb ? &p->lists[1 - cl] : nullptr, p->loss, stream);
         if (rc) return rc;
-        rc = kge_optimizer_step(p->optimizer, p->flat_param, p->flat_grad, p->flat_state1, p->flat_state2, p->flat_numel, p->lr,
-                                first_opt_step + k, 1, nullptr, stream);
-        if (rc) return rc;
-        if (has_next) cl ^= 1;
-        offset += (uint64_t)p->draws_per_batch;
-    }
-    return 0;
+        return kge_optimizer_step(p->optimizer, p->flat_param, p->flat_grad, p->flat_state1, p->flat_state2, p->flat_numel, p->lr,
+                                  first_opt_step + k, 1, nullptr, stream);
+    });
 }
 
 /* ---- two-phase owner-computes step of the pointwise models, kge_own.hip */
@@ -702,13 +711,7 @@ int kge_own_step(const kge_model_desc* m, const int32_t* pairs, int64_t n_pairs,
         set_error("kge_own_step: bad arguments");
         return -1;
     }
-    if (next_pairs) {
-        if (next_n < 0 || !next_inv || !lists_ok(next_lists) || next_lists->count == lists->count || (slots && (n_slots & (n_slots - 1)))) {
-            set_error("kge_own_step: the next batch's sampler needs its inverse incidence map and its own list set");
-            return -1;
-        }
-        if (validate_packed_key(m, "kge_own_step")) return -1;
-    }
+    if (next_pairs && check_next_sampler("kge_own_step", m, lists, next_inv, next_n, slots, n_slots, next_lists)) return -1;
     return launch_own_step(m, pairs, n_pairs, lists, items, n_items, listed, inc, partials, dense, lmbda, reg_type, reset_lists,
                            next_pairs, next_inv, next_n, bern_prob, slots, n_slots, seed, next_offset, next_lists, loss, stage, (hipStream_t)stream);
 }
@@ -736,55 +739,36 @@ int kge_own_run(const kge_own_plan* p, int64_t first_batch, int64_t n_steps, int
         return -1;
     }
     const int dense = (p->optimizer == KGE_OPT_ADAM || p->optimizer == KGE_OPT_RMSPROP) ? 1 : 0;
-    int cl = cur_list;
-    uint64_t offset = first_offset;
-    for (int64_t k = 0; k < n_steps; ++k) {
-        const kge_pull_batch* b = p->batches + first_batch + k;
-        int rc;
-        if (k == 0 && !lists_ready) {
-            rc = kge_pull_sample(b->pairs, b->inv, b->n_pairs, p->model.tot_entity, p->bern_prob, p->slots, p->n_slots, p->seed, offset,
-                                 nullptr, &p->lists[cl], stream);
-            if (rc) return rc;
-        }
-        const bool last = k + 1 == n_steps;      // (sample_after_last: as kge_pull_run -- 1 = the following batch, 2 = batch 0 of the next epoch)
-        const bool wrap = last && sample_after_last == 2;
-        const bool has_next = wrap || ((!last || sample_after_last == 1) && first_batch + k + 1 < p->n_batches);
-        const kge_pull_batch* nb = wrap ? p->batches : (has_next ? b + 1 : nullptr);
-        if (ownx_model(p->model.model)) {
+    return run_steps(run_view(p, p->model), first_batch, n_steps, cur_list, lists_ready, first_offset, sample_after_last, stream,
+                     [=](int64_t k, const kge_pull_batch* b, const kge_pull_batch* nb, int cl, uint64_t next_offset) {
+        const int32_t* next_pairs = nb ? nb->pairs : nullptr;
+        const int32_t* next_inv = nb ? nb->inv : nullptr;
+        const int64_t next_n = nb ? nb->n_pairs : 0;
+        const kge_pull_lists* next_lists = nb ? &p->lists[1 - cl] : nullptr;
+        if (ownx_model(p->model.model))
             // ANALOGY / CP / SimplE / QuatE: the model-generic staged step (kge_ownx.hip)
-            rc = launch_ownx_step(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip,
-                                  b->inc, p->partials, b->multi, b->n_multi, dense, p->lmbda, p->reg_type, p->optimizer, p->lr,
-                                  first_opt_step + k, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr, nb ? nb->n_pairs : 0, p->bern_prob,
-                                  p->slots, p->n_slots, p->seed, offset + (uint64_t)p->draws_per_batch, nb ? &p->lists[1 - cl] : nullptr,
-                                  p->loss, p->stage, (hipStream_t)stream);
-            if (rc) return rc;
-        } else if (p->stage) {
+            return launch_ownx_step(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip,
+                                    b->inc, p->partials, b->multi, b->n_multi, dense, p->lmbda, p->reg_type, p->optimizer, p->lr,
+                                    first_opt_step + k, next_pairs, next_inv, next_n, p->bern_prob, p->slots, p->n_slots, p->seed, next_offset,
+                                    next_lists, p->loss, p->stage, (hipStream_t)stream);
+        if (p->stage) {
             // staged form: the owners apply the optimiser themselves; only rows cut across workgroups go through k_own_apply
-            rc = launch_own_step_fused(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items,
-                                       b->dense_skip, b->inc, p->partials, dense, p->lmbda, p->reg_type, p->optimizer, p->lr,
-                                       first_opt_step + k, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr, nb ? nb->n_pairs : 0,
-                                       p->bern_prob, p->slots, p->n_slots, p->seed, offset + (uint64_t)p->draws_per_batch,
-                                       nb ? &p->lists[1 - cl] : nullptr, p->loss, p->stage, (hipStream_t)stream);
-            if (rc) return rc;
-            if (b->n_multi > 0) {
-                rc = launch_own_apply(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items,
-                                      b->dense_skip, b->multi, b->n_multi, p->partials, dense, p->optimizer, p->lr, first_opt_step + k, 1,
-                                      (hipStream_t)stream);
-                if (rc) return rc;
-            }
-        } else {
-            rc = kge_own_step(&p->model, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc, p->partials,
-                              dense, p->lmbda, p->reg_type, 1, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr, nb ? nb->n_pairs : 0, p->bern_prob, p->slots,
-                              p->n_slots, p->seed, offset + (uint64_t)p->draws_per_batch, nb ? &p->lists[1 - cl] : nullptr, p->loss, nullptr, stream);
-            if (rc) return rc;
-            rc = kge_own_apply(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip,
-                               b->multi, b->n_multi, p->partials, dense, p->optimizer, p->lr, first_opt_step + k, stream);
-            if (rc) return rc;
+            int rc = launch_own_step_fused(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items,
+                                           b->dense_skip, b->inc, p->partials, dense, p->lmbda, p->reg_type, p->optimizer, p->lr,
+                                           first_opt_step + k, next_pairs, next_inv, next_n, p->bern_prob, p->slots, p->n_slots, p->seed,
+                                           next_offset, next_lists, p->loss, p->stage, (hipStream_t)stream);
+            if (rc || b->n_multi <= 0) return rc;
+            return launch_own_apply(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items,
+                                    b->dense_skip, b->multi, b->n_multi, p->partials, dense, p->optimizer, p->lr, first_opt_step + k, 1,
+                                    (hipStream_t)stream);
         }
-        if (has_next) cl ^= 1;
-        offset += (uint64_t)p->draws_per_batch;
-    }
-    return 0;
+        int rc = kge_own_step(&p->model, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc, p->partials,
+                              dense, p->lmbda, p->reg_type, 1, next_pairs, next_inv, next_n, p->bern_prob, p->slots, p->n_slots, p->seed,
+                              next_offset, next_lists, p->loss, nullptr, stream);
+        if (rc) return rc;
+        return kge_own_apply(&p->model, p->state1, p->state2, b->pairs, b->n_pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip,
+                             b->multi, b->n_multi, p->partials, dense, p->optimizer, p->lr, first_opt_step + k, stream);
+    });
 }
 
 int kge_head_1n_forward(const float* x, int64_t batch, int32_t dim, const float* ent, int64_t tot_entity, const float* bias,

@@ -1016,6 +1016,30 @@ class PullDirection:
         self.c = L.PullDirection(self.codes.data_ptr(), self.recs.data_ptr(), int(n_pairs), 0)
 
 
+def _next_sampler_args(sample_next):
+    """The nine ride-along sampler arguments of kge_pull_step / kge_transx_grad_step / kge_own_step, from
+    sample_next = (next_pairs, next_inv, bern_prob, slots, seed, next_offset, next_lists) or None (no sampler rides along)."""
+    if sample_next is None:
+        return (None, None, 0, None, None, 0, 0, 0, None)
+    npairs, ninv, bern, slots, seed, noff, nlists = sample_next
+    return (_i32(npairs, "next_pairs"), _i32(ninv, "next_inv"), npairs.shape[0], _dev(bern, torch.float32, "bern_prob") if bern is not None else None,
+            ctypes.c_void_p(slots.data_ptr()) if slots is not None else None, slots.numel() if slots is not None else 0,
+            int(seed) & (2 ** 64 - 1), int(noff) & (2 ** 64 - 1), ctypes.byref(nlists.c))
+
+
+def _prepared(fn, name, args, off_idx, keep):
+    """Marshal once, call many times: call(next_offset) repeats fn(*args) with only args[off_idx] -- the ride-along sampler's
+    Philox offset, the one argument that differs from epoch to epoch -- replaced.  `keep` holds the arguments' storage alive."""
+    args = list(args)
+
+    def call(next_offset=None):
+        if next_offset is not None:
+            args[off_idx] = int(next_offset) & (2 ** 64 - 1)
+        L.check(fn(*args, _stream()), name)
+    call.keep = keep
+    return call
+
+
 def pull_step(desc_in, tables_out, hat_in, hat_out, norm_in, norm_out, state1, state2, pairs, lists, items, inc, partials, multi,
               margin, optimizer, lr, step, loss_buf, reset_lists=True, dev_hyper=None, run_finish=True, sample_next=None,
               dense_skip=None, prepare_only=False, direction=None):
@@ -1027,13 +1051,7 @@ def pull_step(desc_in, tables_out, hat_in, hat_out, norm_in, norm_out, state1, s
     to, s1, s2, hi, ho = _ptr_pair(tables_out), _ptr_pair(state1), _ptr_pair(state2), _ptr_pair(hat_in), _ptr_pair(hat_out)
     # run_finish=False (timing only): the owners still write their partial sums, the finishing launch is skipped
     n_multi = multi.shape[0] if (multi is not None and run_finish) else 0
-    if sample_next is not None:
-        npairs, ninv, bern, slots, seed, noff, nlists = sample_next
-        nx = (_i32(npairs, "next_pairs"), _i32(ninv, "next_inv"), npairs.shape[0], _dev(bern, torch.float32, "bern_prob") if bern is not None else None,
-              ctypes.c_void_p(slots.data_ptr()) if slots is not None else None, slots.numel() if slots is not None else 0,
-              int(seed) & (2 ** 64 - 1), int(noff) & (2 ** 64 - 1), ctypes.byref(nlists.c))
-    else:
-        nx = (None, None, 0, None, None, 0, 0, 0, None)
+    nx = _next_sampler_args(sample_next)
     args = (
         ctypes.byref(desc_in), ctypes.addressof(to), ctypes.addressof(hi), ctypes.addressof(ho) if hat_out is not None else None,
         _dev(norm_in, torch.float32, "norm_in"),
@@ -1047,17 +1065,8 @@ def pull_step(desc_in, tables_out, hat_in, hat_out, norm_in, norm_out, state1, s
         *nx, _dev(loss_buf, torch.float32, "loss"), ctypes.byref(direction.c) if direction is not None else None)
     keep = (desc_in, to, hi, ho, s1, s2, tables_out, hat_in, hat_out, norm_in, norm_out, state1, state2, pairs, lists, items, inc,
             partials, multi, loss_buf, dense_skip, sample_next, direction)
-    if prepare_only:   # marshal once, call many times (a data-parallel step runs this launch between two collectives:
-        fn = L.load().kge_pull_step                                   # host time per step matters there)
-        argl = list(args)
-        off_idx = len(argl) - 4      # next_offset: the one argument that differs from epoch to epoch (Philox counters advance)
-
-        def call(next_offset=None):
-            if next_offset is not None:
-                argl[off_idx] = int(next_offset) & (2 ** 64 - 1)
-            L.check(fn(*argl, _stream()), "kge_pull_step")
-        call.keep = keep
-        return call
+    if prepare_only:   # (a data-parallel step runs this launch between two collectives: host time per step matters there)
+        return _prepared(L.load().kge_pull_step, "kge_pull_step", args, len(args) - 4, keep)
     L.check(L.load().kge_pull_step(*args, _stream()), "kge_pull_step")
 
 
@@ -1106,6 +1115,42 @@ def pull_list_set_bytes(batch_size, tot_entity):
     return int(batch_size) * (4 + 4 + 3 * 16) + int(tot_entity) * (4 + 4 + L.PULL_BUCKET * 4 + L.PULL_BUCKET * 16)
 
 
+def _plan_batches(index):
+    """The host array of struct kge_pull_batch over every batch of an incidence index."""
+    batches = (L.PullBatch * index.n_batches)()
+    for b in range(index.n_batches):
+        pairs, inc, items, multi = index.batch(b)
+        skip = index.skip(b)
+        batches[b] = L.PullBatch(pairs.data_ptr(), items.data_ptr() if items.shape[0] else None, items.shape[0],
+                                 skip.data_ptr() if skip is not None else None, inc.data_ptr(), index.inv(b).data_ptr(),
+                                 multi.data_ptr() if multi.shape[0] else None, multi.shape[0], pairs.shape[0])
+    return batches
+
+
+def _plan_common(c, lists, batches, index, bern, slots, seed, draws_per_batch, loss_buf):
+    """The fields kge_pull_plan, kge_transx_plan and kge_own_plan share by name: list sets, batches, sampler, loss."""
+    for half in (0, 1):
+        c.lists[half] = lists[half].c
+    c.batches = ctypes.cast(batches, ctypes.POINTER(L.PullBatch))
+    c.n_batches = index.n_batches
+    c.bern_prob = bern.data_ptr() if bern is not None else None
+    c.slots = slots.data_ptr() if slots is not None else None
+    c.n_slots = slots.numel() if slots is not None else 0
+    c.seed = int(seed) & (2 ** 64 - 1)
+    c.draws_per_batch = int(draws_per_batch)
+    c.loss = loss_buf.data_ptr()
+
+
+def _run(fn, name, c, *args):
+    """kge_pull_run / kge_transx_run / kge_own_run on plan struct `c`:
+    args = (first_batch, n_steps, [src_half,] cur_list, lists_ready, first_opt_step, first_offset, sample_after_last)."""
+    *head, lists_ready, first_opt_step, first_offset, sample_after_last = args
+    rc = fn(ctypes.byref(c), *map(int, head), 1 if lists_ready else 0, int(first_opt_step), int(first_offset) & (2 ** 64 - 1),
+            int(sample_after_last), _stream())
+    if rc:
+        L.check(rc, name)
+
+
 class PullPlan:
     """struct kge_pull_plan for a (model, index, state) triple: everything that does not change from step to step,
     marshalled once.  `run` enqueues a whole sequence of steps with ONE foreign call (the per-step work is ~35 us of GPU
@@ -1118,39 +1163,23 @@ class PullPlan:
         for half in (0, 1):
             c.model[half] = make_desc(model_name, tables[half], None, tot_entity=tot_entity, tot_relation=tot_relation, **desc_kwargs)
             c.norm[half] = norms[half].data_ptr()
-            c.lists[half] = lists[half].c
             for t in (0, 1):
                 c.hat[half][t] = hats[half][t].data_ptr()
         for t in (0, 1):
             c.state1[t] = state1[t].data_ptr() if state1 is not None else None
             c.state2[t] = state2[t].data_ptr() if state2 is not None else None
-        self.batches = (L.PullBatch * index.n_batches)()
-        for b in range(index.n_batches):
-            pairs, inc, items, multi = index.batch(b)
-            skip = index.skip(b)
-            self.batches[b] = L.PullBatch(pairs.data_ptr(), items.data_ptr(), items.shape[0],
-                                          skip.data_ptr() if skip is not None else None, inc.data_ptr(), index.inv(b).data_ptr(),
-                                          multi.data_ptr() if multi.shape[0] else None, multi.shape[0], pairs.shape[0])
-        c.batches = ctypes.cast(self.batches, ctypes.POINTER(L.PullBatch))
-        c.n_batches = index.n_batches
+        self.batches = _plan_batches(index)
+        _plan_common(c, lists, self.batches, index, bern, slots, seed, draws_per_batch, loss_buf)
         c.partials = partials.data_ptr()
         c.margin, c.optimizer, c.lr = float(margin), OPTIMIZER_IDS[optimizer], float(lr)
-        c.bern_prob = bern.data_ptr() if bern is not None else None
-        c.slots = slots.data_ptr() if slots is not None else None
-        c.n_slots = slots.numel() if slots is not None else 0
-        c.seed = int(seed) & (2 ** 64 - 1)
-        c.draws_per_batch = int(draws_per_batch)
-        c.loss = loss_buf.data_ptr()
         if direction is not None:      # two-phase steps (kge_pull_run fills n_pairs per batch)
             c.direction = direction.c
         self.c = c
         self.fn = L.load().kge_pull_run
 
     def run(self, first_batch, n_steps, src_half, cur_list, lists_ready, first_opt_step, first_offset, sample_after_last):
-        rc = self.fn(ctypes.byref(self.c), int(first_batch), int(n_steps), int(src_half), int(cur_list), 1 if lists_ready else 0,
-                     int(first_opt_step), int(first_offset) & (2 ** 64 - 1), int(sample_after_last), _stream())
-        if rc:
-            L.check(rc, "kge_pull_run")
+        _run(self.fn, "kge_pull_run", self.c, first_batch, n_steps, src_half, cur_list, lists_ready, first_opt_step, first_offset,
+             sample_after_last)
 
 
 # ---------------------------------------------------------------------------- TransH / TransD gradients, two-launch owner-computes form
@@ -1178,13 +1207,7 @@ def transx_grad_step(desc, pairs, lists, items, listed, inc, partials, multi, ma
     """kge_transx_grad_step: the TransH / TransD gradients of one batch into desc's dense gradient tables, no float atomics
     (csrc/kge_pullx.hip).  sample_next as pull_step."""
     n_multi = multi.shape[0] if multi is not None else 0
-    if sample_next is not None:
-        npairs, ninv, bern, slots, seed, noff, nlists = sample_next
-        nx = (_i32(npairs, "next_pairs"), _i32(ninv, "next_inv"), npairs.shape[0], _dev(bern, torch.float32, "bern_prob") if bern is not None else None,
-              ctypes.c_void_p(slots.data_ptr()) if slots is not None else None, slots.numel() if slots is not None else 0,
-              int(seed) & (2 ** 64 - 1), int(noff) & (2 ** 64 - 1), ctypes.byref(nlists.c))
-    else:
-        nx = (None, None, 0, None, None, 0, 0, 0, None)
+    nx = _next_sampler_args(sample_next)
     args = [ctypes.byref(desc), _i32(pairs, "pairs"), pairs.shape[0], ctypes.byref(lists.c),
             _i32(items, "items") if items.shape[0] else None, items.shape[0], _i32(listed, "listed") if listed is not None else None,
             _i32(inc, "inc"), _dev(partials, torch.float32, "partials"), _i32(multi, "multi") if n_multi else None, n_multi,
@@ -1192,15 +1215,8 @@ def transx_grad_step(desc, pairs, lists, items, listed, inc, partials, multi, ma
             1 if reset_lists else 0, *nx, _dev(loss_buf, torch.float32, "loss")]
     fn = L.load().kge_transx_grad_step
     if prepare_only:
-        off_idx = len(args) - 3      # next_offset: the one argument that changes from epoch to epoch
-        keep = (desc, pairs, lists, items, listed, inc, partials, multi, scratch, loss_buf, sample_next)
-
-        def call(next_offset=None):
-            if next_offset is not None:
-                args[off_idx] = int(next_offset) & (2 ** 64 - 1)
-            L.check(fn(*args, _stream()), "kge_transx_grad_step")
-        call.keep = keep
-        return call
+        return _prepared(fn, "kge_transx_grad_step", args, len(args) - 3,
+                         (desc, pairs, lists, items, listed, inc, partials, multi, scratch, loss_buf, sample_next))
     L.check(fn(*args, _stream()), "kge_transx_grad_step")
 
 
@@ -1212,17 +1228,8 @@ class TransXPlan:
         self.keep = (desc, flat, lists, index, partials, scratch, loss_buf, bern, slots)
         c = L.TransXPlanC()
         ctypes.memmove(ctypes.byref(c.model), ctypes.byref(desc), ctypes.sizeof(L.ModelDesc))
-        for half in (0, 1):
-            c.lists[half] = lists[half].c
-        self.batches = (L.PullBatch * index.n_batches)()
-        for b in range(index.n_batches):
-            pairs, inc, items, multi = index.batch(b)
-            skip = index.skip(b)
-            self.batches[b] = L.PullBatch(pairs.data_ptr(), items.data_ptr() if items.shape[0] else None, items.shape[0],
-                                          skip.data_ptr() if skip is not None else None, inc.data_ptr(), index.inv(b).data_ptr(),
-                                          multi.data_ptr() if multi.shape[0] else None, multi.shape[0], pairs.shape[0])
-        c.batches = ctypes.cast(self.batches, ctypes.POINTER(L.PullBatch))
-        c.n_batches = index.n_batches
+        self.batches = _plan_batches(index)
+        _plan_common(c, lists, self.batches, index, bern, slots, seed, draws_per_batch, loss_buf)
         c.partials, c.stage, c.recs = partials.data_ptr(), scratch.stage.data_ptr(), scratch.recs.data_ptr()
         c.margin = float(margin)
         c.flat_param, c.flat_grad = flat.param.data_ptr(), flat.grad.data_ptr()
@@ -1230,20 +1237,11 @@ class TransXPlan:
         c.flat_state2 = flat.state2.data_ptr() if flat.state2 is not None else None
         c.flat_numel = flat.param.numel()
         c.optimizer, c.lr = OPTIMIZER_IDS[optimizer], float(lr)
-        c.bern_prob = bern.data_ptr() if bern is not None else None
-        c.slots = slots.data_ptr() if slots is not None else None
-        c.n_slots = slots.numel() if slots is not None else 0
-        c.seed = int(seed) & (2 ** 64 - 1)
-        c.draws_per_batch = int(draws_per_batch)
-        c.loss = loss_buf.data_ptr()
         self.c = c
         self.fn = L.load().kge_transx_run
 
-    def run(self, first_batch, n_steps, cur_list, lists_ready, first_opt_step, first_offset, sample_after_last):
-        rc = self.fn(ctypes.byref(self.c), int(first_batch), int(n_steps), int(cur_list), 1 if lists_ready else 0,
-                     int(first_opt_step), int(first_offset) & (2 ** 64 - 1), int(sample_after_last), _stream())
-        if rc:
-            L.check(rc, "kge_transx_run")
+    def run(self, *args):   # (first_batch, n_steps, cur_list, lists_ready, first_opt_step, first_offset, sample_after_last)
+        _run(self.fn, "kge_transx_run", self.c, *args)
 
 
 # ---------------------------------------------------------------------------- two-phase owner-computes step (pointwise models)
@@ -1270,13 +1268,7 @@ def _ptr_array(tensors, n=L.KGE_MAX_TABLES):
 def own_step(desc, pairs, lists, items, listed, inc, partials, dense, lmbda, reg_type, loss_buf, reset_lists=True, sample_next=None,
              stage=None):
     """Phase 1 (kge_own_step): gradient rows of every touched parameter row into desc.grads, no atomics."""
-    if sample_next is not None:
-        npairs, ninv, bern, slots, seed, noff, nlists = sample_next
-        nx = (_i32(npairs, "next_pairs"), _i32(ninv, "next_inv"), npairs.shape[0], _dev(bern, torch.float32, "bern_prob") if bern is not None else None,
-              ctypes.c_void_p(slots.data_ptr()) if slots is not None else None, slots.numel() if slots is not None else 0,
-              int(seed) & (2 ** 64 - 1), int(noff) & (2 ** 64 - 1), ctypes.byref(nlists.c))
-    else:
-        nx = (None, None, 0, None, None, 0, 0, 0, None)
+    nx = _next_sampler_args(sample_next)
     L.check(L.load().kge_own_step(ctypes.byref(desc), _i32(pairs, "pairs"), pairs.shape[0], ctypes.byref(lists.c), _i32(items, "items"),
                                   items.shape[0], _i32(listed, "listed") if listed is not None else None, _i32(inc, "inc"),
                                   _dev(partials, torch.float32, "partials"), 1 if dense else 0, float(lmbda), int(reg_type),
@@ -1309,34 +1301,16 @@ class OwnPlan:
             c.state1[i] = t.data_ptr() if t is not None else None
         for i, t in enumerate(state2 or ()):
             c.state2[i] = t.data_ptr() if t is not None else None
-        for half in (0, 1):
-            c.lists[half] = lists[half].c
-        self.batches = (L.PullBatch * index.n_batches)()
-        for b in range(index.n_batches):
-            pairs, inc, items, multi = index.batch(b)
-            skip = index.skip(b)
-            self.batches[b] = L.PullBatch(pairs.data_ptr(), items.data_ptr(), items.shape[0],
-                                          skip.data_ptr() if skip is not None else None, inc.data_ptr(), index.inv(b).data_ptr(),
-                                          multi.data_ptr() if multi.shape[0] else None, multi.shape[0], pairs.shape[0])
-        c.batches = ctypes.cast(self.batches, ctypes.POINTER(L.PullBatch))
-        c.n_batches = index.n_batches
+        self.batches = _plan_batches(index)
+        _plan_common(c, lists, self.batches, index, bern, slots, seed, draws_per_batch, loss_buf)
         c.partials = partials.data_ptr()
         c.optimizer, c.lr, c.lmbda, c.reg_type = OPTIMIZER_IDS[optimizer], float(lr), float(lmbda), int(reg_type)
-        c.bern_prob = bern.data_ptr() if bern is not None else None
-        c.slots = slots.data_ptr() if slots is not None else None
-        c.n_slots = slots.numel() if slots is not None else 0
-        c.seed = int(seed) & (2 ** 64 - 1)
-        c.draws_per_batch = int(draws_per_batch)
-        c.loss = loss_buf.data_ptr()
         c.stage = stage.data_ptr() if stage is not None else None
         self.c = c
         self.fn = L.load().kge_own_run
 
-    def run(self, first_batch, n_steps, cur_list, lists_ready, first_opt_step, first_offset, sample_after_last):
-        rc = self.fn(ctypes.byref(self.c), int(first_batch), int(n_steps), int(cur_list), 1 if lists_ready else 0,
-                     int(first_opt_step), int(first_offset) & (2 ** 64 - 1), int(sample_after_last), _stream())
-        if rc:
-            L.check(rc, "kge_own_run")
+    def run(self, *args):   # (first_batch, n_steps, cur_list, lists_ready, first_opt_step, first_offset, sample_after_last)
+        _run(self.fn, "kge_own_run", self.c, *args)
 
 
 # ---------------------------------------------------------------------------- 1-N scoring head (projection models)

@@ -88,6 +88,10 @@ class FlatState:
         self.state2 = torch.zeros_like(self.param_shard) if optimizer == "adam" else None
         self.step = 0
 
+    def views_of(self, buf):
+        """`buf`, a buffer laid out like `param` (gradient rows, optimiser state), cut into the tables' shapes; None stays None."""
+        return None if buf is None else [buf[o:o + v.numel()].view_as(v) for o, v in zip(self.offsets, self.views)]
+
     def optimizer_step_advance(self, lr, hyper, cursor, next_cursor, next_hyper, batch_stride, n_batches, draws):
         self.step += 1
         self.K.optimizer_step_advance(self.optimizer, self.param_shard, self.grad_shard, self.state1, self.state2, lr, hyper,
@@ -144,7 +148,52 @@ class FlatState:
                               zero_grad=True, dev_hyper=dev_hyper)
 
 
-class PullState:
+class OwnerRunState:
+    """The epoch cursor of the owner-computes runs (Trainer paths `pull`, `own`, `transx`; the native loop is run_steps in
+    csrc/kge_api.hip).  Two sampler list sets: the step on batch k consumes `lists[cur_list]` while the sampler of batch k + 1,
+    riding in the same launch, fills the other.  `ready` = (batch index, Philox offset) the current set was sampled for, or None
+    when it is cleared."""
+
+    def __init__(self, lists):
+        self.lists, self.cur_list, self.ready = lists, 0, None
+
+    def run_steps(self, gen, index, n_steps, flat, run):
+        """The generator's next n_steps batches, enqueued by one native call:
+        run(first_batch, n_steps, cur_list, lists_ready, first_opt_step, first_offset, sample_after_last)."""
+        if n_steps <= 0:
+            return
+        first, offset = gen._batch_idx, gen._draws
+        if gen._pending < n_steps or first + n_steps > index.n_batches:
+            raise StopIteration
+        draws = n_steps * index.batch_size * gen.neg_rate
+        gen._batch_idx += n_steps
+        gen._pending -= n_steps
+        gen._draws += draws
+        ready = self.ready == (first, offset)
+        if not ready and self.ready is not None:   # a sampler rode along for a batch that is not the next one: discard
+            self.lists[self.cur_list].clear()
+        # the last step carries the sampler of the following batch: the next one of this epoch (1), or -- at the end of the
+        # epoch -- batch 0 of the next epoch (2: the permutation is walked again and the Philox counters keep counting, so the
+        # draw is exactly the one the next epoch's first step would make; if no epoch follows, the unused set is discarded by
+        # the `ready` check above).  Saves the stand-alone sampler launch (12 us at B = 32768) at every epoch boundary.
+        after = 1 if (gen._pending > 0 and first + n_steps < index.n_batches) else (2 if gen._pending == 0 else 0)
+        run(first, n_steps, self.cur_list, ready, flat.step + 1, offset, after)
+        flat.step += n_steps
+        carried = n_steps - 1 + (1 if after else 0)            # number of ride-along samplers = list-set flips
+        self.cur_list ^= carried & 1
+        self.ready = (first + n_steps if after == 1 else 0, offset + draws) if after else None
+
+
+class OwnerState(OwnerRunState):
+    """State of the `own` and `transx` paths: the index it was built for, the run plan and the device buffers the plan points into."""
+
+    def __init__(self, index, lists, plan, **buffers):
+        super().__init__(lists)
+        self.index, self.plan = index, plan
+        self.__dict__.update(buffers)
+
+
+class PullState(OwnerRunState):
     """Device state of the owner-computes training step (csrc/kge_pull.hip): the second half of the double-buffered
     tables, the row norms of both halves and the per-step sampler lists.  `cur` = which half holds the current tables
     (0 = FlatState.param, i.e. the storage behind the model's nn.Parameters)."""
@@ -172,16 +221,18 @@ class PullState:
         self.E, self.R = E, R
         self.norms = [torch.empty(E + R, dtype=torch.float32, device=dev) for _ in range(2)]
         self.batch_size = batch_size
-        # two sampler list sets: the step on batch k consumes one while the sampler of batch k+1, riding in the same
-        # launch, fills the other.  `ready` = (batch index, Philox offset) the current set was sampled for.
-        self.lists = [K.PullListSet(batch_size, E, dev) for _ in range(2)]
-        self.cur_list = 0
-        self.ready = None
+        super().__init__([K.PullListSet(batch_size, E, dev) for _ in range(2)])
         self.calls = {}   # prepared kge_pull_step calls of the data-parallel gradient step
         self.partials = torch.empty(max(1, max_slots) * K.pull_partial_stride(d), dtype=torch.float32, device=dev)
         # two-phase ("staged direction") form: every pair evaluated once (k_pull_eval), the owners sum its record
         self.direction = K.PullDirection(batch_size, d, bool(getattr(model, "l1_flag", True)), dev) if two_phase else None
         self.cur = 0
+
+    def run_steps(self, gen, index, n_steps, flat, run):
+        """As OwnerRunState.run_steps; `run` also takes, after n_steps, the table half the first step reads (the halves alternate)."""
+        first = gen._batch_idx
+        super().run_steps(gen, index, n_steps, flat, lambda b, n, *rest: run(b, n, self.cur, *rest))
+        self.cur ^= (gen._batch_idx - first) & 1
 
     def sync_in(self):
         """(Re)derive the row norms from the tables the model currently holds (they may have been set from outside)."""

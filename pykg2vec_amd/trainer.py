@@ -24,7 +24,7 @@ from .evaluator import Evaluator
 from .generator import Generator
 
 
-from .state import FlatState, PatienceStopper, PullState, _log   # noqa: F401  (re-exported: tests and the graft import them from here)
+from .state import FlatState, OwnerState, PatienceStopper, PullState, _log   # noqa: F401  (re-exported: tests and the graft import them from here)
 
 
 class Trainer:
@@ -416,32 +416,7 @@ class Trainer:
     def _pull_steps(self, n_steps):
         """The next n_steps steps of the current epoch, enqueued by one native call (kge_pull_run)."""
         ps, idx = self._pull_state()
-        gen = self.generator
-        B = idx.batch_size
-        if n_steps <= 0:
-            return
-        first = gen._batch_idx
-        if gen._pending < n_steps or first + n_steps > idx.n_batches:
-            raise StopIteration
-        offset = gen._draws
-        gen._batch_idx += n_steps
-        gen._pending -= n_steps
-        gen._draws += n_steps * B * gen.neg_rate
-        ready = ps.ready == (first, offset)
-        if not ready and ps.ready is not None:   # a sampler rode along for a batch that is not the next one: discard
-            ps.lists[ps.cur_list].clear()
-        # the last step carries the sampler of the following batch: the next one of this epoch (1), or -- at the end of the
-        # epoch -- batch 0 of the next epoch (2: the permutation is walked again and the Philox counters keep counting, so the
-        # draw is exactly the one the next epoch's first step would make; if no epoch follows, the unused set is discarded by
-        # the `ready` check above).  Saves the stand-alone sampler launch (12 us at B = 32768) at every epoch boundary.
-        after = 1 if (gen._pending > 0 and first + n_steps < idx.n_batches) else (2 if gen._pending == 0 else 0)
-        ps.plan.run(first, n_steps, ps.cur, ps.cur_list, ready, self.flat.step + 1, offset, after)
-        self.flat.step += n_steps
-        carried = n_steps - 1 + (1 if after else 0)            # number of ride-along samplers = list-set flips
-        ps.cur ^= n_steps & 1
-        ps.cur_list ^= carried & 1
-        next_batch = first + n_steps if after == 1 else 0
-        ps.ready = (next_batch, offset + n_steps * B * gen.neg_rate) if after else None
+        ps.run_steps(self.generator, idx, n_steps, self.flat, ps.plan.run)
 
     def pull_step_explicit(self, ph, pr, pt, nh, nr, nt, segment=None, compact=None):
         """The owner-computes step on an explicit batch (positives + given negatives, neg_rate 1): the incidence index
@@ -506,15 +481,12 @@ class Trainer:
         idx = gen.pull_index(groups_per_block=K.own_groups_per_block(name, self.model.hidden_size),
                              compact=None if self._own_dense() else True)
         st = getattr(self, "_own", None)
-        if st is None or st["index"] is not idx:
+        if st is None or st.index is not idx:
             dev = flat.param.device
             generic = name in self.OWN_GENERIC_MODELS     # (csrc/kge_ownx.hip: owners apply in place, no gradient rows are kept)
             gbuf = None if generic else torch.empty_like(flat.param)      # gradient rows (only the touched ones are ever written / read)
-            off = [v.data_ptr() - flat.param.data_ptr() for v in flat.views]
-            view = lambda buf: [buf[o // 4:o // 4 + v.numel()].view_as(v) for o, v in zip(off, flat.views)]
-            desc = self.model.make_desc(flat.views, None if generic else view(gbuf))
-            s1 = view(flat.state1) if flat.state1 is not None else None
-            s2 = view(flat.state2) if flat.state2 is not None else None
+            desc = self.model.make_desc(flat.views, flat.views_of(gbuf))
+            s1, s2 = flat.views_of(flat.state1), flat.views_of(flat.state2)
             lists = [K.PullListSet(idx.batch_size, cfg.tot_entity, dev) for _ in range(2)]
             stride = K.own_partial_stride(name, self.model.hidden_size)
             partials = torch.empty(max(1, idx.max_slots) * stride, dtype=torch.float32, device=dev)
@@ -526,34 +498,13 @@ class Trainer:
             plan = K.OwnPlan(desc, s1, s2, lists, idx, partials, cfg.optimizer, cfg.learning_rate, self.model.kernel_lmbda(),
                              self.model.kernel_reg_type(), self.loss_buf, gen.bern, gen.slots, gen.seed, idx.batch_size * gen.neg_rate,
                              stage=stage)
-            st = self._own = dict(index=idx, gbuf=gbuf, desc=desc, s1=s1, s2=s2, lists=lists, partials=partials, plan=plan,
-                                  cur_list=0, ready=None, stage=stage)
+            st = self._own = OwnerState(idx, lists, plan, gbuf=gbuf, desc=desc, s1=s1, s2=s2, partials=partials, stage=stage)
         return st
 
     def _own_steps(self, n_steps):
         """The next n_steps steps of the current epoch, enqueued by one native call (kge_own_run)."""
-        if n_steps <= 0:
-            return
         st = self._own_state()
-        gen, idx = self.generator, st["index"]
-        B = idx.batch_size
-        first = gen._batch_idx
-        if gen._pending < n_steps or first + n_steps > idx.n_batches:
-            raise StopIteration
-        offset = gen._draws
-        gen._batch_idx += n_steps
-        gen._pending -= n_steps
-        gen._draws += n_steps * B * gen.neg_rate
-        ready = st["ready"] == (first, offset)
-        if not ready and st["ready"] is not None:   # a sampler rode along for a batch that is not the next one: discard
-            st["lists"][st["cur_list"]].clear()
-        # (as _pull_steps: 1 = the next batch of this epoch, 2 = batch 0 of the next epoch rides in the epoch's last step)
-        after = 1 if (gen._pending > 0 and first + n_steps < idx.n_batches) else (2 if gen._pending == 0 else 0)
-        st["plan"].run(first, n_steps, st["cur_list"], ready, self.flat.step + 1, offset, after)
-        self.flat.step += n_steps
-        carried = n_steps - 1 + (1 if after else 0)
-        st["cur_list"] ^= carried & 1
-        st["ready"] = ((first + n_steps if after == 1 else 0), offset + n_steps * B * gen.neg_rate) if after else None
+        st.run_steps(self.generator, st.index, n_steps, self.flat, st.plan.run)
 
     def own_step_explicit(self, h, r, t, y):
         """The two-phase step on an explicit pointwise batch in the sampler's layout for neg_rate 1 (rows 2i = positive i, 2i+1 = its
@@ -573,10 +524,8 @@ class Trainer:
         dev = flat.param.device
         lists = K.PullListSet(len(pos), cfg.tot_entity, dev)
         K.pull_lists_explicit(pairs, idx.inv(0), h[1::2].contiguous(), t[1::2].contiguous(), lists)
-        gbuf = torch.empty_like(flat.param)
-        off = [v.data_ptr() - flat.param.data_ptr() for v in flat.views]
-        view = lambda buf: [buf[o // 4:o // 4 + v.numel()].view_as(v) for o, v in zip(off, flat.views)]
-        gviews = view(gbuf)
+        gviews = flat.views_of(torch.empty_like(flat.param))
+        s1, s2 = flat.views_of(flat.state1), flat.views_of(flat.state2)
         desc = K.make_desc(name, flat.views, gviews, tot_entity=cfg.tot_entity, tot_relation=cfg.tot_relation, **self.model.desc_kwargs())
         stride = K.own_partial_stride(name, self.model.hidden_size)
         partials = torch.empty(max(1, idx.max_slots) * stride, dtype=torch.float32, device=dev)
@@ -585,18 +534,16 @@ class Trainer:
                  if (staged is None or staged) else None)
         if name in self.OWN_GENERIC_MODELS:     # the model-generic step exists as a run only: a one-batch plan, lists given
             desc = self.model.make_desc(flat.views, gviews)
-            plan = K.OwnPlan(desc, view(flat.state1) if flat.state1 is not None else None,
-                             view(flat.state2) if flat.state2 is not None else None, [lists, K.PullListSet(len(pos), cfg.tot_entity, dev)],
-                             idx, partials, cfg.optimizer, cfg.learning_rate, self.model.kernel_lmbda(), self.model.kernel_reg_type(),
-                             self.loss_buf, None, None, 0, len(pos), stage=stage)
+            plan = K.OwnPlan(desc, s1, s2, [lists, K.PullListSet(len(pos), cfg.tot_entity, dev)], idx, partials, cfg.optimizer,
+                             cfg.learning_rate, self.model.kernel_lmbda(), self.model.kernel_reg_type(), self.loss_buf, None, None, 0,
+                             len(pos), stage=stage)
             flat.step += 1
             plan.run(0, 1, 0, True, flat.step, 0, 0)
             return None
         K.own_step(desc, pairs, lists, items, idx.skip(0), inc, partials, dense, self.model.kernel_lmbda(), self.model.kernel_reg_type(),
                    self.loss_buf, reset_lists=False, stage=stage)
         flat.step += 1
-        K.own_apply(desc, view(flat.state1) if flat.state1 is not None else None, view(flat.state2) if flat.state2 is not None else None,
-                    pairs, lists, items, idx.skip(0), multi, partials, dense, cfg.optimizer, cfg.learning_rate, flat.step)
+        K.own_apply(desc, s1, s2, pairs, lists, items, idx.skip(0), multi, partials, dense, cfg.optimizer, cfg.learning_rate, flat.step)
         return gviews
 
     # ------------------------------------------------------------------ TransH / TransD: gradients without float atomics
@@ -627,40 +574,21 @@ class Trainer:
         d = self.model.parameter_list[0].weight.shape[1]
         # (compact = None: the index lists only the touched rows when the batch touches a small part of the tables, else every row)
         idx = self.generator.pull_index(groups_per_block=K.transx_groups_per_block(d), segment=32)
-        if st is None or st["index"] is not idx:
-            dev = self.flat.param.device
-            E = int(self.config.tot_entity)
-            st = self._transx = {
-                "index": idx, "lists": [K.PullListSet(idx.batch_size, E, dev) for _ in range(2)], "cur_list": 0, "ready": None,
-                "partials": torch.empty(max(1, idx.max_slots) * K.transx_partial_stride(d), dtype=torch.float32, device=dev),
-                "scratch": K.TransXScratch(self.model.kernel_name, d, idx.batch_size, dev), "plan": None}
+        if st is None or st.index is not idx:
+            gen, cfg, dev = self.generator, self.config, self.flat.param.device
+            lists = [K.PullListSet(idx.batch_size, int(cfg.tot_entity), dev) for _ in range(2)]
+            partials = torch.empty(max(1, idx.max_slots) * K.transx_partial_stride(d), dtype=torch.float32, device=dev)
+            scratch = K.TransXScratch(self.model.kernel_name, d, idx.batch_size, dev)
+            plan = K.TransXPlan(self._desc, self.flat, lists, idx, partials, scratch, cfg.margin, cfg.optimizer, cfg.learning_rate,
+                                self.loss_buf, gen.bern, gen.slots, gen.seed, idx.batch_size * gen.neg_rate)
+            st = self._transx = OwnerState(idx, lists, plan, partials=partials, scratch=scratch)
         return st
 
     def _transx_steps(self, n_steps):
         """The next n_steps steps of the current epoch, enqueued by one native call (kge_transx_run: per step evaluate pairs /
         owners sum / finish, with the next batch's sampler riding along, then the dense optimiser over the flat buffers)."""
         st = self._transx_state()
-        gen, cfg, idx = self.generator, self.config, st["index"]
-        B = idx.batch_size
-        if st.get("plan") is None:
-            st["plan"] = K.TransXPlan(self._desc, self.flat, st["lists"], idx, st["partials"], st["scratch"], cfg.margin, cfg.optimizer,
-                                      cfg.learning_rate, self.loss_buf, gen.bern, gen.slots, gen.seed, B * gen.neg_rate)
-        first = gen._batch_idx
-        if gen._pending < n_steps or first + n_steps > idx.n_batches:
-            raise StopIteration
-        offset = gen._draws
-        gen._batch_idx += n_steps
-        gen._pending -= n_steps
-        gen._draws += n_steps * B * gen.neg_rate
-        ready = st["ready"] == (first, offset)
-        if not ready and st["ready"] is not None:   # a sampler rode along for a batch that is not the next one: discard
-            st["lists"][st["cur_list"]].clear()
-        after = 1 if (gen._pending > 0 and first + n_steps < idx.n_batches) else (2 if gen._pending == 0 else 0)
-        st["plan"].run(first, n_steps, st["cur_list"], ready, self.flat.step + 1, offset, after)
-        self.flat.step += n_steps
-        carried = n_steps - 1 + (1 if after else 0)
-        st["cur_list"] ^= carried & 1
-        st["ready"] = ((first + n_steps if after == 1 else 0), offset + n_steps * B * gen.neg_rate) if after else None
+        st.run_steps(self.generator, st.index, n_steps, self.flat, st.plan.run)
 
     def transx_step_explicit(self, ph, pr, pt, nh, nr, nt):
         """The same step on an explicit batch (positives + given negatives, neg_rate 1): gradients into the flat buffer, no
