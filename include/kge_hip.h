@@ -1036,6 +1036,68 @@ int kge_conve_eval_ranks(const kge_conve_desc* d, const int64_t* triples, int64_
                          const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
                          int32_t* ties, void* stream);
 
+/* ---- HypER (models/projection.py:508-618): the body in front of the 1-N head (csrc/kge_hyper.hip).  For a row with
+ * entity e and relation r, D = ent_hidden_size, Dr = rel_hidden_size, L = D - 8, F = 32 L:
+ *     y0 = bn0(ent[e]) * m0   (one channel),   filt = fc1_w rel[r] + fc1_b   ([32 channels][9 taps], per row),
+ *     c[ch, p] = sum_w y0[p + w] filt[ch, w]   (p in [0, L), no bias),   A = bn1(c) * m1   (no relu),   u = A fc_w^T + fc_b,
+ *     x = relu(bn2(u * m2))   (bn2 in BOTH forms: the eval form normalises with the running buffers).
+ * There is ONE relation table [R, Dr]: a direction selects nothing, so the body takes no side.  Batch norm, the training and eval
+ * forms, the running-buffer update, the Philox draw and the kept-element rule are those of ConvE above, with
+ *     site 0 (input_dropout):       elem = pixel in [0, D)
+ *     site 1 (feature_map_dropout): elem = channel in [0, 32): one draw per row and channel (Dropout2d)
+ *     site 2 (hidden_dropout):      elem = j in [0, D)
+ *     row = row0 + position in the call's row list.  The fused step numbers the h rows 0 .. B-1 and the t rows B .. 2B-1.
+ * Both embeddings are built with padding_idx = 0: row 0 is an ordinary row in the forward, but the LOOKUP's gradient of id 0 is
+ * dropped on both tables.  g_rel[0] therefore stays as it was, and g_ent[0] receives the head's share (x . ent^T) only.
+ * Gradients are accumulated into g_*; all 13 are sums in a fixed order (no atomics in the body; what ConvE says of the loss holds here).
+ * Refused before any launch, with the entry point's name in kge_last_error(): null tables or running buffers, non-positive sizes,
+ * ent_hidden_size < 9 (no conv output), a hidden size above KGE_HYPER_MAX_HIDDEN (eight relation rows of the filter kernel, and the
+ * image with four channels of the conv gradient in the conv backward, are held in static LDS), a momentum outside (0, 1], a negative
+ * eps, n = 1 with train = 1, a dropout rate outside [0, 1), an offset of 2^62 or more, a workspace that is too small; the backward
+ * and the fused step also refuse train = 0. */
+#define KGE_HYPER_MAX_HIDDEN 1024
+typedef struct kge_hyper_desc {
+    int64_t tot_entity, tot_relation;
+    int32_t ent_hidden_size, rel_hidden_size;
+    float input_dropout, feature_map_dropout, hidden_dropout; /* sites 0, 1, 2 */
+    int32_t train;                                            /* 0 = model.eval() */
+    uint64_t seed, offset;                                    /* Philox key and step offset */
+    float eps[3], momentum[3];                                /* bn0, bn1, bn2 */
+    /* the 13 parameters in state-dict order: [E], [E,D], [R,Dr], [1], [1], [32], [32], [D], [D], [D,F], [D], [288,Dr], [288] */
+    const float *b, *ent, *rel, *bn0_w, *bn0_b, *bn1_w, *bn1_b, *bn2_w, *bn2_b, *fc_w, *fc_b, *fc1_w, *fc1_b;
+    float *bn0_mean, *bn0_var, *bn1_mean, *bn1_var, *bn2_mean, *bn2_var; /* running buffers [1], [1], [32], [32], [D], [D] */
+    /* dense grads, may be NULL for forward */
+    float *g_b, *g_ent, *g_rel, *g_bn0_w, *g_bn0_b, *g_bn1_w, *g_bn1_b, *g_bn2_w, *g_bn2_b, *g_fc_w, *g_fc_b, *g_fc1_w, *g_fc1_b;
+} kge_hyper_desc;
+
+/* x[n, D] of the rows (e_i, r_i) (one direction: the batch statistics are those of the n rows); row0: the mask row number of the
+ * call's first row.  The training form updates the six running buffers once.  saved: kge_hyper_saved_floats(d, n) floats that the
+ * backward of the same rows reads (conv output [n, F] | u [n, D] | filt [n, 288] | the statistics used). */
+size_t kge_hyper_saved_floats(const kge_hyper_desc* d, int64_t n);
+size_t kge_hyper_body_forward_workspace_bytes(const kge_hyper_desc* d, int64_t n);
+int kge_hyper_body_forward(const kge_hyper_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, float* x, float* saved,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* g_* += d(sum x o dx) / d tensor for the same rows, row0, descriptor (seed, offset) and `saved`; training form only.  g_b is the
+ * head's and is not touched; the lookup gradients of id 0 are dropped. */
+size_t kge_hyper_body_backward_workspace_bytes(const kge_hyper_desc* d, int64_t n);
+int kge_hyper_body_backward(const kge_hyper_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, const float* dx,
+                            const float* saved, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One Trainer.train_step_projection, arguments of kge_conve_train_bce: the body on (h, r) and on (t, r) in the same launches (each
+ * with its own batch statistics; every running buffer is updated twice, tail first), kge_head_1n_bce per direction with the bias b
+ * (g_ent and g_b accumulated), both backwards. */
+size_t kge_hyper_train_bce_workspace_bytes(const kge_hyper_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr);
+int kge_hyper_train_bce(const kge_hyper_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch, const int64_t* hr_off,
+                        const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids, int64_t n_tr, float label_smoothing,
+                        void* workspace, size_t workspace_bytes, float* loss, void* stream);
+
+/* Filtered and raw ranks, arguments and `ranks` layout ([4, n]) of kge_conve_eval_ranks: the eval-form body on (h, r) and on (t, r),
+ * then kge_head_1n_rank per side with the bias b.  Writes no running buffer. */
+size_t kge_hyper_eval_ranks_workspace_bytes(const kge_hyper_desc* d, int64_t n);
+int kge_hyper_eval_ranks(const kge_hyper_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                         const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                         int32_t* ties, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

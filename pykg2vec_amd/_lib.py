@@ -178,7 +178,39 @@ class ConveDesc(ctypes.Structure):
 
 _CVD = ctypes.POINTER(ConveDesc)
 
+# HypER's 13 parameters in state-dict (= descriptor) order (the bare parameter b comes first), and its six running buffers
+HYPER_TABLES = ("b", "ent", "rel", "bn0_w", "bn0_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "fc_w", "fc_b", "fc1_w", "fc1_b")
+HYPER_BUFFERS = CONVE_BUFFERS
+HYPER_MAX_HIDDEN = 1024
+
+
+class HyperDesc(ctypes.Structure):
+    """struct kge_hyper_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("ent_hidden_size", ctypes.c_int32),
+                ("rel_hidden_size", ctypes.c_int32), ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float),
+                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
+        + [(n, ctypes.c_void_p) for n in HYPER_TABLES] + [(n, ctypes.c_void_p) for n in HYPER_BUFFERS] \
+        + [("g_" + n, ctypes.c_void_p) for n in HYPER_TABLES]
+
+
+_HYD = ctypes.POINTER(HyperDesc)
+
 _SIGNATURES = {
+    "kge_hyper_saved_floats": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
+    "kge_hyper_body_forward_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
+    "kge_hyper_body_forward": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_hyper_body_backward_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
+    "kge_hyper_body_backward": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_hyper_train_bce_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "kge_hyper_train_bce": (ctypes.c_int, [_HYD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_hyper_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
+    "kge_hyper_eval_ranks": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_conve_saved_floats": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
     "kge_conve_body_forward_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
     "kge_conve_body_forward": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,

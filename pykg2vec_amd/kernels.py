@@ -726,6 +726,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
         return proje_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     if isinstance(desc, L.ConveDesc):
         return conve_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
+    if isinstance(desc, L.HyperDesc):
+        return hyper_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -1396,7 +1398,7 @@ def head_1n_bce(x, ent, bias, label_off, label_ids, label_smoothing, loss_buf, g
     return dx
 
 
-# ---------------------------------------------------------------- shared by the models with their own descriptor (ConvKB, TuckER, ProjE, ConvE)
+# ---------------------------------------------------------------- shared by the models with their own descriptor (ConvKB, TuckER, ProjE, ConvE, HypER)
 def _check_embeddings(model, *specs):
     """specs: (name, tensor, rows indexed by id, columns)."""
     for name, t, rows, cols in specs:
@@ -1798,3 +1800,83 @@ def conve_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothi
 def conve_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
     """int32 [4, n] as eval_ranks, in one kge_conve_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
     return _projection_eval_ranks("kge_conve_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)
+
+
+# ---------------------------------------------------------------- HypER (csrc/kge_hyper.hip): its own descriptor and entry points
+def hyper_shapes(tot_entity, tot_relation, ent_hidden_size, rel_hidden_size):
+    """The shapes of the 13 parameters (state-dict order, b first) and of the six running buffers."""
+    E, R, D, Dr = int(tot_entity), int(tot_relation), int(ent_hidden_size), int(rel_hidden_size)
+    return ([(E,), (E, D), (R, Dr), (1,), (1,), (32,), (32,), (D,), (D,), (D, 32 * (D - 8)), (D,), (288, Dr), (288,)],
+            [(1,), (1,), (32,), (32,), (D,), (D,)])
+
+
+def hyper_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, ent_hidden_size, rel_hidden_size, dropouts=(0.0, 0.0, 0.0),
+               eps=(1e-5, 1e-5, 1e-5), momentum=(0.1, 0.1, 0.1), train=False, seed=0, offset=0):
+    """kge_hyper_desc.  `tables` / `grads`: the 13 parameters in state-dict order (b, ent_embeddings.weight, rel_embeddings.weight,
+    bn0.weight, bn0.bias, bn1.weight, bn1.bias, bn2.weight, bn2.bias, fc.weight, fc.bias, fc1.weight, fc1.bias); `buffers`: the running
+    mean / variance of bn0, bn1, bn2, which the training form updates in place.  Shapes are checked here (the kernels index by id and
+    by shape without a bounds test) whenever the geometry is one the library accepts; the geometry, the rates, the momenta and the
+    offset are checked by the library, which refuses bad ones loudly."""
+    E, R, D, Dr = int(tot_entity), int(tot_relation), int(ent_hidden_size), int(rel_hidden_size)
+    if len(tables) != 13 or len(buffers) != 6:
+        raise L.KgeHipError("hyper: 13 tensors and 6 running buffers expected, got %d and %d" % (len(tables), len(buffers)))
+    if any(m is None for m in momentum):
+        raise L.KgeHipError("hyper: momentum None (the cumulative moving average) is not built")
+    if D >= 9 and Dr >= 1:
+        _check_embeddings("hyper", ("ent_embeddings", tables[1], E, D), ("rel_embeddings", tables[2], R, Dr))
+        want_t, want_b = hyper_shapes(E, R, D, Dr)
+        for i, (name, t, shape) in enumerate(zip(L.HYPER_TABLES + L.HYPER_BUFFERS, list(tables) + list(buffers), want_t + want_b)):
+            if i not in (1, 2) and tuple(t.shape) != shape:
+                raise L.KgeHipError("hyper: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
+    d = L.HyperDesc()
+    d.tot_entity, d.tot_relation, d.ent_hidden_size, d.rel_hidden_size = E, R, D, Dr
+    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
+    _set_rng(d, train, seed, offset)
+    for i in range(3):
+        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
+    for name, t in zip(L.HYPER_TABLES + L.HYPER_BUFFERS, list(tables) + list(buffers)):
+        setattr(d, name, _dev(t, torch.float32, name).value)
+    if grads is not None:
+        if len(grads) != 13:
+            raise L.KgeHipError("hyper: 13 gradient tensors expected, got %d" % len(grads))
+        _bind_grads(d, ["g_" + n for n in L.HYPER_TABLES], ["grad of " + n for n in L.HYPER_TABLES], grads, tables)
+    d._keepalive = (tables, buffers, grads)
+    d._ws = None
+    return d
+
+
+def hyper_body_forward(desc, e, r, row0=0):
+    """(x float32 [n, D], saved): the body of HypER.forward on the rows (e_i, r_i) of one direction; the training form updates the
+    descriptor's running buffers once.  `saved` is what hyper_body_backward reads."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    lib = L.load()
+    x = torch.empty((n, desc.ent_hidden_size), dtype=torch.float32, device=e.device)
+    wp, wb = _desc_ws(desc, "kge_hyper_body_forward_workspace_bytes", n)
+    saved = torch.empty(max(1, int(lib.kge_hyper_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
+    L.check(lib.kge_hyper_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(x, torch.float32, "x"),
+                                       _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_hyper_body_forward")
+    return x, saved
+
+
+def hyper_body_backward(desc, e, r, dx, saved, row0=0):
+    """g_* of the descriptor += the body's gradients given d loss / d x (same rows, row0, seed, offset and `saved` as the forward)."""
+    n = e.numel()
+    wp, wb = _desc_ws(desc, "kge_hyper_body_backward_workspace_bytes", n)
+    L.check(L.load().kge_hyper_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(dx, torch.float32, "dx"),
+                                             _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_hyper_body_backward")
+
+
+def hyper_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
+    """One train_step_projection of HypER: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice (tail
+    direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
+    B, n_hr, n_tr, args = _label_csr_args("hyper_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
+    wp, wb = _desc_ws(desc, "kge_hyper_train_bce_workspace_bytes", B, n_hr, n_tr)
+    L.check(L.load().kge_hyper_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+                                         _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_hyper_train_bce")
+
+
+def hyper_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks, in one kge_hyper_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
+    return _projection_eval_ranks("kge_hyper_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)

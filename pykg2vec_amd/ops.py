@@ -11,7 +11,9 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
   torch.ops.kge.proje_body_backward(key, e, r, side, seed, offset, dx, weights) -> their dense gradients
   torch.ops.kge.conve_body(key, e, r, side, seed, offset, weights) -> (x float32 [N, k], saved)   the body of ConvE.forward (models/projection.py:86-99, 104-113) up to the head; weights = its 13 tensors in state-dict order; the training form updates the model's running buffers, a write outside the op's schema: eager execution only
   torch.ops.kge.conve_body_backward(key, e, r, side, seed, offset, dx, saved, weights) -> their dense gradients (b's is the head's: zero here)
-  torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]   the projection models' 1-N head (models/projection.py:100-102)
+  torch.ops.kge.hyper_body(key, e, r, row0, seed, offset, weights) -> (x float32 [N, D], saved)   the body of HypER.forward (models/projection.py:583-606) up to the head; weights = its 13 tensors in state-dict order (b first); row0 = the mask row of the call's first row; the training form updates the model's running buffers, a write outside the op's schema: eager execution only
+  torch.ops.kge.hyper_body_backward(key, e, r, row0, seed, offset, dx, saved, weights) -> their dense gradients (b's is the head's: zero here; the lookup gradients of id 0 are dropped, padding_idx = 0)
+  torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]  the projection models' 1-N head (models/projection.py:100-102)
   torch.ops.kge.one_to_n_scores_backward(x, ent, preds, dpreds, need_bias) -> (dx, g_ent, g_bias)
 
 Registered with torch.library.custom_op (schema, fake-tensor kernels, autograd formulas), so the scorer is visible to torch.ops,
@@ -281,6 +283,59 @@ def _conve_backward(ctx, dx, _dsaved):
 
 
 conve_body.register_autograd(_conve_backward, setup_context=_conve_setup)
+
+
+# HypER's body (include/kge_hip.h: kge_hyper_body_*).  There is one relation table, so a direction selects nothing but the mask rows:
+# row0 = 0 for the tail direction and n for the head direction, so that the two forward calls of a training step under one (seed,
+# offset) draw the fused step's masks.  offset < 0 = the eval form (running statistics in all three batch norms, no draws).  Like
+# kge::conve_body, the training form updates the model's running buffers, a write outside the op's schema (mutates_args is empty):
+# eager execution only.
+@torch.library.custom_op("kge::hyper_body", mutates_args=(), device_types="cuda")
+def hyper_body(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
+    m = _model(key)
+    return K.hyper_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                                r.contiguous(), row0=row0)
+
+
+@hyper_body.register_fake
+def _(key, e, r, row0, seed, offset, weights):
+    n, D = e.numel(), weights[1].shape[1]
+    return weights[1].new_empty((n, D)), weights[1].new_empty((n * (weights[9].shape[1] + D + 288) + 66 + 2 * D,))
+
+
+@hyper_body.register_kernel("cpu")
+def _(key, e, r, row0, seed, offset, weights):
+    raise L.KgeHipError("kge::hyper_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
+
+
+@torch.library.custom_op("kge::hyper_body_backward", mutates_args=(), device_types="cuda")
+def hyper_body_backward(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
+                        weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.hyper_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                          r.contiguous(), dx.contiguous(), saved, row0=row0)
+    return grads
+
+
+@hyper_body_backward.register_fake
+def _(key, e, r, row0, seed, offset, dx, saved, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _hyper_setup(ctx, inputs, output):
+    key, e, r, row0, seed, offset, weights = inputs
+    ctx.key, ctx.row0, ctx.seed, ctx.offset = key, row0, seed, offset
+    ctx.save_for_backward(e, r, output[1], *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _hyper_backward(ctx, dx, _dsaved):
+    e, r, saved, *weights = ctx.saved_tensors
+    return None, None, None, None, None, None, hyper_body_backward(ctx.key, e, r, ctx.row0, ctx.seed, ctx.offset, dx, saved, weights)
+
+
+hyper_body.register_autograd(_hyper_backward, setup_context=_hyper_setup)
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

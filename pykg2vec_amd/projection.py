@@ -2,8 +2,9 @@
 (csrc/kge_tucker.hip) in front of the 1-N head (csrc/kge_head.hip).  ProjE_pointwise: a pointwise tanh body whose loss reads only the
 labelled columns of the 1-N product (csrc/kge_proje.hip); it is the one model here that trains with sampled negatives on this path.
 ConvE: batch norm, a 3 x 3 convolution, a fully connected layer on the matrix cores and two more batch norms (csrc/kge_conve.hip) in
-front of the head with its bias b; its torch layers are holders of parameters and buffers only.  InteractE, HypER and AcrE keep their
-PyTorch layers and call the head themselves."""
+front of the head with its bias b; its torch layers are holders of parameters and buffers only.  HypER: the same stack with a
+convolution filter that a second linear layer computes per row from the relation embedding, and padding_idx = 0 on both tables
+(csrc/kge_hyper.hip).  InteractE and AcrE keep their PyTorch layers and call the head themselves."""
 import torch
 
 from . import _lib as L  # noqa: F401
@@ -149,6 +150,107 @@ class ConvE(ProjectionModel):
         if self.training:
             self._count_batches(1)
         return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.b.weight, False)
+
+    def predict_tail_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
+        return rank
+
+    def predict_head_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
+        return rank
+
+
+class HypER(ProjectionModel):
+    """projection.py:508-618.  forward(e, r, direction) = sigmoid(x @ ent.T + b) with x = relu(bn2(hdrop(fc(flatten(fdrop(bn1(conv(
+    idrop(bn0(ent[e])), filt)))))))) and filt = fc1(rel[r]) viewed [32, 9]: a 1 x 9 filter per row and channel (the reference's grouped
+    convolution and permutes are exactly this).  There is one relation table: `direction` selects no relation row, only the mask rows.
+    The torch layers (bn0, bn1, bn2, fc, fc1) hold parameters and buffers only, so state_dict() has the reference's keys, order and
+    shapes (the bare parameter b first) and loads a reference checkpoint; the arithmetic is csrc/kge_hyper.hip.  Both embeddings are built
+    with padding_idx = 0 and then overwritten by xavier_uniform_, as the reference does: row 0 is an ordinary row in the forward, the
+    lookup's gradient of id 0 is dropped (grad of rel row 0 is zero; grad of ent row 0 is the head's share only).  Under train() a
+    forward normalises with the statistics of its own rows, updates the six running buffers and the three num_batches_tracked counters
+    as torch does, and draws the Philox masks of (dropout_seed, dropout_offset), the mask rows of the "head" direction following those of
+    the "tail" direction; with any rate > 0 it then advances dropout_offset by one.  Under eval() all three batch norms use the running
+    buffers (bn2 too, unlike ConvE), nothing is drawn and nothing is written."""
+    kernel_name = "hyper"
+    TENSORS = ("b", "ent_embeddings.weight", "rel_embeddings.weight", "bn0.weight", "bn0.bias", "bn1.weight", "bn1.bias", "bn2.weight",
+               "bn2.bias", "fc.weight", "fc.bias", "fc1.weight", "fc1.bias")   # descriptor order = state-dict order
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        param_list = ["tot_entity", "tot_relation", "ent_hidden_size", "rel_hidden_size", "input_dropout", "hidden_dropout",
+                      "feature_map_dropout"]
+        self.__dict__.update(self.load_params(param_list, kwargs))
+        self._device = kwargs.get("device")   # the reference requires the kwarg; here it defaults to where the weights live
+        self.filt_h, self.filt_w, self.in_channels, self.out_channels = 1, 9, 1, 32
+        D, Dr = int(self.ent_hidden_size), int(self.rel_hidden_size)
+        # (the reference replaces the three rates by nn.Dropout modules inp_drop / feature_map_drop / hidden_drop; here they stay numbers)
+        self.dropouts = (float(self.input_dropout), float(self.feature_map_dropout), float(self.hidden_dropout))
+        self.ent_embeddings = NamedEmbedding("ent_embeddings", self.tot_entity, D, padding_idx=0)
+        self.rel_embeddings = NamedEmbedding("rel_embeddings", self.tot_relation, Dr, padding_idx=0)
+        self.bn0 = torch.nn.BatchNorm2d(self.in_channels)
+        self.bn1 = torch.nn.BatchNorm2d(self.out_channels)
+        self.bn2 = torch.nn.BatchNorm1d(D)
+        self.register_parameter("b", torch.nn.Parameter(torch.zeros(self.tot_entity)))
+        # (max(..., 1): a geometry the library refuses must still construct, so that the refusal is the library's sentence)
+        self.fc = torch.nn.Linear(max((D - self.filt_w + 1) * self.out_channels, 1), D)
+        self.fc1 = torch.nn.Linear(Dr, self.in_channels * self.out_channels * self.filt_h * self.filt_w)
+        torch.nn.init.xavier_uniform_(self.ent_embeddings.weight.data)   # (overwrites the zero row of padding_idx, as the reference does)
+        torch.nn.init.xavier_uniform_(self.rel_embeddings.weight.data)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings]
+        self.loss = Criterion.multi_class_bce
+        self.dropout_seed = int(kwargs.get("seed", 0) or 0)
+        self.dropout_offset = 0
+
+    @property
+    def device(self):
+        return self._device if self._device is not None else self.ent_embeddings.weight.device
+
+    def _norms(self):
+        return (self.bn0, self.bn1, self.bn2)
+
+    def trainable_tensors(self):
+        return [self.b, self.ent_embeddings.weight, self.rel_embeddings.weight, self.bn0.weight, self.bn0.bias, self.bn1.weight,
+                self.bn1.bias, self.bn2.weight, self.bn2.bias, self.fc.weight, self.fc.bias, self.fc1.weight, self.fc1.bias]
+
+    def running_buffers(self):
+        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+
+    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        return K.hyper_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
+                            tot_relation=self.tot_relation, ent_hidden_size=int(self.ent_hidden_size),
+                            rel_hidden_size=int(self.rel_hidden_size), dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()],
+                            momentum=[bn.momentum for bn in self._norms()], train=self.training if train is None else train,
+                            seed=self.dropout_seed if seed is None else seed, offset=self.dropout_offset if offset is None else offset)
+
+    def _count_batches(self, calls):
+        for bn in self._norms():
+            bn.num_batches_tracked += calls
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        K.hyper_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
+        self._count_batches(2)   # the step is two training forwards
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def embed2(self, e, r):
+        return self.ent_embeddings(e), self.rel_embeddings(r)
+
+    def forward(self, e, r, direction="tail"):
+        assert direction in ("head", "tail"), "Unknown forward direction"
+        offset = -1   # eval(): running statistics, no dropout
+        if self.training:
+            offset = self.dropout_offset
+            if any(p > 0.0 for p in self.dropouts):
+                self.dropout_offset += 1
+        x, _saved = torch.ops.kge.hyper_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
+                                             self.trainable_tensors())
+        if self.training:
+            self._count_batches(1)
+        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.b, False)
 
     def predict_tail_rank(self, e, r, topk=-1):
         _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
