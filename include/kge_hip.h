@@ -1098,6 +1098,81 @@ int kge_hyper_eval_ranks(const kge_hyper_desc* d, const int64_t* triples, int64_
                          const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
                          int32_t* ties, void* stream);
 
+/* ---- InteractE (models/projection.py:347-505): the body in front of the 1-N head (csrc/kge_interacte.hip).  With
+ * K = reshape_width * reshape_height, H = 2 reshape_width, W = reshape_height, P = feature_permutation, NF = num_filters,
+ * ks = kernel_size, pad = ks / 2, C = P NF, F = C H W, for a row with entity e and relation r:
+ *     comb = [ent[e] | rel[r]]   (2K values),   img[p] = comb[perm[p, :]] viewed [H, W]   (p in [0, P)),   y0 = bn0(img) * m0,
+ *     c[p NF + f, y, x] = sum_{i, j < ks} conv_filt[f, 0, i, j] y0[p, (y + i - pad) mod H, (x + j - pad) mod W]
+ *                         (depthwise, the same NF filters for every p, no bias, circular padding, output H x W),
+ *     A = relu(bn1(c)) * m1,   u = flatten(A) fc_w^T + fc_b,   x = relu(bn2(u * m2))   (bn2 in BOTH forms, as HypER).
+ * There is ONE relation table [R, K]: a direction selects nothing, so the body takes no side.  Neither table has a padding_idx: every
+ * id's lookup gradient is scattered, id 0 included.  perm / inv_perm: int32 [P, 2K] on the device, every row of perm a permutation
+ * of [0, 2K) and inv_perm[p, perm[p, i]] = i; the library does not read them on the host, the caller guarantees both (the Python
+ * wrapper checks perm and builds inv_perm).  Batch norm, the training and eval forms, the running-buffer update, the Philox draw and
+ * the kept-element rule are those of ConvE above, with
+ *     site 0 (input_dropout):       elem = p H W + pixel in [0, 2K P)
+ *     site 1 (feature_map_dropout): elem = channel in [0, C): one draw per row and channel (Dropout2d)
+ *     site 2 (hidden_dropout):      elem = j in [0, K)
+ *     row = row0 + position in the call's row list.  The fused step numbers the h rows 0 .. B-1 and the t rows B .. 2B-1.
+ * Gradients are accumulated into g_*; all 12 are sums in a fixed order (no atomics in the body; what ConvE says of the loss holds here).
+ * Refused before any launch, with the entry point's name in kge_last_error(): null tables, running buffers or perm / inv_perm,
+ * non-positive sizes, an even kernel_size or one below 3 (the reference's output is then no longer H x W), kernel_size / 2 >
+ * min(H, W) (the circular padding wraps once), K above KGE_INTERACTE_MAX_HIDDEN (the padded image of a permutation, its raw values
+ * and four channels of the conv gradient are held in static LDS), kernel_size above KGE_INTERACTE_MAX_KERNEL (a filter's taps per wave
+ * are held in static LDS), F above KGE_INTERACTE_MAX_FLAT (feature indices are 32-bit), a momentum outside (0, 1], a negative eps,
+ * n = 1 with train = 1, a dropout rate outside [0, 1), an offset of 2^62 or more, a workspace that is too small; the backward and the
+ * fused step also refuse train = 0.  P NF needs no limit of its own: nothing of size C lives in LDS. */
+#define KGE_INTERACTE_MAX_HIDDEN 512
+#define KGE_INTERACTE_MAX_KERNEL 11
+#define KGE_INTERACTE_MAX_FLAT (1 << 22)
+typedef struct kge_interacte_desc {
+    /* layout (no padding): 0 tot_entity, 8 tot_relation, 16 reshape_height, 20 reshape_width, 24 feature_permutation, 28 num_filters,
+     * 32 kernel_size, 36 input_dropout, 40 feature_map_dropout, 44 hidden_dropout, 48 train, 52 reserved, 56 seed, 64 offset, 72 eps,
+     * 84 momentum, 96 perm, 104 inv_perm, 112 .. 200 the 12 tables, 208 .. 248 the six buffers, 256 .. 344 the 12 gradients; sizeof 352 */
+    int64_t tot_entity, tot_relation;
+    int32_t reshape_height, reshape_width, feature_permutation, num_filters, kernel_size;
+    float input_dropout, feature_map_dropout, hidden_dropout; /* sites 0, 1, 2 */
+    int32_t train;                                            /* 0 = model.eval() */
+    int32_t reserved;                                         /* not read */
+    uint64_t seed, offset;                                    /* Philox key and step offset */
+    float eps[3], momentum[3];                                /* bn0, bn1, bn2 */
+    const int32_t *perm, *inv_perm;                           /* [P, 2K] each, device */
+    /* the 12 parameters in state-dict order (a module's bare parameters precede its submodules'): [E], [NF,1,ks,ks], [E,K], [R,K], [P],
+     * [P], [C], [C], [K], [K], [K,F], [K] */
+    const float *bias, *conv_filt, *ent, *rel, *bn0_w, *bn0_b, *bn1_w, *bn1_b, *bn2_w, *bn2_b, *fc_w, *fc_b;
+    float *bn0_mean, *bn0_var, *bn1_mean, *bn1_var, *bn2_mean, *bn2_var; /* running buffers [P], [P], [C], [C], [K], [K] */
+    /* dense grads, may be NULL for forward */
+    float *g_bias, *g_conv_filt, *g_ent, *g_rel, *g_bn0_w, *g_bn0_b, *g_bn1_w, *g_bn1_b, *g_bn2_w, *g_bn2_b, *g_fc_w, *g_fc_b;
+} kge_interacte_desc;
+
+/* x[n, K] of the rows (e_i, r_i) (one direction: the batch statistics are those of the n rows); row0: the mask row number of the
+ * call's first row.  The training form updates the six running buffers once.  saved: kge_interacte_saved_floats(d, n) floats that the
+ * backward of the same rows reads (conv output [n, F] | u [n, K] | the feature-map factors [n, C] | the statistics used). */
+size_t kge_interacte_saved_floats(const kge_interacte_desc* d, int64_t n);
+size_t kge_interacte_body_forward_workspace_bytes(const kge_interacte_desc* d, int64_t n);
+int kge_interacte_body_forward(const kge_interacte_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, float* x, float* saved,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* g_* += d(sum x o dx) / d tensor for the same rows, row0, descriptor (seed, offset) and `saved`; training form only.  g_bias is the
+ * head's and is not touched. */
+size_t kge_interacte_body_backward_workspace_bytes(const kge_interacte_desc* d, int64_t n);
+int kge_interacte_body_backward(const kge_interacte_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, const float* dx,
+                                const float* saved, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One Trainer.train_step_projection, arguments of kge_conve_train_bce: the body on (h, r) and on (t, r) in the same launches (each
+ * with its own batch statistics; every running buffer is updated twice, tail first), kge_head_1n_bce per direction with `bias`
+ * (g_ent and g_bias accumulated), both backwards. */
+size_t kge_interacte_train_bce_workspace_bytes(const kge_interacte_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr);
+int kge_interacte_train_bce(const kge_interacte_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch,
+                            const int64_t* hr_off, const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids, int64_t n_tr,
+                            float label_smoothing, void* workspace, size_t workspace_bytes, float* loss, void* stream);
+
+/* Filtered and raw ranks, arguments and `ranks` layout ([4, n]) of kge_conve_eval_ranks: the eval-form body on (h, r) and on (t, r),
+ * then kge_head_1n_rank per side with `bias`.  Writes no running buffer. */
+size_t kge_interacte_eval_ranks_workspace_bytes(const kge_interacte_desc* d, int64_t n);
+int kge_interacte_eval_ranks(const kge_interacte_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                             const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                             int32_t* ties, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ MODEL_MAP = {  # lower-case name -> "module.Class", same keys as Importer.modelM
     "kg2e": "pairwise.KG2E", "hole": "pairwise.HoLE", "octonione": "pointwise.OctonionE",
     "convkb": "pointwise.ConvKB", "tucker": "projection.TuckER",
     "proje_pointwise": "projection.ProjE_pointwise", "conve": "projection.ConvE",
-    "hyper": "projection.HypER",
+    "hyper": "projection.HypER", "interacte": "projection.InteractE",
 }
 
 

@@ -196,7 +196,43 @@ class HyperDesc(ctypes.Structure):
 
 _HYD = ctypes.POINTER(HyperDesc)
 
+# InteractE's 12 parameters in state-dict (= descriptor) order (the bare parameters bias and conv_filt come first), and its six buffers
+INTERACTE_TABLES = ("bias", "conv_filt", "ent", "rel", "bn0_w", "bn0_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "fc_w", "fc_b")
+INTERACTE_BUFFERS = CONVE_BUFFERS
+INTERACTE_MAX_HIDDEN = 512
+INTERACTE_MAX_KERNEL = 11
+INTERACTE_MAX_FLAT = 1 << 22
+
+
+class InteracteDesc(ctypes.Structure):
+    """struct kge_interacte_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("reshape_height", ctypes.c_int32),
+                ("reshape_width", ctypes.c_int32), ("feature_permutation", ctypes.c_int32), ("num_filters", ctypes.c_int32),
+                ("kernel_size", ctypes.c_int32), ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float),
+                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64),
+                ("offset", ctypes.c_uint64), ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3),
+                ("perm", ctypes.c_void_p), ("inv_perm", ctypes.c_void_p)] \
+        + [(n, ctypes.c_void_p) for n in INTERACTE_TABLES] + [(n, ctypes.c_void_p) for n in INTERACTE_BUFFERS] \
+        + [("g_" + n, ctypes.c_void_p) for n in INTERACTE_TABLES]
+
+
+_ITD = ctypes.POINTER(InteracteDesc)
+
 _SIGNATURES = {
+    "kge_interacte_saved_floats": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
+    "kge_interacte_body_forward_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
+    "kge_interacte_body_forward": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_interacte_body_backward_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
+    "kge_interacte_body_backward": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_interacte_train_bce_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "kge_interacte_train_bce": (ctypes.c_int, [_ITD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_interacte_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
+    "kge_interacte_eval_ranks": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_hyper_saved_floats": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
     "kge_hyper_body_forward_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
     "kge_hyper_body_forward": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,

@@ -728,6 +728,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
         return conve_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     if isinstance(desc, L.HyperDesc):
         return hyper_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
+    if isinstance(desc, L.InteracteDesc):
+        return interacte_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -1880,3 +1882,116 @@ def hyper_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothi
 def hyper_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
     """int32 [4, n] as eval_ranks, in one kge_hyper_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
     return _projection_eval_ranks("kge_hyper_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)
+
+
+# ---------------------------------------------------------------- InteractE (csrc/kge_interacte.hip): its own descriptor and entry points
+def interacte_shapes(tot_entity, tot_relation, reshape_height, reshape_width, feature_permutation, num_filters, kernel_size):
+    """The shapes of the 12 parameters (state-dict order, bias and conv_filt first) and of the six running buffers."""
+    E, R, P, NF, ks = int(tot_entity), int(tot_relation), int(feature_permutation), int(num_filters), int(kernel_size)
+    k = int(reshape_height) * int(reshape_width)
+    C = P * NF
+    return ([(E,), (NF, 1, ks, ks), (E, k), (R, k), (P,), (P,), (C,), (C,), (k,), (k,), (k, C * 2 * k), (k,)],
+            [(P,), (P,), (C,), (C,), (k,), (k,)])
+
+
+def interacte_perm(chequer_perm, feature_permutation, hidden_size, device):
+    """(perm, inv_perm): the int32 [P, 2K] device copies kge_interacte_desc points to.  Every row of chequer_perm must be a
+    permutation of [0, 2K): the kernels gather by these indices without a bounds test, so this is checked here, on the host;
+    inv_perm[p, perm[p, i]] = i."""
+    P, n2 = int(feature_permutation), 2 * int(hidden_size)
+    cp = torch.as_tensor(chequer_perm).detach().cpu()
+    if cp.dtype not in (torch.int64, torch.int32) or tuple(cp.shape) != (P, n2):
+        raise L.KgeHipError("interacte: chequer_perm must be an integer tensor of shape %s (got %s %s)" % ((P, n2), cp.dtype, tuple(cp.shape)))
+    cp = cp.to(torch.int64)
+    want = torch.arange(n2, dtype=torch.int64)
+    for p in range(P):
+        if not torch.equal(torch.sort(cp[p]).values, want):
+            raise L.KgeHipError("interacte: row %d of chequer_perm is not a permutation of [0, %d)" % (p, n2))
+    inv = torch.empty_like(cp)
+    inv.scatter_(1, cp, want.expand(P, n2).contiguous())
+    return cp.to(torch.int32).contiguous().to(device), inv.to(torch.int32).contiguous().to(device)
+
+
+def interacte_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, reshape_height, reshape_width, feature_permutation, num_filters,
+                   kernel_size, chequer_perm=None, perms=None, dropouts=(0.0, 0.0, 0.0), eps=(1e-5, 1e-5, 1e-5), momentum=(0.1, 0.1, 0.1),
+                   train=False, seed=0, offset=0):
+    """kge_interacte_desc.  `tables` / `grads`: the 12 parameters in state-dict order (bias, conv_filt, ent_embeddings.weight,
+    rel_embeddings.weight, bn0.weight, bn0.bias, bn1.weight, bn1.bias, bn2.weight, bn2.bias, fc.weight, fc.bias); `buffers`: the running
+    mean / variance of bn0, bn1, bn2, which the training form updates in place.  chequer_perm: the model's [P, 2K] index tensor, checked
+    and inverted by interacte_perm; perms: the pair interacte_perm returned for it (a model caches it), instead.  Shapes are checked here
+    (the kernels index by id and by shape without a bounds test) whenever the geometry is one the library accepts; the geometry, the
+    rates, the momenta and the offset are checked by the library, which refuses bad ones loudly."""
+    E, R, rh, rw = int(tot_entity), int(tot_relation), int(reshape_height), int(reshape_width)
+    P, NF, ks = int(feature_permutation), int(num_filters), int(kernel_size)
+    k = rh * rw
+    if len(tables) != 12 or len(buffers) != 6:
+        raise L.KgeHipError("interacte: 12 tensors and 6 running buffers expected, got %d and %d" % (len(tables), len(buffers)))
+    if any(m is None for m in momentum):
+        raise L.KgeHipError("interacte: momentum None (the cumulative moving average) is not built")
+    if perms is None:
+        if chequer_perm is None:
+            raise L.KgeHipError("interacte: chequer_perm (or the pair interacte_perm made of it) is required")
+        perms = interacte_perm(chequer_perm, P, k, tables[2].device)
+    if min(rh, rw, P, NF) >= 1 and ks >= 3 and ks % 2 == 1:
+        _check_embeddings("interacte", ("ent_embeddings", tables[2], E, k), ("rel_embeddings", tables[3], R, k))
+        want_t, want_b = interacte_shapes(E, R, rh, rw, P, NF, ks)
+        for i, (name, t, shape) in enumerate(zip(L.INTERACTE_TABLES + L.INTERACTE_BUFFERS, list(tables) + list(buffers), want_t + want_b)):
+            if i not in (2, 3) and tuple(t.shape) != shape:
+                raise L.KgeHipError("interacte: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
+        for name, t in zip(("perm", "inv_perm"), perms):
+            if tuple(t.shape) != (P, 2 * k):
+                raise L.KgeHipError("interacte: %s must be %s (got %s)" % (name, (P, 2 * k), tuple(t.shape)))
+    d = L.InteracteDesc()
+    d.tot_entity, d.tot_relation, d.reshape_height, d.reshape_width = E, R, rh, rw
+    d.feature_permutation, d.num_filters, d.kernel_size = P, NF, ks
+    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
+    _set_rng(d, train, seed, offset)
+    for i in range(3):
+        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
+    d.perm, d.inv_perm = (_dev(t, torch.int32, name).value for name, t in zip(("perm", "inv_perm"), perms))
+    for name, t in zip(L.INTERACTE_TABLES + L.INTERACTE_BUFFERS, list(tables) + list(buffers)):
+        setattr(d, name, _dev(t, torch.float32, name).value)
+    if grads is not None:
+        if len(grads) != 12:
+            raise L.KgeHipError("interacte: 12 gradient tensors expected, got %d" % len(grads))
+        _bind_grads(d, ["g_" + n for n in L.INTERACTE_TABLES], ["grad of " + n for n in L.INTERACTE_TABLES], grads, tables)
+    d._keepalive = (tables, buffers, grads, perms)
+    d._ws = None
+    return d
+
+
+def interacte_body_forward(desc, e, r, row0=0):
+    """(x float32 [n, K], saved): the body of InteractE.forward on the rows (e_i, r_i) of one direction; the training form updates the
+    descriptor's running buffers once.  `saved` is what interacte_body_backward reads."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    lib = L.load()
+    x = torch.empty((n, desc.reshape_height * desc.reshape_width), dtype=torch.float32, device=e.device)
+    wp, wb = _desc_ws(desc, "kge_interacte_body_forward_workspace_bytes", n)
+    saved = torch.empty(max(1, int(lib.kge_interacte_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
+    L.check(lib.kge_interacte_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(x, torch.float32, "x"),
+                                           _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_interacte_body_forward")
+    return x, saved
+
+
+def interacte_body_backward(desc, e, r, dx, saved, row0=0):
+    """g_* of the descriptor += the body's gradients given d loss / d x (same rows, row0, seed, offset and `saved` as the forward)."""
+    n = e.numel()
+    wp, wb = _desc_ws(desc, "kge_interacte_body_backward_workspace_bytes", n)
+    L.check(L.load().kge_interacte_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(dx, torch.float32, "dx"),
+                                                 _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_interacte_body_backward")
+
+
+def interacte_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
+    """One train_step_projection of InteractE: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice
+    (tail direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
+    B, n_hr, n_tr, args = _label_csr_args("interacte_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
+    wp, wb = _desc_ws(desc, "kge_interacte_train_bce_workspace_bytes", B, n_hr, n_tr)
+    L.check(L.load().kge_interacte_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+                                             _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_interacte_train_bce")
+
+
+def interacte_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks, in one kge_interacte_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
+    return _projection_eval_ranks("kge_interacte_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)

@@ -4,7 +4,9 @@ labelled columns of the 1-N product (csrc/kge_proje.hip); it is the one model he
 ConvE: batch norm, a 3 x 3 convolution, a fully connected layer on the matrix cores and two more batch norms (csrc/kge_conve.hip) in
 front of the head with its bias b; its torch layers are holders of parameters and buffers only.  HypER: the same stack with a
 convolution filter that a second linear layer computes per row from the relation embedding, and padding_idx = 0 on both tables
-(csrc/kge_hyper.hip).  InteractE and AcrE keep their PyTorch layers and call the head themselves."""
+(csrc/kge_hyper.hip).  InteractE: chequer permutations of [ent[e] | rel[r]], a depthwise convolution with circular padding whose
+filters the permutations share, and the same fc / batch-norm tail (csrc/kge_interacte.hip).  AcrE keeps its PyTorch layers and calls
+the head itself."""
 import torch
 
 from . import _lib as L  # noqa: F401
@@ -251,6 +253,141 @@ class HypER(ProjectionModel):
         if self.training:
             self._count_batches(1)
         return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.b, False)
+
+    def predict_tail_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
+        return rank
+
+    def predict_head_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
+        return rank
+
+
+class InteractE(ProjectionModel):
+    """projection.py:347-505.  forward(e, r, direction) = sigmoid(x @ ent.T + bias) with x = relu(bn2(hdrop(fc(flatten(fdrop(relu(bn1(
+    conv(idrop(bn0(img)))))))))), img the feature_permutation chequer permutations of [ent[e] | rel[r]] viewed [2 reshape_width,
+    reshape_height], and conv the depthwise convolution with circular padding whose num_filters filters are shared by the
+    permutations.  There is one relation table: `direction` selects no relation row, only the mask rows.  The torch layers (bn0, bn1,
+    bn2, fc) hold parameters and buffers only, so state_dict() has the reference's keys, order and shapes (the bare parameters bias and
+    conv_filt first) and loads a reference checkpoint; the arithmetic is csrc/kge_interacte.hip.  chequer_perm is a plain attribute
+    (not in state_dict(), as in the reference) drawn by _get_chequer_perm with the reference's np.random calls in the reference's
+    order; `m.chequer_perm = tensor` loads another model's.  Its int32 device copy and inverse are cached and rebuilt when the
+    attribute is reassigned, changed in place or the weights move; a row that is no permutation of [0, 2 hidden_size) is refused
+    there.  Under train() a forward normalises with the statistics of its own rows, updates the six running buffers and the three
+    num_batches_tracked counters as torch does, and draws the Philox masks of (dropout_seed, dropout_offset), the mask rows of the
+    "head" direction following those of the "tail" direction; with any rate > 0 it then advances dropout_offset by one.  Under
+    eval() all three batch norms use the running buffers, nothing is drawn and nothing is written."""
+    kernel_name = "interacte"
+    TENSORS = ("bias", "conv_filt", "ent_embeddings.weight", "rel_embeddings.weight", "bn0.weight", "bn0.bias", "bn1.weight", "bn1.bias",
+               "bn2.weight", "bn2.bias", "fc.weight", "fc.bias")   # descriptor order = state-dict order
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        param_list = ["tot_entity", "tot_relation", "hidden_size", "input_dropout", "hidden_dropout", "feature_map_dropout",
+                      "feature_permutation", "num_filters", "kernel_size", "reshape_height", "reshape_width"]
+        self.__dict__.update(self.load_params(param_list, kwargs))
+        self.hidden_size = self.reshape_width * self.reshape_height
+        self._device = kwargs.get("device")   # the reference requires the kwarg; here it defaults to where the weights live
+        k, P, NF, ks = int(self.hidden_size), int(self.feature_permutation), int(self.num_filters), int(self.kernel_size)
+        # (the reference replaces the three rates by nn.Dropout modules inp_drop / feature_map_drop / hidden_drop; here they stay numbers)
+        self.dropouts = (float(self.input_dropout), float(self.feature_map_dropout), float(self.hidden_dropout))
+        self.ent_embeddings = NamedEmbedding("ent_embeddings", self.tot_entity, k, padding_idx=None)
+        self.rel_embeddings = NamedEmbedding("rel_embeddings", self.tot_relation, k, padding_idx=None)
+        self.bn0 = torch.nn.BatchNorm2d(P)
+        self.padding = 0
+        self.bn1 = torch.nn.BatchNorm2d(NF * P)
+        self.flat_sz = self.reshape_height * 2 * self.reshape_width * NF * P
+        self.bn2 = torch.nn.BatchNorm1d(k)
+        self.fc = torch.nn.Linear(self.flat_sz, k)
+        self._perm_cache = None
+        self.chequer_perm = self._get_chequer_perm()
+        self.register_parameter("bias", torch.nn.Parameter(torch.zeros(self.tot_entity)))
+        self.register_parameter("conv_filt", torch.nn.Parameter(torch.zeros(NF, 1, ks, ks)))
+        torch.nn.init.xavier_uniform_(self.ent_embeddings.weight)
+        torch.nn.init.xavier_uniform_(self.rel_embeddings.weight)
+        torch.nn.init.xavier_uniform_(self.conv_filt)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings]
+        self.loss = Criterion.multi_class_bce
+        self.dropout_seed = int(kwargs.get("seed", 0) or 0)
+        self.dropout_offset = 0
+
+    @property
+    def device(self):
+        return self._device if self._device is not None else self.ent_embeddings.weight.device
+
+    def _get_chequer_perm(self):
+        """The reference's draw (projection.py:468-505): all entity permutations first, then all relation ones, from np.random."""
+        import numpy as np
+        k, P = int(self.hidden_size), int(self.feature_permutation)
+        ent_perm = np.int32([np.random.permutation(k) for _ in range(P)])
+        rel_perm = np.int32([np.random.permutation(k) for _ in range(P)])
+        comb_idx = []
+        for p in range(P):
+            temp, idx = [], 0
+            for i in range(int(self.reshape_height)):
+                for _ in range(int(self.reshape_width)):
+                    pair = [ent_perm[p, idx], rel_perm[p, idx] + k]
+                    temp += pair if (p + i) % 2 == 0 else pair[::-1]   # the chequer: the entity value leads where p + i is even
+                    idx += 1
+            comb_idx.append(temp)
+        return torch.LongTensor(np.int32(comb_idx).reshape(P, 2 * k))
+
+    def _perms(self):
+        """The cached (perm, inv_perm) int32 device pair of chequer_perm (K.interacte_perm checks the permutation rows)."""
+        cp, dev = self.chequer_perm, self.ent_embeddings.weight.device
+        key = (id(cp), getattr(cp, "_version", None), getattr(cp, "device", None), dev)
+        if self._perm_cache is None or self._perm_cache[0] != key:
+            # (the cache holds cp itself, so that its id cannot be reused by another tensor while the entry lives)
+            self._perm_cache = (key, cp, K.interacte_perm(cp, int(self.feature_permutation), int(self.hidden_size), dev))
+        return self._perm_cache[2]
+
+    def _norms(self):
+        return (self.bn0, self.bn1, self.bn2)
+
+    def trainable_tensors(self):
+        return [self.bias, self.conv_filt, self.ent_embeddings.weight, self.rel_embeddings.weight, self.bn0.weight, self.bn0.bias,
+                self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias, self.fc.weight, self.fc.bias]
+
+    def running_buffers(self):
+        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+
+    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        return K.interacte_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
+                                tot_relation=self.tot_relation, reshape_height=int(self.reshape_height),
+                                reshape_width=int(self.reshape_width), feature_permutation=int(self.feature_permutation),
+                                num_filters=int(self.num_filters), kernel_size=int(self.kernel_size), perms=self._perms(),
+                                dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()],
+                                momentum=[bn.momentum for bn in self._norms()], train=self.training if train is None else train,
+                                seed=self.dropout_seed if seed is None else seed, offset=self.dropout_offset if offset is None else offset)
+
+    def _count_batches(self, calls):
+        for bn in self._norms():
+            bn.num_batches_tracked += calls
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        K.interacte_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
+        self._count_batches(2)   # the step is two training forwards
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def embed2(self, e, r):
+        return self.ent_embeddings(e), self.rel_embeddings(r)
+
+    def forward(self, e, r, direction="tail"):
+        assert direction in ("head", "tail"), "Unknown forward direction"
+        offset = -1   # eval(): running statistics, no dropout
+        if self.training:
+            offset = self.dropout_offset
+            if any(p > 0.0 for p in self.dropouts):
+                self.dropout_offset += 1
+        x, _saved = torch.ops.kge.interacte_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
+                                                 self.trainable_tensors())
+        if self.training:
+            self._count_batches(1)
+        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.bias, False)
 
     def predict_tail_rank(self, e, r, topk=-1):
         _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
