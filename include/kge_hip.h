@@ -1173,6 +1173,85 @@ int kge_interacte_eval_ranks(const kge_interacte_desc* d, const int64_t* triples
                              const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
                              int32_t* ties, void* stream);
 
+/* ---- AcrE (models/projection.py:621-746): the body in front of the 1-N head (csrc/kge_acre.hip).  hidden_size
+ * is 200 by construction: the image is always 20 x 20, the entity's 10 x 20 stacked on the relation's 10 x 20.  With C = in_channels,
+ * a1 / a2 / a3 = first / second / third_atrous, F = 400 C, for a row with entity e and relation r:
+ *     img = [ent[e] | rel[r]] viewed [20, 20],   y0 = bn0(img) * m0,   res = y0   (the residual carries the dropped input)
+ *     serial (way = 0):   z1 = conv1(y0) (1 -> C),  z2 = conv2(z1) (C -> C),  z3 = conv3(z2) (C -> C),  c = z3 + res (broadcast over C)
+ *     parallel (way = 1): zi = conv_i(y0) (1 -> C, i = 1 .. 3),  c = [res | z1 | z2 | z3] gate_w^T + gate_b   ([C, 1600] -> [C, 400])
+ *     A = relu(bn1(c)) * m1,   u = flatten(A) fc_w^T + fc_b,   x = relu(bn2(u * m2))   (bn2 in BOTH forms, as HypER and InteractE).
+ * Every convolution is 3 x 3 with dilation a_i and zero padding a_i (output 20 x 20) and has a bias iff acre_bias; there is no
+ * nonlinearity between them.  There is ONE relation table [2 tot_relation, 200]: a direction selects nothing, relation ids run over
+ * [0, 2 tot_relation).  Neither table has a padding_idx: every id's lookup gradient is scattered, id 0 included.  Batch norm, the
+ * training and eval forms, the running-buffer update, the Philox draw and the kept-element rule are those of ConvE above, with
+ *     site 0 (input_dropout):       elem = pixel in [0, 400), the entity half first
+ *     site 1 (feature_map_dropout): elem = channel in [0, C): one draw per row and channel (Dropout2d)
+ *     site 2 (hidden_dropout):      elem = j in [0, 200)
+ *     row = row0 + position in the call's row list.  The fused step numbers the h rows 0 .. B-1 and the t rows B .. 2B-1.
+ * Gradients are accumulated into g_*; all are sums in a fixed order (no atomics in the body; what ConvE says of the loss holds here).
+ * The conv bias pointers (and their gradients') are NULL iff acre_bias = 0; the gate pointers are NULL iff way = 0.
+ * Refused before any launch, with the entry point's name in kge_last_error(): null tables, running buffers or (where needed)
+ * gradients, non-positive sizes, hidden_size != 200, way outside {0, 1}, a dilation below 1 or above KGE_ACRE_MAX_ATROUS,
+ * in_channels above KGE_ACRE_MAX_CHANNELS (a layer of C x 400 values is held in static LDS), conv-bias or gate pointers inconsistent
+ * with acre_bias / way, a momentum outside (0, 1], a negative eps, n = 1 with train = 1, a dropout rate outside [0, 1), an offset of
+ * 2^62 or more, a workspace that is too small; the backward and the fused step also refuse train = 0.  The parallel way (way = 1)
+ * is described here but not built: every entry point refuses it with a sentence that names it. */
+#define KGE_ACRE_MAX_CHANNELS 32
+#define KGE_ACRE_MAX_ATROUS 4
+typedef struct kge_acre_desc {
+    /* layout (no padding): 0 tot_entity, 8 tot_relation, 16 hidden_size, 20 in_channels, 24 way, 28 first_atrous, 32 second_atrous,
+     * 36 third_atrous, 40 acre_bias, 44 input_dropout, 48 feature_map_dropout, 52 hidden_dropout, 56 train, 60 reserved, 64 seed,
+     * 72 offset, 80 eps, 92 momentum, 104 .. 248 the 19 tables, 256 .. 296 the six buffers, 304 .. 448 the 19 gradients; sizeof 456 */
+    int64_t tot_entity, tot_relation;
+    int32_t hidden_size, in_channels;
+    int32_t way;                                              /* 0 = serial, 1 = parallel */
+    int32_t first_atrous, second_atrous, third_atrous;
+    int32_t acre_bias;                                        /* 0 / 1 */
+    float input_dropout, feature_map_dropout, hidden_dropout; /* sites 0, 1, 2 */
+    int32_t train;                                            /* 0 = model.eval() */
+    int32_t reserved;                                         /* not read */
+    uint64_t seed, offset;                                    /* Philox key and step offset */
+    float eps[3], momentum[3];                                /* bn0, bn1, bn2 */
+    /* the parameters in state-dict order (a module's bare parameter precedes its submodules'): [E], [E,200], [2R,200], [1], [1], [C],
+     * [C], [200], [200], [200,F], [200], conv1 [C,1,3,3] [C], conv2 and conv3 [C,C,3,3] [C] (serial) or [C,1,3,3] [C] (parallel),
+     * gate [400,1600] [400] (parallel only) */
+    const float *bias, *ent, *rel, *bn0_w, *bn0_b, *bn1_w, *bn1_b, *bn2_w, *bn2_b, *fc_w, *fc_b, *conv1_w, *conv1_b, *conv2_w, *conv2_b,
+        *conv3_w, *conv3_b, *gate_w, *gate_b;
+    float *bn0_mean, *bn0_var, *bn1_mean, *bn1_var, *bn2_mean, *bn2_var; /* running buffers [1], [1], [C], [C], [200], [200] */
+    /* dense grads, may be NULL for forward */
+    float *g_bias, *g_ent, *g_rel, *g_bn0_w, *g_bn0_b, *g_bn1_w, *g_bn1_b, *g_bn2_w, *g_bn2_b, *g_fc_w, *g_fc_b, *g_conv1_w, *g_conv1_b,
+        *g_conv2_w, *g_conv2_b, *g_conv3_w, *g_conv3_b, *g_gate_w, *g_gate_b;
+} kge_acre_desc;
+
+/* x[n, 200] of the rows (e_i, r_i) (one direction: the batch statistics are those of the n rows); row0: the mask row number of the
+ * call's first row.  The training form updates the six running buffers once.  saved: kge_acre_saved_floats(d, n) =
+ * n (3 F + 200 + C) + 2 + 2 C + 400 floats that the backward of the same rows reads (c, z1, z2 [n, F] each | u [n, 200] | the
+ * feature-map factors [n, C] | the statistics used). */
+size_t kge_acre_saved_floats(const kge_acre_desc* d, int64_t n);
+size_t kge_acre_body_forward_workspace_bytes(const kge_acre_desc* d, int64_t n);
+int kge_acre_body_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, float* x, float* saved,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* g_* += d(sum x o dx) / d tensor for the same rows, row0, descriptor (seed, offset) and `saved`; training form only.  g_bias is the
+ * head's and is not touched. */
+size_t kge_acre_body_backward_workspace_bytes(const kge_acre_desc* d, int64_t n);
+int kge_acre_body_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, const float* dx,
+                           const float* saved, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One Trainer.train_step_projection, arguments of kge_conve_train_bce: the body on (h, r) and on (t, r) in the same launches (each
+ * with its own batch statistics; every running buffer is updated twice, tail first), kge_head_1n_bce per direction with `bias`
+ * (g_ent and g_bias accumulated), both backwards. */
+size_t kge_acre_train_bce_workspace_bytes(const kge_acre_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr);
+int kge_acre_train_bce(const kge_acre_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch, const int64_t* hr_off,
+                       const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids, int64_t n_tr, float label_smoothing,
+                       void* workspace, size_t workspace_bytes, float* loss, void* stream);
+
+/* Filtered and raw ranks, arguments and `ranks` layout ([4, n]) of kge_conve_eval_ranks: the eval-form body on (h, r) and on (t, r),
+ * then kge_head_1n_rank per side with `bias`.  Writes no running buffer. */
+size_t kge_acre_eval_ranks_workspace_bytes(const kge_acre_desc* d, int64_t n);
+int kge_acre_eval_ranks(const kge_acre_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                        const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                        int32_t* ties, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ MODEL_MAP = {  # lower-case name -> "module.Class", same keys as Importer.modelM
     "convkb": "pointwise.ConvKB", "tucker": "projection.TuckER",
     "proje_pointwise": "projection.ProjE_pointwise", "conve": "projection.ConvE",
     "hyper": "projection.HypER", "interacte": "projection.InteractE",
+    "acre": "projection.AcrE",
 }
 
 

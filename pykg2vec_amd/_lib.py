@@ -218,6 +218,30 @@ class InteracteDesc(ctypes.Structure):
 
 _ITD = ctypes.POINTER(InteracteDesc)
 
+# AcrE's parameters in state-dict (= descriptor) order (the bare parameter bias comes first): 17 in the serial way, 19 in the parallel
+# (the gate); the descriptor has all 19 slots, the conv biases NULL without acre_bias and the gate NULL in the serial way
+ACRE_TABLES_SERIAL = ("bias", "ent", "rel", "bn0_w", "bn0_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "fc_w", "fc_b", "conv1_w", "conv1_b",
+                      "conv2_w", "conv2_b", "conv3_w", "conv3_b")
+ACRE_TABLES_PARALLEL = ACRE_TABLES_SERIAL + ("gate_w", "gate_b")
+ACRE_BUFFERS = CONVE_BUFFERS
+ACRE_MAX_CHANNELS = 32
+ACRE_MAX_ATROUS = 4
+
+
+class AcreDesc(ctypes.Structure):
+    """struct kge_acre_desc"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("hidden_size", ctypes.c_int32),
+                ("in_channels", ctypes.c_int32), ("way", ctypes.c_int32), ("first_atrous", ctypes.c_int32),
+                ("second_atrous", ctypes.c_int32), ("third_atrous", ctypes.c_int32), ("acre_bias", ctypes.c_int32),
+                ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float), ("hidden_dropout", ctypes.c_float),
+                ("train", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
+        + [(n, ctypes.c_void_p) for n in ACRE_TABLES_PARALLEL] + [(n, ctypes.c_void_p) for n in ACRE_BUFFERS] \
+        + [("g_" + n, ctypes.c_void_p) for n in ACRE_TABLES_PARALLEL]
+
+
+_ACD = ctypes.POINTER(AcreDesc)
+
 _SIGNATURES = {
     "kge_interacte_saved_floats": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
     "kge_interacte_body_forward_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
@@ -233,6 +257,20 @@ _SIGNATURES = {
     "kge_interacte_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
     "kge_interacte_eval_ranks": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
                                  + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_acre_saved_floats": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
+    "kge_acre_body_forward_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
+    "kge_acre_body_forward": (ctypes.c_int, [_ACD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_acre_body_backward_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
+    "kge_acre_body_backward": (ctypes.c_int, [_ACD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_acre_train_bce_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "kge_acre_train_bce": (ctypes.c_int, [_ACD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_acre_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
+    "kge_acre_eval_ranks": (ctypes.c_int, [_ACD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                            + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_hyper_saved_floats": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
     "kge_hyper_body_forward_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
     "kge_hyper_body_forward": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,

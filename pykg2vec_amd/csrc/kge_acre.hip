@@ -1,0 +1,1174 @@
+// kge_acre.hip -- the body of AcrE (models/projection.py:621-746) in front of the 1-N head of kge_head.hip.
+// K = hidden_size = 200, the image is always H x W = 20 x 20 (HW = 400 = 2K), C = in_channels, a1 / a2 / a3 the three dilations,
+// F = 400 C.  For a row with entity e and relation r, in the SERIAL way (way = 0; the parallel way is refused, see ac_check):
+//     img = [ent[e] | rel[r]] viewed [20, 20]                  ONE relation table [2R, K]; a direction selects nothing
+//     y0  = bn0(img) * m0                                      input dropout, site 0; res = y0
+//     z1  = conv1(y0)   1 -> C, 3 x 3, dilation a1, zero padding a1      VALU from y0 in LDS (k_acre_conv1), STORED
+//     z2  = conv2(z1)   C -> C, dilation a2                    an implicit GEMM on v_mfma_f32_16x16x4_f32 (k_acre_cc): per row
+//     z3  = conv3(z2)   C -> C, dilation a3                    M = C output channels, N = 400 positions, K = 9 C; the input layer is
+//                                                              held in LDS, a tap that falls into the padding is a zero operand and
+//                                                              C is padded to the tile by zero operands (nothing padded in memory)
+//     c   = z3 + res (res broadcast over the channels)         added in k_acre_cc's epilogue; z2 and c STORED
+//     A   = relu(bn1(c)) * m1                                  feature-map dropout, site 1: a whole channel of a row; never stored
+//     u   = A fc_w^T + fc_b                                    [n, F] x [F, K] on the matrix cores, F split over workgroups (k_acre_fc),
+//                                                              the partial tiles added in split order (k_acre_fc_finish)
+//     x   = relu(bn2(u * m2))                                  hidden dropout, site 2; bn2 in BOTH forms
+// Every convolution has a bias iff acre_bias.  There is no nonlinearity between the three convolutions.  Batch norm, the two forms,
+// the statistics as fixed-order (mean, M2) sums and `dirs` are those of kge_interacte.hip, whose tail (fc, bn2, bn1, scatter) this
+// file repeats with P = 1.
+//
+// Backward (training form only), dx the gradient at x:
+//     k_acre_bn2_bwd / k_acre_fc_gw / k_acre_fc_da / k_acre_bn1_part / k_acre_bn1_bwd_fin     as InteractE's
+//     k_acre_bn1_dc     dc = d loss / d c through bn1, in place of dy1; dz3 = dc and d res = sum over the channels of dc, ascending
+//     k_acre_cc_gw      per row: gwp[row][o, i, t] = sum_pos dz[o, pos] in[i, pos + tap t] on the matrix cores (M = o, N = i, the 400
+//                       positions are the contraction; both layers in LDS) and the bias partial gbp[row][o] = sum_pos dz[o, pos]
+//     k_acre_cc<true>   dz_in = the same implicit GEMM with the flipped, transposed filter
+//     k_acre_c1_bwd     per row: conv1's filter and bias partials (VALU), dy0 = (conv1^T dz1 + d res) * m0, bn0's two row sums
+//     k_acre_rowsum     g += the per-row partials: 16 row classes (row mod 16) each in row order, then the 16 sums as a fixed tree
+//     k_acre_bn0_fin / k_acre_dcomb / k_acre_scatter    bn0's backward, d ent | d rel rows, the ordered scatter (every id, 0 included)
+// z1 and z2 are SAVED by the forward, not recomputed: they pass through global memory between the launches anyway.
+// No kernel of this file uses atomics.
+//
+// The dropout draw is the shared one (kge_projection.h spells the Philox counters out), with
+//     site 0: elem = pixel in [0, 400), entity half first;   site 1: elem = channel in [0, C);   site 2: elem = j in [0, K)
+//     row = row0 + position in the call's row list.  The fused step numbers the h rows 0 .. B-1 and the t rows B .. 2B-1.
+#include "kge_projection.h"
+#include "kge_mfma_blocks.h"
+
+namespace kge {
+
+constexpr int kAcK = 200;           // hidden_size
+constexpr int kAcW = 20;            // image width and height
+constexpr int kAcHW = 400;
+constexpr int kAcMaxC = KGE_ACRE_MAX_CHANNELS;
+constexpr int kAcLS = 404;          // LDS stride of a channel's 400 values: 16 channels at one position fall on 16 distinct banks
+constexpr int kAcRows = 64;         // batch rows of a matrix-core tile of the fc kernels
+constexpr int kAcKC = 128;
+constexpr int kAcStride = 68;
+constexpr int kAcPT = 7;            // position tiles (of 16) per wave of k_acre_cc: 25 tiles over 4 waves
+static_assert(kAcMaxC % 16 == 0 && 4 * kAcPT >= kAcHW / 16 && kAcHW % 16 == 0, "tiles");
+
+struct AcArgs {
+    const float *ent, *rel, *w0, *b0, *w1, *b1, *w2, *b2, *fcw, *fcb;
+    const float *cw[3], *cb[3];     // conv weights [C, 1 or C, 3, 3] and biases [C] (NULL without acre_bias)
+    int dil[3];
+    int K, HW, C, F;
+    int dirs;
+    int64_t n;                      // rows per direction
+    uint32_t row0;
+    int on[3];                      // site draws (training form and p > 0)
+    DropKey key;
+    uint32_t thr[3];
+    float scale[3];
+    float* stats;                   // [dirs][SS]: mean0, rstd0, mean1[C], rstd1[C], mean2[K], rstd2[K]
+    int SS, o1, o2;                 // SS = 2 + 2C + 2K, o1 = 2, o2 = 2 + 2C
+};
+__device__ __forceinline__ const float* ac_stats(const AcArgs& a, int d) { return a.stats + (size_t)d * a.SS; }
+__device__ __forceinline__ float ac_factor(const AcArgs& a, int site, int elem, int64_t gr) {
+    return a.on[site] ? drop_row_factor(a.key, site, elem, (int64_t)a.row0 + gr, a.thr[site], a.scale[site]) : 1.0f;
+}
+__device__ __forceinline__ float ac_comb(const AcArgs& a, const float* __restrict__ er, const float* __restrict__ rr, int c) {
+    return c < a.K ? er[c] : rr[c - a.K];
+}
+// position of tap t (0 .. 8) of a 3 x 3 filter with dilation d around pos, or -1 in the zero padding
+__device__ __forceinline__ int ac_tap(int pos, int t, int d) {
+    const int y = pos / kAcW + (t / 3 - 1) * d, x = pos % kAcW + (t % 3 - 1) * d;
+    return (y >= 0 && y < kAcW && x >= 0 && x < kAcW) ? y * kAcW + x : -1;
+}
+
+__device__ __forceinline__ double ac_wave_sum_xor(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// one wave per row: (mean, M2) of the row's 400 values [ent[e] | rel[r]], summed in double: the mean of zero-centred embeddings
+// nearly cancels, and bn0's running mean is compared on its own size
+__global__ void __launch_bounds__(256) k_acre_row_stats(AcArgs a, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
+                                                        double2* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int64_t gr = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gr >= a.n * a.dirs) return;
+    const float* __restrict__ er = a.ent + e[gr] * a.K;
+    const float* __restrict__ rr = a.rel + r[gr] * a.K;
+    double s = 0.0;
+    for (int c = lane; c < a.HW; c += 64) s += (double)ac_comb(a, er, rr, c);
+    const double mean = ac_wave_sum_xor(s) / (double)a.HW;
+    double m2 = 0.0;
+    for (int c = lane; c < a.HW; c += 64) { const double v = (double)ac_comb(a, er, rr, c) - mean; m2 += v * v; }
+    m2 = ac_wave_sum_xor(m2);
+    if (lane == 0) part[gr] = make_double2(mean, m2);
+}
+
+// one wave: bn0's statistics of every direction from the per-row partials (each over 400 values), in double, the tail direction
+// first; mean / rstd -> stats, running buffers updated (momentum, unbiased variance)
+__global__ void __launch_bounds__(64) k_acre_bn0_stats(AcArgs a, const double2* __restrict__ part, float eps, float mom,
+                                                       float* __restrict__ run_mean, float* __restrict__ run_var) {
+    const int lane = threadIdx.x;
+    for (int d = 0; d < a.dirs; ++d) {
+        const double2* __restrict__ p = part + (size_t)d * a.n;
+        double s = 0.0;
+        for (int64_t b = lane; b < a.n; b += 64) s += p[b].x;
+        const double mean = ac_wave_sum_xor(s) / (double)a.n;
+        double m2 = 0.0;
+        for (int64_t b = lane; b < a.n; b += 64) { const double2 v = p[b]; const double dv = v.x - mean; m2 += v.y + (double)a.HW * (dv * dv); }
+        m2 = ac_wave_sum_xor(m2);
+        const double tot = (double)a.n * (double)a.HW;
+        if (lane == 0) {
+            float* st = a.stats + (size_t)d * a.SS;
+            const float meanf = (float)mean;
+            st[0] = meanf;
+            st[1] = 1.0f / sqrtf((float)(m2 / tot) + eps);
+            run_mean[0] = (1.0f - mom) * run_mean[0] + mom * meanf;
+            run_var[0] = (1.0f - mom) * run_var[0] + mom * (float)(m2 / (tot - 1.0));
+        }
+    }
+}
+
+// one wave per channel: the statistics of every direction from the per-row partials part[row * pstride + c] (each over cnt values),
+// the tail direction first; mean / rstd -> stats, running buffers updated (momentum, unbiased variance)
+__global__ void __launch_bounds__(256) k_acre_bn_fin(AcArgs a, const float2* __restrict__ part, int chans, int pstride, int cnt, int mean_at,
+                                                     int rstd_at, float eps, float mom, float* __restrict__ run_mean,
+                                                     float* __restrict__ run_var) {
+    const int lane = threadIdx.x & 63;
+    const int c = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= chans) return;
+    for (int d = 0; d < a.dirs; ++d) {
+        const float2* __restrict__ p = part + (size_t)d * a.n * pstride + c;
+        float s = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) s += p[b * pstride].x;
+        const float mean = wave_sum_xor(s) / (float)a.n;
+        float m2 = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) { const float2 v = p[b * pstride]; const float dv = v.x - mean; m2 += v.y + (float)cnt * (dv * dv); }
+        m2 = wave_sum_xor(m2);
+        const float tot = (float)a.n * (float)cnt;
+        if (lane == 0) {
+            float* st = a.stats + (size_t)d * a.SS;
+            st[mean_at + c] = mean;
+            st[rstd_at + c] = 1.0f / sqrtf(m2 / tot + eps);
+            run_mean[c] = (1.0f - mom) * run_mean[c] + mom * mean;
+            run_var[c] = (1.0f - mom) * run_var[c] + mom * (m2 / (tot - 1.0f));
+        }
+    }
+}
+
+// eval form: bn0, bn1 and bn2 normalise with the running buffers
+__global__ void __launch_bounds__(256) k_acre_stats_eval(AcArgs a, float eps0, float eps1, float eps2, const float* __restrict__ rm0,
+                                                         const float* __restrict__ rv0, const float* __restrict__ rm1,
+                                                         const float* __restrict__ rv1, const float* __restrict__ rm2,
+                                                         const float* __restrict__ rv2) {
+    const int t0 = (int)blockIdx.x * 256 + threadIdx.x;
+    for (int d = 0; d < a.dirs; ++d) {
+        float* st = a.stats + (size_t)d * a.SS;
+        for (int t = t0; t < 1 + a.C + a.K; t += (int)gridDim.x * 256) {
+            if (t < 1) { st[0] = rm0[0]; st[1] = 1.0f / sqrtf(rv0[0] + eps0); }
+            else if (t < 1 + a.C) { const int c = t - 1; st[a.o1 + c] = rm1[c]; st[a.o1 + a.C + c] = 1.0f / sqrtf(rv1[c] + eps1); }
+            else { const int j = t - 1 - a.C; st[a.o2 + j] = rm2[j]; st[a.o2 + a.K + j] = 1.0f / sqrtf(rv2[j] + eps2); }
+        }
+    }
+}
+
+// y0 = bn0(img) * m0 of row gr as 400 floats in LDS.  All 256 threads; ends with a barrier
+__device__ __forceinline__ void ac_load_y0(const AcArgs& a, const float* __restrict__ st, const int64_t* __restrict__ e,
+                                           const int64_t* __restrict__ r, int64_t gr, float* __restrict__ y0s) {
+    const float mean0 = st[0], g0 = st[1] * a.w0[0], b0 = a.b0[0];
+    const float* __restrict__ er = a.ent + e[gr] * a.K;
+    const float* __restrict__ rr = a.rel + r[gr] * a.K;
+    for (int pix = threadIdx.x; pix < kAcHW; pix += 256)
+        y0s[pix] = ((ac_comb(a, er, rr, pix) - mean0) * g0 + b0) * ac_factor(a, 0, pix, gr);
+    __syncthreads();
+}
+// the C channels of row gr of a stored layer [N, F] into LDS with channel stride kAcLS.  All 256 threads; ends with a barrier
+__device__ __forceinline__ void ac_load_layer(const AcArgs& a, const float* __restrict__ src, int64_t gr, float* __restrict__ ls) {
+    const float* __restrict__ s = src + gr * a.F;
+    for (int idx = threadIdx.x; idx < a.F; idx += 256) { const int ch = idx / kAcHW; ls[ch * kAcLS + (idx - ch * kAcHW)] = s[idx]; }
+    __syncthreads();
+}
+
+// one workgroup per row, one wave per output channel: out[o, pos] = b[o] + sum_t w[o, t] y0[pos + tap t], layer L's filter and dilation
+__global__ void __launch_bounds__(256) k_acre_conv1(AcArgs a, int L, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
+                                                    float* __restrict__ out) {
+    __shared__ float y0s[kAcHW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gr = blockIdx.x;
+    ac_load_y0(a, ac_stats(a, (int)(gr / a.n)), e, r, gr, y0s);
+    const int d = a.dil[L];
+    for (int o = wave; o < a.C; o += 4) {
+        float w[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) w[t] = a.cw[L][o * 9 + t];
+        const float bias = a.cb[L] ? a.cb[L][o] : 0.0f;
+        float* __restrict__ dst = out + gr * a.F + (int64_t)o * kAcHW;
+        for (int pos = lane; pos < kAcHW; pos += 64) {
+            float v = bias;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int sp = ac_tap(pos, t, d);
+                v += w[t] * (sp >= 0 ? y0s[sp] : 0.0f);
+            }
+            dst[pos] = v;
+        }
+    }
+}
+
+// one workgroup per row: the C -> C dilated convolution of layer L as an implicit GEMM.  The input layer sits in LDS; wave w owns the
+// position tiles w, w + 4, ... (16 positions each, at most kAcPT) for every block of 16 output channels.  Operands of one
+// v_mfma_f32_16x16x4_f32: A[m = channel l][k = input channel g] = the filter value of tap t, B[k = g][n = position l] = the input at the
+// tap's place or 0 in the padding; the contraction runs over the taps and the input channels in blocks of 4.
+// BWD = false: out[o, pos] = b[o] + sum_{i, t} w[o, i, t] in[i, pos + tap t]  (+ y0[pos] when addres: the residual)
+// BWD = true:  out[i, pos] = sum_{o, t} w[o, i, t] in[o, pos - tap t]: the filter transposed and flipped (tap 8 - t), no bias
+template <bool BWD>
+__global__ void __launch_bounds__(256) k_acre_cc(AcArgs a, int L, int addres, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
+                                                 const float* __restrict__ in, float* __restrict__ out) {
+    __shared__ float ls[kAcMaxC * kAcLS];
+    __shared__ float y0s[kAcHW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int64_t gr = blockIdx.x;
+    if (addres) ac_load_y0(a, ac_stats(a, (int)(gr / a.n)), e, r, gr, y0s);
+    ac_load_layer(a, in, gr, ls);
+    const int d = a.dil[L], C = a.C;
+    const float* __restrict__ w = a.cw[L];
+    for (int ot = 0; ot < (C + 15) / 16; ++ot) {
+        const int ol = 16 * ot + l;          // the A operand's channel
+        const bool olok = ol < C;
+        f32x4v acc[kAcPT];
+#pragma unroll
+        for (int j = 0; j < kAcPT; ++j) acc[j] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < 9; ++t) {
+            int sp[kAcPT];
+#pragma unroll
+            for (int j = 0; j < kAcPT; ++j) {
+                const int pt = wave + 4 * j;
+                sp[j] = pt < kAcHW / 16 ? ac_tap(16 * pt + l, t, d) : -1;
+            }
+            for (int i0 = 0; i0 < C; i0 += 4) {
+                const int i = i0 + g;
+                const bool iok = i < C;
+                const int ic = iok ? i : C - 1;
+                float av = 0.0f;
+                if (olok && iok) av = BWD ? w[(i * C + ol) * 9 + (8 - t)] : w[(ol * C + i) * 9 + t];
+                const float* __restrict__ lrow = ls + ic * kAcLS;
+#pragma unroll
+                for (int j = 0; j < kAcPT; ++j) {
+                    if (wave + 4 * j >= kAcHW / 16) continue;   // (wave-uniform)
+                    const float bv = (iok && sp[j] >= 0) ? lrow[sp[j] >= 0 ? sp[j] : 0] : 0.0f;
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kAcPT; ++j) {
+            const int pt = wave + 4 * j;
+            if (pt >= kAcHW / 16) continue;
+            const int pos = 16 * pt + l;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int o = 16 * ot + 4 * g + q;
+                if (o >= C) continue;
+                float v = acc[j][q];
+                if constexpr (!BWD) {
+                    if (a.cb[L]) v += a.cb[L][o];
+                    if (addres) v += y0s[pos];
+                }
+                out[gr * a.F + (int64_t)o * kAcHW + pos] = v;
+            }
+        }
+    }
+}
+
+// one wave per (row, channel): the channel's (mean, M2) over the row's 400 values of c -> part[row][C], and its feature-map factor
+__global__ void __launch_bounds__(256) k_acre_c_stats(AcArgs a, const float* __restrict__ c, float2* __restrict__ part, float* __restrict__ m1f) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gr = blockIdx.x;
+    for (int ch = (int)blockIdx.y * 4 + wave; ch < a.C; ch += 4 * (int)gridDim.y) {
+        const float* __restrict__ src = c + gr * a.F + (int64_t)ch * kAcHW;
+        float s = 0.0f;
+        for (int pos = lane; pos < kAcHW; pos += 64) s += src[pos];
+        const float mean = wave_sum_xor(s) / (float)kAcHW;
+        float m2 = 0.0f;
+        for (int pos = lane; pos < kAcHW; pos += 64) { const float v = src[pos] - mean; m2 += v * v; }
+        m2 = wave_sum_xor(m2);
+        if (lane == 0) {
+            part[gr * a.C + ch] = make_float2(mean, m2);
+            m1f[gr * a.C + ch] = ac_factor(a, 1, ch, gr);
+        }
+    }
+}
+
+// y1 = bn1(c) before the relu, and A[row][f] = relu(y1) * m1, formed from the stored c
+__device__ __forceinline__ float ac_bn1(const AcArgs& a, const float* __restrict__ st, const float* __restrict__ conv, int64_t gr, int f, int ch) {
+    return (conv[gr * a.F + f] - st[a.o1 + ch]) * (st[a.o1 + a.C + ch] * a.w1[ch]) + a.b1[ch];
+}
+template <bool TRAIN>
+__device__ __forceinline__ float ac_feature(const AcArgs& a, const float* __restrict__ st, const float* __restrict__ conv,
+                                            const float* __restrict__ m1f, int64_t gr, int f) {
+    const int ch = f / a.HW;
+    float v = fmaxf(ac_bn1(a, st, conv, gr, f, ch), 0.0f);
+    if constexpr (TRAIN) v *= m1f[gr * a.C + ch];
+    return v;
+}
+
+// upart[split][row][j] = sum over the split's f of A[row][f] fc_w[j][f].  grid (dirs x row tiles, tiles of 64 j, splits of F): wave w
+// owns columns 16 (4 blockIdx.y + w) + l; the A tile of 64 rows x 128 f is staged in LDS in the layout read_blocks<4> reads.
+// (k_acre_fc, k_acre_fc_gw and k_acre_fc_da are the third copy of InteractE's fc kernels; DESIGN.md section 21 notes it.)
+template <bool TRAIN>
+__global__ void __launch_bounds__(256) k_acre_fc(AcArgs a, const float* __restrict__ conv, const float* __restrict__ m1f, int tiles, int f_per,
+                                                 float* __restrict__ upart) {
+    __shared__ float As[kAcKC * kAcStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int d = (int)blockIdx.x / tiles;
+    const int64_t b0 = (int64_t)((int)blockIdx.x % tiles) * kAcRows, gr0 = (int64_t)d * a.n + b0;
+    const float* __restrict__ st = ac_stats(a, d);
+    const int j = 16 * ((int)blockIdx.y * 4 + wave) + l, jc = min(j, a.K - 1);
+    const int f_lo = (int)blockIdx.z * f_per, f_hi = min(a.F, f_lo + f_per);
+    const float* __restrict__ wp = a.fcw + (int64_t)jc * a.F;
+    f32x4v acc[4];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) acc[mb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int fc0 = f_lo; fc0 < f_hi; fc0 += kAcKC) {
+        const int kn = min(kAcKC, f_hi - fc0), kn4 = (kn + 3) & ~3;
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < kAcKC * kAcRows; idx += 256) {
+            const int kl = idx & (kAcKC - 1), rl = idx >> 7;   // consecutive threads: consecutive f of one row
+            if (kl >= kn4) continue;
+            float v = 0.0f;
+            if (b0 + rl < a.n && kl < kn) v = ac_feature<TRAIN>(a, st, conv, m1f, gr0 + rl, fc0 + kl);
+            As[kl * kAcStride + 4 * (rl & 15) + (rl >> 4)] = v;
+        }
+        __syncthreads();
+        for (int s = 0; s < kn4; s += 4) {
+            const float b = wp[min(fc0 + s + g, a.F - 1)];   // (rows of As beyond the chunk are zero)
+            float av[4];
+            read_blocks<4>(&As[(s + g) * kAcStride], l, av);
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], b, acc[mb], 0, 0, 0);
+        }
+    }
+    if (j >= a.K) return;
+    float* __restrict__ dst = upart + (int64_t)blockIdx.z * a.n * a.dirs * a.K;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t b = b0 + 16 * mb + 4 * g + q;
+            if (b < a.n) dst[((int64_t)d * a.n + b) * a.K + j] = acc[mb][q];
+        }
+}
+
+// one wave per column j: u = fc_b + the partial tiles in split order (kept for the backward); training form: the column's bn2
+// statistics per direction over u * m2 (tail first, running buffers updated); x = relu(bn2(u * m2)), in the eval form with the
+// running statistics k_acre_stats_eval left in `stats`
+template <bool TRAIN>
+__global__ void __launch_bounds__(256) k_acre_fc_finish(AcArgs a, const float* __restrict__ upart, int splits, float eps, float mom,
+                                                        float* __restrict__ run_mean, float* __restrict__ run_var, float* __restrict__ u,
+                                                        float* __restrict__ x) {
+    const int lane = threadIdx.x & 63;
+    const int j = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= a.K) return;
+    const int64_t N = a.n * a.dirs;
+    const float bias = a.fcb[j];
+    for (int d = 0; d < a.dirs; ++d) {
+        float* st = a.stats + (size_t)d * a.SS;
+        float s = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) {
+            const int64_t gr = (int64_t)d * a.n + b;
+            float v = bias;
+            for (int sp = 0; sp < splits; ++sp) v += upart[((int64_t)sp * N + gr) * a.K + j];
+            u[gr * a.K + j] = v;
+            if constexpr (TRAIN) s += v * ac_factor(a, 2, j, gr);
+        }
+        float mean, rstd;
+        if constexpr (TRAIN) {
+            mean = wave_sum_xor(s) / (float)a.n;
+            float m2 = 0.0f;
+            for (int64_t b = lane; b < a.n; b += 64) {
+                const int64_t gr = (int64_t)d * a.n + b;
+                const float dv = u[gr * a.K + j] * ac_factor(a, 2, j, gr) - mean;   // (u: written by this lane above)
+                m2 += dv * dv;
+            }
+            m2 = wave_sum_xor(m2);
+            rstd = 1.0f / sqrtf(m2 / (float)a.n + eps);
+            if (lane == 0) {
+                st[a.o2 + j] = mean;
+                st[a.o2 + a.K + j] = rstd;
+                run_mean[j] = (1.0f - mom) * run_mean[j] + mom * mean;
+                run_var[j] = (1.0f - mom) * run_var[j] + mom * (m2 / ((float)a.n - 1.0f));
+            }
+        } else {
+            mean = st[a.o2 + j];
+            rstd = st[a.o2 + a.K + j];
+        }
+        const float gj = rstd * a.w2[j], bj = a.b2[j];
+        for (int64_t b = lane; b < a.n; b += 64) {
+            const int64_t gr = (int64_t)d * a.n + b;
+            float v = u[gr * a.K + j];
+            if constexpr (TRAIN) v *= ac_factor(a, 2, j, gr);
+            x[gr * a.K + j] = fmaxf((v - mean) * gj + bj, 0.0f);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ backward
+// one wave per column j, the directions in order: dy2 = dx [bn2 > 0]; S1 = sum dy2, S2 = sum dy2 xh2; du = w2 rstd (dy2 - S1 / n - xh2 S2 / n) m2
+__global__ void __launch_bounds__(256) k_acre_bn2_bwd(AcArgs a, const float* __restrict__ dx, const float* __restrict__ u, float* __restrict__ du,
+                                                      float* __restrict__ g_w2, float* __restrict__ g_b2, float* __restrict__ g_fcb) {
+    const int lane = threadIdx.x & 63;
+    const int j = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= a.K) return;
+    const float w2 = a.w2[j], b2 = a.b2[j];
+    for (int d = 0; d < a.dirs; ++d) {
+        const float* __restrict__ st = ac_stats(a, d);
+        const float mean = st[a.o2 + j], rstd = st[a.o2 + a.K + j];
+        float s1 = 0.0f, s2 = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) {
+            const int64_t gr = (int64_t)d * a.n + b;
+            const float xh = (u[gr * a.K + j] * ac_factor(a, 2, j, gr) - mean) * rstd;
+            const float dy = xh * w2 + b2 > 0.0f ? dx[gr * a.K + j] : 0.0f;
+            s1 += dy;
+            s2 += dy * xh;
+        }
+        s1 = wave_sum_xor(s1);
+        s2 = wave_sum_xor(s2);
+        const float inv = 1.0f / (float)a.n;
+        float sb = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) {
+            const int64_t gr = (int64_t)d * a.n + b;
+            const float m = ac_factor(a, 2, j, gr);
+            const float xh = (u[gr * a.K + j] * m - mean) * rstd;
+            const float dy = xh * w2 + b2 > 0.0f ? dx[gr * a.K + j] : 0.0f;
+            const float v = (w2 * rstd) * (dy - s1 * inv - xh * (s2 * inv)) * m;
+            du[gr * a.K + j] = v;
+            sb += v;
+        }
+        sb = wave_sum_xor(sb);
+        if (lane == 0) { g_w2[j] += s2; g_b2[j] += s1; g_fcb[j] += sb; }
+    }
+}
+
+// g_fc[j][f] += sum over ALL rows (both directions, in row order) of du[row][j] A[row][f].  grid (ceil(F / 64), ceil(K / 128)): wave w
+// owns the 16 f of block 4 blockIdx.x + w for the 128 j of blockIdx.y (8 accumulator blocks); the batch is the contraction.
+__global__ void __launch_bounds__(256) k_acre_fc_gw(AcArgs a, const float* __restrict__ conv, const float* __restrict__ m1f,
+                                                    const float* __restrict__ du, float* __restrict__ g_fc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int f = 16 * ((int)blockIdx.x * 4 + wave) + l;
+    if (f - l >= a.F) return;   // (wave-uniform)
+    const bool fok = f < a.F;
+    const int fcl = min(f, a.F - 1);
+    const int k0 = (int)blockIdx.y * 128;
+    const int nkb = min(8, (a.K - k0 + 15) / 16);
+    const int64_t N = a.n * a.dirs;
+    f32x4v acc[8];
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb) acc[kb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t r0 = 0; r0 < N; r0 += 4) {
+        const int64_t gr = r0 + g;
+        const bool ok = gr < N;
+        const int64_t grc = ok ? gr : N - 1;
+        const float v1 = ac_feature<true>(a, ac_stats(a, (int)(grc / a.n)), conv, m1f, grc, fcl);
+        const float A = ok && fok ? v1 : 0.0f;
+        const float* __restrict__ dp = du + grc * a.K;
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb)
+            if (kb < nkb) {
+                const int j = k0 + 16 * kb + l;
+                const float v = ok && j < a.K ? dp[min(j, a.K - 1)] : 0.0f;
+                acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(v, A, acc[kb], 0, 0, 0);
+            }
+    }
+    if (!fok) return;
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = k0 + 16 * kb + 4 * g + q;
+            if (kb < nkb && j < a.K) g_fc[(int64_t)j * a.F + f] += acc[kb][q];
+        }
+}
+
+// dy1[row][f] = (sum_j du[row][j] fc_w[j][f]) * m1 [bn1 > 0]: the gradient at bn1's output.  grid (dirs x row tiles, ceil(F / 64))
+__global__ void __launch_bounds__(256) k_acre_fc_da(AcArgs a, const float* __restrict__ conv, const float* __restrict__ m1f,
+                                                    const float* __restrict__ du, int tiles, float* __restrict__ dy1) {
+    __shared__ float As[kAcKC * kAcStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int d = (int)blockIdx.x / tiles;
+    const int64_t b0 = (int64_t)((int)blockIdx.x % tiles) * kAcRows, gr0 = (int64_t)d * a.n + b0;
+    const float* __restrict__ st = ac_stats(a, d);
+    const int f = 16 * ((int)blockIdx.y * 4 + wave) + l;
+    const bool live = f - l < a.F;   // (wave-uniform)
+    const int fcl = min(f, a.F - 1);
+    f32x4v acc[4];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) acc[mb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int j0 = 0; j0 < a.K; j0 += kAcKC) {
+        const int kn = min(kAcKC, a.K - j0), kn4 = (kn + 3) & ~3;
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < kAcKC * kAcRows; idx += 256) {
+            const int kl = idx & (kAcKC - 1), rl = idx >> 7;
+            if (kl >= kn4) continue;
+            float v = 0.0f;
+            if (b0 + rl < a.n && kl < kn) v = du[(gr0 + rl) * a.K + j0 + kl];
+            As[kl * kAcStride + 4 * (rl & 15) + (rl >> 4)] = v;
+        }
+        __syncthreads();
+        if (live)
+            for (int s = 0; s < kn4; s += 4) {
+                const float b = a.fcw[(int64_t)min(j0 + s + g, a.K - 1) * a.F + fcl];   // (rows of As beyond the chunk are zero)
+                float av[4];
+                read_blocks<4>(&As[(s + g) * kAcStride], l, av);
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], b, acc[mb], 0, 0, 0);
+            }
+    }
+    if (!live || f >= a.F) return;
+    const int ch = f / a.HW;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t b = b0 + 16 * mb + 4 * g + q;
+            if (b >= a.n) continue;
+            const int64_t gr = (int64_t)d * a.n + b;
+            const float keep = ac_bn1(a, st, conv, gr, f, ch) > 0.0f ? m1f[gr * a.C + ch] : 0.0f;
+            dy1[gr * a.F + f] = acc[mb][q] * keep;
+        }
+}
+
+// one wave per (row, channel): S1 = sum dy1, S2 = sum dy1 xh1 over the row's 400 outputs
+__global__ void __launch_bounds__(256) k_acre_bn1_part(AcArgs a, const float* __restrict__ conv, const float* __restrict__ dy1,
+                                                       float2* __restrict__ part) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gr = blockIdx.x;
+    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    for (int ch = (int)blockIdx.y * 4 + wave; ch < a.C; ch += 4 * (int)gridDim.y) {
+        const float mean = st[a.o1 + ch], rstd = st[a.o1 + a.C + ch];
+        const int64_t base = gr * a.F + (int64_t)ch * a.HW;
+        float s1 = 0.0f, s2 = 0.0f;
+        for (int pos = lane; pos < a.HW; pos += 64) {
+            const float dy = dy1[base + pos];
+            s1 += dy;
+            s2 += dy * ((conv[base + pos] - mean) * rstd);
+        }
+        s1 = wave_sum_xor(s1);
+        s2 = wave_sum_xor(s2);
+        if (lane == 0) part[gr * a.C + ch] = make_float2(s1, s2);
+    }
+}
+
+// one wave per channel, the directions in order: the two sums over the direction's rows -> sums[d][C], g_bn1
+__global__ void __launch_bounds__(256) k_acre_bn1_bwd_fin(AcArgs a, const float2* __restrict__ part, float2* __restrict__ sums,
+                                                          float* __restrict__ g_w1, float* __restrict__ g_b1) {
+    const int lane = threadIdx.x & 63;
+    const int ch = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ch >= a.C) return;
+    for (int d = 0; d < a.dirs; ++d) {
+        float s1 = 0.0f, s2 = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) {
+            const float2 v = part[((int64_t)d * a.n + b) * a.C + ch];
+            s1 += v.x;
+            s2 += v.y;
+        }
+        s1 = wave_sum_xor(s1);
+        s2 = wave_sum_xor(s2);
+        if (lane == 0) { sums[d * a.C + ch] = make_float2(s1, s2); g_w1[ch] += s2; g_b1[ch] += s1; }
+    }
+}
+
+// one wave per (row, channel): dc = w1 rstd1 (dy1 - S1 / N1 - xh1 S2 / N1), written over dy1 IN PLACE (a lane reads and writes its own
+// positions)
+__global__ void __launch_bounds__(256) k_acre_bn1_dc(AcArgs a, const float* __restrict__ conv, float* __restrict__ dy1,
+                                                     const float2* __restrict__ sums) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gr = blockIdx.x;
+    const int d = (int)(gr / a.n);
+    const float* __restrict__ st = ac_stats(a, d);
+    const float invN1 = 1.0f / ((float)a.n * (float)a.HW);
+    for (int ch = (int)blockIdx.y * 4 + wave; ch < a.C; ch += 4 * (int)gridDim.y) {
+        const float mean = st[a.o1 + ch], rstd = st[a.o1 + a.C + ch], gain = a.w1[ch] * rstd;
+        const float2 S = sums[d * a.C + ch];
+        const int64_t base = gr * a.F + (int64_t)ch * a.HW;
+        for (int pos = lane; pos < a.HW; pos += 64) {
+            const float xh = (conv[base + pos] - mean) * rstd;
+            dy1[base + pos] = gain * (dy1[base + pos] - S.x * invN1 - xh * (S.y * invN1));
+        }
+    }
+}
+
+// one workgroup per row: the filter partials of a C -> C layer, gwp[row][(o C + i) 9 + t] = sum_pos dz[o, pos] in[i, pos + tap t], and
+// gbp[row][o] = sum_pos dz[o, pos].  Both layers sit in LDS (103 424 bytes: one workgroup per compute unit).  A wave takes the
+// (tap, 16 o, 16 i) tiles wave, wave + 4, ...; operands of one v_mfma_f32_16x16x4_f32: A[m = o l][k = position g] = dz,
+// B[k = g][n = i l] = the input at the tap's place or 0; the 400 positions are the contraction, in blocks of 4, ascending
+__global__ void __launch_bounds__(256) k_acre_cc_gw(AcArgs a, int L, const float* __restrict__ dz, const float* __restrict__ in,
+                                                    float* __restrict__ gwp, float* __restrict__ gbp) {
+    __shared__ float dzs[kAcMaxC * kAcLS];
+    __shared__ float ins[kAcMaxC * kAcLS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int64_t gr = blockIdx.x;
+    const int d = a.dil[L], C = a.C, CT = (C + 15) / 16;
+    ac_load_layer(a, dz, gr, dzs);
+    ac_load_layer(a, in, gr, ins);
+    for (int task = wave; task < 9 * CT * CT; task += 4) {
+        const int t = task / (CT * CT), ot = (task / CT) % CT, it = task % CT;
+        const int ol = 16 * ot + l, il = 16 * it + l;
+        const bool ook = ol < C, iok = il < C;
+        const float* __restrict__ drow = dzs + (ook ? ol : 0) * kAcLS;
+        const float* __restrict__ irow = ins + (iok ? il : 0) * kAcLS;
+        f32x4v acc = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int p0 = 0; p0 < kAcHW; p0 += 4) {
+            const int pos = p0 + g, sp = ac_tap(pos, t, d);
+            const float av = ook ? drow[pos] : 0.0f;
+            const float bv = (iok && sp >= 0) ? irow[sp >= 0 ? sp : 0] : 0.0f;
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+        if (iok)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int o = 16 * ot + 4 * g + q;
+                if (o < C) gwp[gr * (int64_t)(9 * C * C) + (o * C + il) * 9 + t] = acc[q];
+            }
+    }
+    if (gbp)
+        for (int o = wave; o < C; o += 4) {
+            float s = 0.0f;
+            for (int pos = lane; pos < kAcHW; pos += 64) s += dzs[o * kAcLS + pos];
+            s = wave_sum_xor(s);
+            if (lane == 0) gbp[gr * C + o] = s;
+        }
+}
+
+// one workgroup per row, the 1 -> C layer L whose input is y0.  One wave per channel o: gwp[row][o 9 + t] = sum_pos dz[o, pos]
+// y0[pos + tap t] and gbp[row][o] = sum_pos dz[o, pos].  Then a thread per pixel: the transposed convolution sum_{o, t} w[o, t]
+// dz[o, pix - tap t] (o ascending) plus, with dc, the residual's gradient sum_ch dc[ch, pix] (ch ascending);
+// dy0 = that * m0 -> dimg[row][400]; (sum dy0, sum dy0 xh0) -> pt0[row]
+__global__ void __launch_bounds__(256) k_acre_c1_bwd(AcArgs a, int L, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
+                                                     const float* __restrict__ dz, const float* __restrict__ dc, float* __restrict__ gwp,
+                                                     float* __restrict__ gbp, float* __restrict__ dimg, float2* __restrict__ pt0) {
+    __shared__ float dzs[kAcMaxC * kAcLS];
+    __shared__ float y0s[kAcHW];
+    __shared__ float wl[kAcMaxC * 9];
+    __shared__ float red[8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gr = blockIdx.x;
+    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    const int d = a.dil[L], C = a.C;
+    for (int i = threadIdx.x; i < 9 * C; i += 256) wl[i] = a.cw[L][i];
+    ac_load_y0(a, st, e, r, gr, y0s);
+    ac_load_layer(a, dz, gr, dzs);
+    for (int o = wave; o < C; o += 4) {
+        const float* __restrict__ drow = dzs + o * kAcLS;
+        float sb = 0.0f;
+        for (int pos = lane; pos < kAcHW; pos += 64) sb += drow[pos];
+        sb = wave_sum_xor(sb);
+        if (lane == 0 && gbp) gbp[gr * C + o] = sb;
+        for (int t = 0; t < 9; ++t) {
+            float s = 0.0f;
+            for (int pos = lane; pos < kAcHW; pos += 64) {
+                const int sp = ac_tap(pos, t, d);
+                s += drow[pos] * (sp >= 0 ? y0s[sp] : 0.0f);
+            }
+            s = wave_sum_xor(s);
+            if (lane == 0) gwp[gr * (int64_t)(9 * C) + o * 9 + t] = s;
+        }
+    }
+    const float mean0 = st[0], rstd0 = st[1];
+    const float* __restrict__ er = a.ent + e[gr] * a.K;
+    const float* __restrict__ rr = a.rel + r[gr] * a.K;
+    float t1 = 0.0f, t2 = 0.0f;
+    for (int pix = threadIdx.x; pix < kAcHW; pix += 256) {
+        int sp[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) sp[t] = ac_tap(pix, 8 - t, d);   // pix - tap t
+        float v = 0.0f;
+        for (int o = 0; o < C; ++o) {
+            float s = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) s += wl[o * 9 + t] * (sp[t] >= 0 ? dzs[o * kAcLS + (sp[t] >= 0 ? sp[t] : 0)] : 0.0f);
+            v += s;
+        }
+        if (dc) {
+            float rs = 0.0f;
+            for (int ch = 0; ch < C; ++ch) rs += dc[gr * a.F + (int64_t)ch * kAcHW + pix];
+            v += rs;
+        }
+        v *= ac_factor(a, 0, pix, gr);
+        dimg[gr * kAcHW + pix] = v;
+        t1 += v;
+        t2 += v * ((ac_comb(a, er, rr, pix) - mean0) * rstd0);
+    }
+    t1 = wave_sum_xor(t1);
+    t2 = wave_sum_xor(t2);
+    if (lane == 0) { red[wave] = t1; red[4 + wave] = t2; }
+    __syncthreads();
+    if (threadIdx.x == 0) pt0[gr] = make_float2(((red[0] + red[1]) + red[2]) + red[3], ((red[4] + red[5]) + red[6]) + red[7]);
+}
+
+// dst[i] += sum over the N rows of src[row][i], i < width.  A workgroup owns 16 consecutive i; thread (s, i) adds the rows s, s + 16,
+// ... in order, and the 16 class sums are added as a fixed tree
+__global__ void __launch_bounds__(256) k_acre_rowsum(const float* __restrict__ src, int64_t N, int width, float* __restrict__ dst) {
+    __shared__ float part[16][17];
+    const int il = threadIdx.x & 15, s = threadIdx.x >> 4;
+    const int i = (int)blockIdx.x * 16 + il;
+    float v = 0.0f;
+    if (i < width)
+        for (int64_t row = s; row < N; row += 16) v += src[row * width + i];
+    part[s][il] = v;
+    __syncthreads();
+    if (s == 0 && i < width) {
+        float q[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) q[k] = part[k][il];
+#pragma unroll
+        for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+            for (int k = 0; k < w; ++k) q[k] = q[k] + q[k + w];
+        dst[i] += q[0];
+    }
+}
+
+// one wave: bn0's two sums per direction over the rows' partials -> t0[d], g_bn0
+__global__ void __launch_bounds__(64) k_acre_bn0_fin(AcArgs a, const float2* __restrict__ pt0, float2* __restrict__ t0, float* __restrict__ g_w0,
+                                                     float* __restrict__ g_b0) {
+    const int lane = threadIdx.x;
+    for (int d = 0; d < a.dirs; ++d) {
+        float s1 = 0.0f, s2 = 0.0f;
+        for (int64_t b = lane; b < a.n; b += 64) { const float2 v = pt0[(int64_t)d * a.n + b]; s1 += v.x; s2 += v.y; }
+        s1 = wave_sum_xor(s1);
+        s2 = wave_sum_xor(s2);
+        if (lane == 0) { t0[d] = make_float2(s1, s2); g_w0[0] += s2; g_b0[0] += s1; }
+    }
+}
+
+// one workgroup per row: bn0's backward of dy0 -> dent[row][j] (j < K) | drel[row][j - K]
+__global__ void __launch_bounds__(256) k_acre_dcomb(AcArgs a, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
+                                                    const float* __restrict__ dimg, const float2* __restrict__ t0, float* __restrict__ dent,
+                                                    float* __restrict__ drel) {
+    const int64_t gr = blockIdx.x;
+    const int d = (int)(gr / a.n);
+    const float* __restrict__ st = ac_stats(a, d);
+    const float* __restrict__ er = a.ent + e[gr] * a.K;
+    const float* __restrict__ rr = a.rel + r[gr] * a.K;
+    const float inv = 1.0f / ((float)a.n * (float)a.HW);
+    const float mean0 = st[0], rstd0 = st[1];
+    const float2 T = t0[d];
+    for (int j = threadIdx.x; j < a.HW; j += 256) {
+        const float xh = (ac_comb(a, er, rr, j) - mean0) * rstd0;
+        const float v = (a.w0[0] * rstd0) * (dimg[gr * a.HW + j] - T.x * inv - xh * (T.y * inv));
+        if (j < a.K) dent[gr * a.K + j] = v;
+        else drel[gr * a.K + j - a.K] = v;
+    }
+}
+
+// dst[ids[b]][0 .. width) += src[b * width .. + width) for every row b (id 0 included: no padding_idx), in row order and without
+// atomics: the wave of the FIRST row that names an id owns that id, walks the later rows 64 at a time (ballot) and adds their shares
+// in order
+__global__ void __launch_bounds__(256) k_acre_scatter(const int64_t* __restrict__ ids, int64_t n, int width, const float* __restrict__ src,
+                                                      float* __restrict__ dst) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const int64_t id = ids[row];
+    bool dup = false;
+    for (int64_t b = lane; b < row; b += 64) dup |= ids[b] == id;
+    if (__any(dup)) return;   // (wave-uniform)
+    for (int c0 = 0; c0 < width; c0 += 64) {
+        const int c = c0 + lane;
+        float sum = 0.0f;
+        for (int64_t b0 = row & ~(int64_t)63; b0 < n; b0 += 64) {
+            const int64_t b = b0 + lane;
+            unsigned long long m = __ballot(b >= row && b < n && ids[b] == id);
+            while (m) {
+                const int64_t s = b0 + __builtin_ctzll(m);
+                m &= m - 1;
+                if (c < width) sum += src[s * width + c];
+            }
+        }
+        if (c < width) dst[id * width + c] += sum;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host side
+static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
+    if (!d) { set_error("%s: null descriptor", who); return -1; }
+    const void* t[] = {d->bias, d->ent, d->rel, d->bn0_w, d->bn0_b, d->bn1_w, d->bn1_b, d->bn2_w, d->bn2_b, d->fc_w, d->fc_b,
+                       d->conv1_w, d->conv2_w, d->conv3_w, d->bn0_mean, d->bn0_var, d->bn1_mean, d->bn1_var, d->bn2_mean, d->bn2_var};
+    for (const void* p : t)
+        if (!p) { set_error("%s: null tables (the parameters of the way and the six running buffers are all required)", who); return -1; }
+    if (d->tot_entity <= 0 || d->tot_relation <= 0 || d->hidden_size <= 0 || d->in_channels <= 0) {
+        set_error("%s: tot_entity, tot_relation, hidden_size and in_channels must be positive (got %lld, %lld, %d, %d)", who,
+                  (long long)d->tot_entity, (long long)d->tot_relation, d->hidden_size, d->in_channels);
+        return -1;
+    }
+    if (d->hidden_size != kAcK) {
+        set_error("%s: hidden_size = %d must be 200 (the model views every embedding as 10 x 20)", who, d->hidden_size);
+        return -1;
+    }
+    if (d->way != 0 && d->way != 1) { set_error("%s: way = %d must be 0 (serial) or 1 (parallel)", who, d->way); return -1; }
+    const int dil[3] = {d->first_atrous, d->second_atrous, d->third_atrous};
+    for (int i = 0; i < 3; ++i)
+        if (dil[i] < 1 || dil[i] > KGE_ACRE_MAX_ATROUS) {
+            set_error("%s: dilation %d = %d must be in [1, %d]", who, i + 1, dil[i], KGE_ACRE_MAX_ATROUS);
+            return -1;
+        }
+    if (d->in_channels > kAcMaxC) {
+        set_error("%s: in_channels = %d exceeds %d (a layer of in_channels x 400 values is held in LDS)", who, d->in_channels, kAcMaxC);
+        return -1;
+    }
+    const bool cb = d->conv1_b && d->conv2_b && d->conv3_b, nocb = !d->conv1_b && !d->conv2_b && !d->conv3_b;
+    if (d->acre_bias ? !cb : !nocb) {
+        set_error("%s: the convolution bias pointers must all be set with acre_bias = 1 and all be NULL with acre_bias = 0", who);
+        return -1;
+    }
+    const bool gate = d->gate_w && d->gate_b, nogate = !d->gate_w && !d->gate_b;
+    if (d->way ? !gate : !nogate) {
+        set_error("%s: the gate pointers must both be set in the parallel way and both be NULL in the serial way", who);
+        return -1;
+    }
+    if (d->way == 1) {
+        set_error("%s: the parallel way (way = 1) has not been built on this path; the serial way is", who);
+        return -1;
+    }
+    for (int i = 0; i < 3; ++i) {
+        if (!(d->momentum[i] > 0.0f && d->momentum[i] <= 1.0f)) {
+            set_error("%s: momentum %d must be in (0, 1] (got %g; the cumulative average is not built)", who, i, (double)d->momentum[i]);
+            return -1;
+        }
+        if (!(d->eps[i] >= 0.0f)) { set_error("%s: eps %d must not be negative (got %g)", who, i, (double)d->eps[i]); return -1; }
+    }
+    const float p[3] = {d->input_dropout, d->feature_map_dropout, d->hidden_dropout};
+    if (drop_check(who, p, 3, d->offset)) return -1;
+    if (grads) {
+        const void* g[] = {d->g_bias, d->g_ent, d->g_rel, d->g_bn0_w, d->g_bn0_b, d->g_bn1_w, d->g_bn1_b, d->g_bn2_w, d->g_bn2_b, d->g_fc_w,
+                           d->g_fc_b, d->g_conv1_w, d->g_conv2_w, d->g_conv3_w};
+        for (const void* q : g)
+            if (!q) { set_error("%s: null gradient buffers (one per parameter of the way is required)", who); return -1; }
+        if (d->acre_bias && (!d->g_conv1_b || !d->g_conv2_b || !d->g_conv3_b)) {
+            set_error("%s: null gradient buffers (one per parameter of the way is required)", who);
+            return -1;
+        }
+    }
+    return 0;
+}
+// rows per direction of a call in training form
+static int ac_check_rows(const kge_acre_desc* d, const char* who, int64_t n) {
+    if (d->train && n == 1) {
+        set_error("%s: batch norm in training form needs more than one row per direction (got n = 1)", who);
+        return -1;
+    }
+    return 0;
+}
+
+static int ac_ss(const kge_acre_desc* d) { return 2 + 2 * d->in_channels + 2 * kAcK; }
+static int ac_f(const kge_acre_desc* d) { return d->in_channels * kAcHW; }
+
+static AcArgs ac_args(const kge_acre_desc* d, int64_t n, int dirs, int64_t row0, float* stats) {
+    AcArgs a{};
+    a.ent = d->ent; a.rel = d->rel; a.w0 = d->bn0_w; a.b0 = d->bn0_b; a.w1 = d->bn1_w; a.b1 = d->bn1_b; a.w2 = d->bn2_w; a.b2 = d->bn2_b;
+    a.fcw = d->fc_w; a.fcb = d->fc_b;
+    a.cw[0] = d->conv1_w; a.cw[1] = d->conv2_w; a.cw[2] = d->conv3_w;
+    a.cb[0] = d->conv1_b; a.cb[1] = d->conv2_b; a.cb[2] = d->conv3_b;
+    a.dil[0] = d->first_atrous; a.dil[1] = d->second_atrous; a.dil[2] = d->third_atrous;
+    a.K = kAcK; a.HW = kAcHW; a.C = d->in_channels; a.F = ac_f(d);
+    a.SS = ac_ss(d); a.o1 = 2; a.o2 = 2 + 2 * a.C;
+    a.dirs = dirs; a.n = n; a.row0 = (uint32_t)row0;
+    a.key = drop_key(d->seed, d->offset);
+    const float p[3] = {d->input_dropout, d->feature_map_dropout, d->hidden_dropout};
+    for (int i = 0; i < 3; ++i) {
+        a.on[i] = d->train != 0 && p[i] > 0.0f;
+        a.thr[i] = drop_thr(p[i]);
+        a.scale[i] = drop_scale(p[i]);
+    }
+    a.stats = stats;
+    return a;
+}
+
+static int ac_tiles(int64_t n) { return (int)((n + kAcRows - 1) / kAcRows); }
+// f handled by one workgroup of the fc forward: enough workgroups to fill the device, a function of the shapes alone (the split order
+// is the summation order); a multiple of 4
+static int ac_f_per(int F, int64_t n, int dirs) {
+    const int64_t base = (int64_t)dirs * ac_tiles(n) * ((kAcK + 63) / 64);
+    int64_t splits = (512 + base - 1) / base;
+    if (splits > 64) splits = 64;
+    if (splits < 1) splits = 1;
+    int per = (int)((F + splits - 1) / splits);
+    per = (per + 3) & ~3;
+    return per < 4 ? 4 : per;
+}
+static int ac_splits(int F, int per) { return (F + per - 1) / per; }
+
+// saved (floats): c [N, F] | z1 [N, F] | z2 [N, F] | u [N, K] | m1f [N, C] | stats [dirs][2 + 2C + 2K]
+static size_t ac_saved_floats(const kge_acre_desc* d, int64_t n, int dirs) {
+    return (size_t)dirs * ((size_t)n * ((size_t)3 * ac_f(d) + kAcK + d->in_channels) + ac_ss(d));
+}
+static size_t ac_part_bytes(const kge_acre_desc* d, size_t N) { return align256(N * (d->in_channels > 2 ? d->in_channels : 2) * sizeof(float2)); }
+// forward: row partials float2 [N, max(C, 2)] (bn0's are double2 [N]) | upart [splits, N, K]
+static size_t ac_fwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
+    const size_t N = (size_t)n * dirs;
+    const int F = ac_f(d);
+    return ac_part_bytes(d, N) + align256((size_t)ac_splits(F, ac_f_per(F, n, dirs)) * N * kAcK * sizeof(float));
+}
+// backward: du [N, K] | dy1 = dc [N, F] | dza [N, F] | dzb [N, F] | part1 float2 [N, C] | sums float2 [dirs, C] | gwp3 [N, 9 C C] |
+// gwp2 [N, 9 C C] | gwp1 [N, 9 C] | gbp [3][N, C] | dimg [N, 400] | dent [N, K] | drel [N, K] | pt0 float2 [N] | t0 float2 [dirs]
+struct AcBwdPlan {
+    size_t du, dy1, dza, dzb, part1, sums, gwp3, gwp2, gwp1, gbp, dimg, dent, drel, pt0, t0, total;
+};
+static AcBwdPlan ac_bwd_plan(const kge_acre_desc* d, int64_t n, int dirs) {
+    const size_t N = (size_t)n * dirs, C = (size_t)d->in_channels, F = (size_t)ac_f(d);
+    AcBwdPlan p{};
+    p.du = 0;
+    p.dy1 = p.du + align256(N * kAcK * sizeof(float));
+    p.dza = p.dy1 + align256(N * F * sizeof(float));
+    p.dzb = p.dza + align256(N * F * sizeof(float));
+    p.part1 = p.dzb + align256(N * F * sizeof(float));
+    p.sums = p.part1 + align256(N * C * sizeof(float2));
+    p.gwp3 = p.sums + align256((size_t)dirs * C * sizeof(float2));
+    p.gwp2 = p.gwp3 + align256(N * 9 * C * C * sizeof(float));
+    p.gwp1 = p.gwp2 + align256(N * 9 * C * C * sizeof(float));
+    p.gbp = p.gwp1 + align256(N * 9 * C * sizeof(float));
+    p.dimg = p.gbp + 3 * align256(N * C * sizeof(float));
+    p.dent = p.dimg + align256(N * kAcHW * sizeof(float));
+    p.drel = p.dent + align256(N * kAcK * sizeof(float));
+    p.pt0 = p.drel + align256(N * kAcK * sizeof(float));
+    p.t0 = p.pt0 + align256(N * sizeof(float2));
+    p.total = p.t0 + align256((size_t)dirs * sizeof(float2));
+    return p;
+}
+
+static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int64_t row0, float* x, float* saved,
+                      void* ws, hipStream_t st) {
+    const int64_t N = n * dirs;
+    const int C = d->in_channels, F = ac_f(d);
+    float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + N * F, *m1f = u + N * kAcK, *stats = m1f + N * C;
+    const AcArgs a = ac_args(d, n, dirs, row0, stats);
+    float2* part = (float2*)ws;
+    float* upart = (float*)((char*)ws + ac_part_bytes(d, (size_t)N));
+    const bool train = d->train != 0;
+    const int chan_groups = (C + 3) / 4 < 8 ? (C + 3) / 4 : 8;
+    if (train) {
+        hipLaunchKernelGGL(k_acre_row_stats, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a, e, r, (double2*)ws);
+        hipLaunchKernelGGL(k_acre_bn0_stats, dim3(1), dim3(64), 0, st, a, (const double2*)ws, d->eps[0], d->momentum[0], d->bn0_mean, d->bn0_var);
+    } else {
+        hipLaunchKernelGGL(k_acre_stats_eval, dim3((unsigned)((1 + C + kAcK + 255) / 256)), dim3(256), 0, st, a, d->eps[0], d->eps[1], d->eps[2],
+                           d->bn0_mean, d->bn0_var, d->bn1_mean, d->bn1_var, d->bn2_mean, d->bn2_var);
+    }
+    hipLaunchKernelGGL(k_acre_conv1, dim3((unsigned)N), dim3(256), 0, st, a, 0, e, r, z1);
+    hipLaunchKernelGGL((k_acre_cc<false>), dim3((unsigned)N), dim3(256), 0, st, a, 1, 0, e, r, z1, z2);
+    hipLaunchKernelGGL((k_acre_cc<false>), dim3((unsigned)N), dim3(256), 0, st, a, 2, 1, e, r, z2, c);
+    if (int rc = check_launch("k_acre_row_stats / k_acre_bn0_stats / k_acre_conv1 / k_acre_cc")) return rc;
+    if (train) {
+        hipLaunchKernelGGL(k_acre_c_stats, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, part, m1f);
+        hipLaunchKernelGGL(k_acre_bn_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part, C, C, kAcHW, a.o1, a.o1 + C, d->eps[1],
+                           d->momentum[1], d->bn1_mean, d->bn1_var);
+    }
+    const int per = ac_f_per(F, n, dirs), splits = ac_splits(F, per), tiles = ac_tiles(n);
+    const dim3 grid((unsigned)(dirs * tiles), (unsigned)((kAcK + 63) / 64), (unsigned)splits);
+    const unsigned col_blocks = (unsigned)((kAcK + 3) / 4);
+    if (train) {
+        hipLaunchKernelGGL((k_acre_fc<true>), grid, dim3(256), 0, st, a, c, m1f, tiles, per, upart);
+        hipLaunchKernelGGL((k_acre_fc_finish<true>), dim3(col_blocks), dim3(256), 0, st, a, upart, splits, d->eps[2], d->momentum[2], d->bn2_mean,
+                           d->bn2_var, u, x);
+    } else {
+        hipLaunchKernelGGL((k_acre_fc<false>), grid, dim3(256), 0, st, a, c, m1f, tiles, per, upart);
+        hipLaunchKernelGGL((k_acre_fc_finish<false>), dim3(col_blocks), dim3(256), 0, st, a, upart, splits, d->eps[2], d->momentum[2],
+                           d->bn2_mean, d->bn2_var, u, x);
+    }
+    return check_launch("k_acre_c_stats / k_acre_fc / k_acre_fc_finish");
+}
+
+static int ac_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int64_t row0, const float* dx,
+                       const float* saved, void* ws, hipStream_t st) {
+    const int64_t N = n * dirs;
+    const int C = d->in_channels, F = ac_f(d);
+    const float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + N * F, *m1f = u + N * kAcK;
+    const AcArgs a = ac_args(d, n, dirs, row0, const_cast<float*>(m1f + N * C));
+    const AcBwdPlan p = ac_bwd_plan(d, n, dirs);
+    char* w = (char*)ws;
+    float *du = (float*)(w + p.du), *dy1 = (float*)(w + p.dy1), *dza = (float*)(w + p.dza), *dzb = (float*)(w + p.dzb);
+    float *gwp3 = (float*)(w + p.gwp3), *gwp2 = (float*)(w + p.gwp2), *gwp1 = (float*)(w + p.gwp1), *dimg = (float*)(w + p.dimg);
+    float *dent = (float*)(w + p.dent), *drel = (float*)(w + p.drel);
+    const size_t gbs = align256((size_t)N * C * sizeof(float));
+    float* gbp[3] = {nullptr, nullptr, nullptr};
+    if (d->acre_bias)
+        for (int i = 0; i < 3; ++i) gbp[i] = (float*)(w + p.gbp + i * gbs);
+    float2 *part1 = (float2*)(w + p.part1), *sums = (float2*)(w + p.sums), *pt0 = (float2*)(w + p.pt0), *t0 = (float2*)(w + p.t0);
+    const unsigned row_blocks = (unsigned)((N + 3) / 4), col_blocks = (unsigned)((kAcK + 3) / 4);
+    const int tiles = ac_tiles(n);
+    const int chan_groups = (C + 3) / 4 < 8 ? (C + 3) / 4 : 8;
+    hipLaunchKernelGGL(k_acre_bn2_bwd, dim3(col_blocks), dim3(256), 0, st, a, dx, u, du, d->g_bn2_w, d->g_bn2_b, d->g_fc_b);
+    hipLaunchKernelGGL(k_acre_fc_gw, dim3((unsigned)((F + 63) / 64), (unsigned)((kAcK + 127) / 128)), dim3(256), 0, st, a, c, m1f, du, d->g_fc_w);
+    hipLaunchKernelGGL(k_acre_fc_da, dim3((unsigned)(dirs * tiles), (unsigned)((F + 63) / 64)), dim3(256), 0, st, a, c, m1f, du, tiles, dy1);
+    if (int rc = check_launch("k_acre_bn2_bwd / k_acre_fc_gw / k_acre_fc_da")) return rc;
+    hipLaunchKernelGGL(k_acre_bn1_part, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dy1, part1);
+    hipLaunchKernelGGL(k_acre_bn1_bwd_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part1, sums, d->g_bn1_w, d->g_bn1_b);
+    hipLaunchKernelGGL(k_acre_bn1_dc, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dy1, sums);
+    if (int rc = check_launch("k_acre_bn1_part / k_acre_bn1_bwd_fin / k_acre_bn1_dc")) return rc;
+    // dz3 = dc: conv3's partials against z2, dz2 = conv3^T dz3; conv2's against z1, dz1 = conv2^T dz2; conv1's against y0
+    hipLaunchKernelGGL(k_acre_cc_gw, dim3((unsigned)N), dim3(256), 0, st, a, 2, dy1, z2, gwp3, gbp[2]);
+    hipLaunchKernelGGL((k_acre_cc<true>), dim3((unsigned)N), dim3(256), 0, st, a, 2, 0, e, r, dy1, dza);
+    hipLaunchKernelGGL(k_acre_cc_gw, dim3((unsigned)N), dim3(256), 0, st, a, 1, dza, z1, gwp2, gbp[1]);
+    hipLaunchKernelGGL((k_acre_cc<true>), dim3((unsigned)N), dim3(256), 0, st, a, 1, 0, e, r, dza, dzb);
+    hipLaunchKernelGGL(k_acre_c1_bwd, dim3((unsigned)N), dim3(256), 0, st, a, 0, e, r, dzb, dy1, gwp1, gbp[0], dimg, pt0);
+    if (int rc = check_launch("k_acre_cc_gw / k_acre_cc / k_acre_c1_bwd")) return rc;
+    const int w9 = 9 * C * C;
+    hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((w9 + 15) / 16)), dim3(256), 0, st, gwp3, N, w9, d->g_conv3_w);
+    hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((w9 + 15) / 16)), dim3(256), 0, st, gwp2, N, w9, d->g_conv2_w);
+    hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((9 * C + 15) / 16)), dim3(256), 0, st, gwp1, N, 9 * C, d->g_conv1_w);
+    if (d->acre_bias) {
+        float* gb[3] = {d->g_conv1_b, d->g_conv2_b, d->g_conv3_b};
+        for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, gbp[i], N, C, gb[i]);
+    }
+    hipLaunchKernelGGL(k_acre_bn0_fin, dim3(1), dim3(64), 0, st, a, pt0, t0, d->g_bn0_w, d->g_bn0_b);
+    hipLaunchKernelGGL(k_acre_dcomb, dim3((unsigned)N), dim3(256), 0, st, a, e, r, dimg, t0, dent, drel);
+    if (int rc = check_launch("k_acre_rowsum / k_acre_bn0_fin / k_acre_dcomb")) return rc;
+    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, e, N, kAcK, dent, d->g_ent);
+    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, r, N, kAcK, drel, d->g_rel);
+    return check_launch("k_acre_scatter");
+}
+
+// the relation table has 2 tot_relation rows, every one an ordinary row
+static int ac_check_ids(const char* who, const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, hipStream_t s) {
+    return check_er_ids(who, d->tot_entity, 2 * d->tot_relation, e, r, n, s);
+}
+
+// fused step: ids [4B int64] | x [2B, K] | dx [2B, K] | saved | max(forward, backward, head)
+struct AcStepPlan {
+    size_t ids, x, dx, saved, rest, total;
+};
+static AcStepPlan ac_step_plan(const kge_acre_desc* d, int64_t B, int64_t n_hr, int64_t n_tr) {
+    AcStepPlan p{};
+    const size_t xb = align256((size_t)2 * B * kAcK * sizeof(float));
+    p.ids = 0;
+    p.x = align256((size_t)4 * B * sizeof(int64_t));
+    p.dx = p.x + xb;
+    p.saved = p.dx + xb;
+    p.rest = p.saved + align256(ac_saved_floats(d, B, 2) * sizeof(float));
+    size_t rest = ac_fwd_bytes(d, B, 2);
+    if (ac_bwd_plan(d, B, 2).total > rest) rest = ac_bwd_plan(d, B, 2).total;
+    const size_t h1 = kge_head_1n_bce_workspace_bytes(B, d->tot_entity, n_hr), h2 = kge_head_1n_bce_workspace_bytes(B, d->tot_entity, n_tr);
+    if (h1 > rest) rest = h1;
+    if (h2 > rest) rest = h2;
+    p.total = p.rest + align256(rest);
+    return p;
+}
+
+// the rank pass's body (kge_projection.hip): the eval form on the rows [h; t] as two directions; ws = saved | the forward's workspace
+static int ac_eval_body(const void* desc, const int64_t* e, const int64_t* r, int64_t n, float* x, void* ws, size_t, hipStream_t s) {
+    kge_acre_desc ev = *(const kge_acre_desc*)desc;
+    ev.train = 0;
+    const size_t saved = align256(ac_saved_floats(&ev, n, 2) * sizeof(float));
+    return ac_forward(&ev, e, r, n, 2, 0, x, (float*)ws, (char*)ws + saved, s);
+}
+static ProjectionEval ac_eval(const kge_acre_desc* d, int64_t n) {
+    const int64_t rows = n > 0 ? n : 1;
+    return ProjectionEval{kAcK, d->tot_entity, d->tot_relation, d->ent,
+                          align256(ac_saved_floats(d, rows, 2) * sizeof(float)) + ac_fwd_bytes(d, rows, 2), ac_eval_body, d->bias};
+}
+
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" {
+
+size_t kge_acre_saved_floats(const kge_acre_desc* d, int64_t n) {
+    return ac_check(d, "kge_acre_saved_floats", false) || n < 0 ? 0 : ac_saved_floats(d, n > 0 ? n : 1, 1);
+}
+
+size_t kge_acre_body_forward_workspace_bytes(const kge_acre_desc* d, int64_t n) {
+    return ac_check(d, "kge_acre_body_forward_workspace_bytes", false) || n < 0 ? 0 : ac_fwd_bytes(d, n > 0 ? n : 1, 1);
+}
+
+int kge_acre_body_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, float* x, float* saved,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "kge_acre_body_forward";
+    if (ac_check(d, who, false)) return -1;
+    if (n < 0 || (n > 0 && (!e || !r || !x || !saved)) || row0 < 0 || row0 + n > 0xffffffffLL) {
+        set_error("%s: bad arguments (row0 + n below 2^32)", who);
+        return -1;
+    }
+    if (ac_check_rows(d, who, n)) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ac_fwd_bytes(d, n > 0 ? n : 1, 1))) return -1;
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ac_check_ids(who, d, e, r, n, s)) return rc;
+    return ac_forward(d, e, r, n, 1, row0, x, saved, workspace, s);
+}
+
+size_t kge_acre_body_backward_workspace_bytes(const kge_acre_desc* d, int64_t n) {
+    return ac_check(d, "kge_acre_body_backward_workspace_bytes", false) || n < 0 ? 0 : ac_bwd_plan(d, n > 0 ? n : 1, 1).total;
+}
+
+int kge_acre_body_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, const float* dx,
+                           const float* saved, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "kge_acre_body_backward";
+    if (ac_check(d, who, true)) return -1;
+    if (n < 0 || (n > 0 && (!e || !r || !dx || !saved)) || row0 < 0 || row0 + n > 0xffffffffLL) {
+        set_error("%s: bad arguments (row0 + n below 2^32)", who);
+        return -1;
+    }
+    if (!d->train) { set_error("%s: the eval form (train = 0) has no backward", who); return -1; }
+    if (ac_check_rows(d, who, n)) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ac_bwd_plan(d, n > 0 ? n : 1, 1).total)) return -1;
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ac_check_ids(who, d, e, r, n, s)) return rc;
+    return ac_backward(d, e, r, n, 1, row0, dx, saved, workspace, s);
+}
+
+size_t kge_acre_train_bce_workspace_bytes(const kge_acre_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr) {
+    if (ac_check(d, "kge_acre_train_bce_workspace_bytes", false) || batch < 0 || n_hr < 0 || n_tr < 0) return 0;
+    return ac_step_plan(d, batch > 0 ? batch : 1, n_hr, n_tr).total;
+}
+
+int kge_acre_train_bce(const kge_acre_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch, const int64_t* hr_off,
+                       const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids, int64_t n_tr, float label_smoothing,
+                       void* workspace, size_t workspace_bytes, float* loss, void* stream) {
+    const char* who = "kge_acre_train_bce";
+    if (ac_check(d, who, true)) return -1;
+    if (batch < 0 || n_hr < 0 || n_tr < 0 || !loss || (batch > 0 && (!h || !r || !t || !hr_off || !tr_off)) || (n_hr > 0 && !hr_ids) ||
+        (n_tr > 0 && !tr_ids) || 2 * batch > 0xffffffffLL) {
+        set_error("%s: bad arguments", who);
+        return -1;
+    }
+    if (!d->train) { set_error("%s: the step is the training form (train = 0 has no backward)", who); return -1; }
+    if (ac_check_rows(d, who, batch)) return -1;
+    const AcStepPlan p = ac_step_plan(d, batch > 0 ? batch : 1, n_hr, n_tr);
+    if (ws_check(who, workspace, workspace_bytes, p.total)) return -1;
+    if (batch == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t B = batch, n = 2 * B;
+    const int k = kAcK;
+    char* ws = (char*)workspace;
+    int64_t* e = (int64_t*)(ws + p.ids);
+    int64_t* rr = e + n;
+    float *x = (float*)(ws + p.x), *dx = (float*)(ws + p.dx), *saved = (float*)(ws + p.saved);
+    void* rest = ws + p.rest;
+    const size_t rest_bytes = p.total - p.rest;
+    const size_t idb = (size_t)B * sizeof(int64_t);
+    if (hipMemcpyAsync(e, h, idb, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemcpyAsync(e + B, t, idb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(rr, r, idb, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemcpyAsync(rr + B, r, idb, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        set_error("%s: copying the row ids failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
+    if (int rc = ac_check_ids(who, d, e, rr, n, s)) return rc;
+    // tail direction = forward(h, r, "tail") on rows 0 .. B-1, head direction = forward(t, r, "head") on rows B .. 2B-1, in the same launches
+    if (int rc = ac_forward(d, e, rr, B, 2, 0, x, saved, rest, s)) return rc;
+    if (int rc = kge_head_1n_bce(x, B, k, d->ent, d->tot_entity, d->bias, hr_off, hr_ids, n_hr, label_smoothing, rest, rest_bytes, loss, dx, d->g_ent,
+                                 d->g_bias, stream)) return rc;
+    if (int rc = kge_head_1n_bce(x + B * k, B, k, d->ent, d->tot_entity, d->bias, tr_off, tr_ids, n_tr, label_smoothing, rest, rest_bytes, loss,
+                                 dx + B * k, d->g_ent, d->g_bias, stream)) return rc;
+    return ac_backward(d, e, rr, B, 2, 0, dx, saved, rest, s);
+}
+
+size_t kge_acre_eval_ranks_workspace_bytes(const kge_acre_desc* d, int64_t n) {
+    return ac_check(d, "kge_acre_eval_ranks_workspace_bytes", false) || n < 0 ? 0 : projection_eval_workspace_bytes(ac_eval(d, n), n);
+}
+
+int kge_acre_eval_ranks(const kge_acre_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                        const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks, int32_t* ties,
+                        void* stream) {
+    const char* who = "kge_acre_eval_ranks";
+    if (ac_check(d, who, false)) return -1;
+    return projection_eval_ranks(who, ac_eval(d, n), d, triples, n, tail_off, tail_ids, head_off, head_ids, workspace, workspace_bytes, ranks,
+                                 ties, stream);
+}
+
+}  // extern "C"

@@ -730,6 +730,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
         return hyper_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     if isinstance(desc, L.InteracteDesc):
         return interacte_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
+    if isinstance(desc, L.AcreDesc):
+        return acre_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     n = triples.shape[0]
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
@@ -1995,3 +1997,106 @@ def interacte_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smo
 def interacte_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
     """int32 [4, n] as eval_ranks, in one kge_interacte_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
     return _projection_eval_ranks("kge_interacte_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)
+
+
+# ---------------------------------------------------------------- AcrE (csrc/kge_acre.hip): its own descriptor and entry points
+ACRE_WAYS = {"serial": 0, "parallel": 1}
+
+
+def acre_shapes(tot_entity, tot_relation, in_channels, way, acre_bias):
+    """(names, shapes) of the parameters in state-dict order (bias first) for the way and acre_bias, and the shapes of the six running
+    buffers.  The serial way has 17 parameters with acre_bias and 11 + 3 without, the parallel way two more (the gate)."""
+    E, R, C, k = int(tot_entity), int(tot_relation), int(in_channels), 200
+    Cin = C if way == 0 else 1
+    names = ["bias", "ent", "rel", "bn0_w", "bn0_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "fc_w", "fc_b"]
+    shapes = [(E,), (E, k), (2 * R, k), (1,), (1,), (C,), (C,), (k,), (k,), (k, 400 * C), (k,)]
+    for i, cin in enumerate((1, Cin, Cin)):
+        names.append("conv%d_w" % (i + 1))
+        shapes.append((C, cin, 3, 3))
+        if acre_bias:
+            names.append("conv%d_b" % (i + 1))
+            shapes.append((C,))
+    if way == 1:
+        names += ["gate_w", "gate_b"]
+        shapes += [(400, 1600), (400,)]
+    return names, shapes, [(1,), (1,), (C,), (C,), (k,), (k,)]
+
+
+def acre_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, hidden_size=200, in_channels, way="serial", first_atrous=1,
+              second_atrous=2, third_atrous=2, acre_bias=True, dropouts=(0.0, 0.0, 0.0), eps=(1e-5, 1e-5, 1e-5), momentum=(0.1, 0.1, 0.1),
+              train=False, seed=0, offset=0):
+    """kge_acre_desc.  `tables` / `grads`: the model's parameters in state-dict order (bias, ent_embeddings.weight,
+    rel_embeddings.weight, bn0.weight, bn0.bias, bn1.weight, bn1.bias, bn2.weight, bn2.bias, fc.weight, fc.bias, conv1.weight,
+    [conv1.bias,] conv2.weight, [conv2.bias,] conv3.weight, [conv3.bias,] [W_gate_e.weight, W_gate_e.bias]): the conv biases are there iff
+    acre_bias, the gate iff way is "parallel"; `buffers`: the running mean / variance of bn0, bn1, bn2, which the training form updates
+    in place.  way: "serial" / "parallel" (or 0 / 1).  dropouts: (input, feature_map, hidden).  Shapes are checked here (the kernels
+    index by id and by shape without a bounds test) whenever the geometry is one the library accepts; the geometry, the rates, the
+    momenta and the offset are checked by the library, which refuses bad ones loudly."""
+    E, R, k, C = int(tot_entity), int(tot_relation), int(hidden_size), int(in_channels)
+    w = ACRE_WAYS.get(way, way)
+    if not isinstance(w, int):
+        raise L.KgeHipError("acre: way must be 'serial' or 'parallel' (got %r)" % (way,))
+    names, shapes, want_b = acre_shapes(E, R, max(C, 1), w, bool(acre_bias))
+    if len(tables) != len(names) or len(buffers) != 6:
+        raise L.KgeHipError("acre: %d tensors and 6 running buffers expected (way %r, acre_bias %r), got %d and %d"
+                            % (len(names), way, bool(acre_bias), len(tables), len(buffers)))
+    if any(m is None for m in momentum):
+        raise L.KgeHipError("acre: momentum None (the cumulative moving average) is not built")
+    if k == 200 and 1 <= C <= L.ACRE_MAX_CHANNELS and w in (0, 1):
+        _check_embeddings("acre", ("ent_embeddings", tables[1], E, k), ("rel_embeddings", tables[2], 2 * R, k))
+        for i, (name, t, shape) in enumerate(zip(names + list(L.ACRE_BUFFERS), list(tables) + list(buffers), shapes + want_b)):
+            if i not in (1, 2) and tuple(t.shape) != shape:
+                raise L.KgeHipError("acre: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
+    d = L.AcreDesc()
+    d.tot_entity, d.tot_relation, d.hidden_size, d.in_channels, d.way = E, R, k, C, w
+    d.first_atrous, d.second_atrous, d.third_atrous, d.acre_bias = int(first_atrous), int(second_atrous), int(third_atrous), int(bool(acre_bias))
+    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
+    _set_rng(d, train, seed, offset)
+    for i in range(3):
+        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
+    for name, t in zip(names + list(L.ACRE_BUFFERS), list(tables) + list(buffers)):
+        setattr(d, name, _dev(t, torch.float32, name).value)
+    if grads is not None:
+        if len(grads) != len(names):
+            raise L.KgeHipError("acre: %d gradient tensors expected, got %d" % (len(names), len(grads)))
+        _bind_grads(d, ["g_" + n for n in names], ["grad of " + n for n in names], grads, tables)
+    d._keepalive = (tables, buffers, grads)
+    d._ws = None
+    return d
+
+
+def acre_body_forward(desc, e, r, row0=0):
+    """(x float32 [n, 200], saved): the body of AcrE.forward on the rows (e_i, r_i) of one direction; the training form updates the
+    descriptor's running buffers once.  `saved` is what acre_body_backward reads."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    lib = L.load()
+    x = torch.empty((n, 200), dtype=torch.float32, device=e.device)
+    wp, wb = _desc_ws(desc, "kge_acre_body_forward_workspace_bytes", n)
+    saved = torch.empty(max(1, int(lib.kge_acre_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
+    L.check(lib.kge_acre_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(x, torch.float32, "x"),
+                                      _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_acre_body_forward")
+    return x, saved
+
+
+def acre_body_backward(desc, e, r, dx, saved, row0=0):
+    """g_* of the descriptor += the body's gradients given d loss / d x (same rows, row0, seed, offset and `saved` as the forward)."""
+    n = e.numel()
+    wp, wb = _desc_ws(desc, "kge_acre_body_backward_workspace_bytes", n)
+    L.check(L.load().kge_acre_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(dx, torch.float32, "dx"),
+                                            _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_acre_body_backward")
+
+
+def acre_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
+    """One train_step_projection of AcrE: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice
+    (tail direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
+    B, n_hr, n_tr, args = _label_csr_args("acre_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
+    wp, wb = _desc_ws(desc, "kge_acre_train_bce_workspace_bytes", B, n_hr, n_tr)
+    L.check(L.load().kge_acre_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+                                        _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_acre_train_bce")
+
+
+def acre_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks, in one kge_acre_eval_ranks call; ties: optional int32 [2, n] that receives the head's tie counts."""
+    return _projection_eval_ranks("kge_acre_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)

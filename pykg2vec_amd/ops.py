@@ -15,6 +15,8 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
   torch.ops.kge.hyper_body_backward(key, e, r, row0, seed, offset, dx, saved, weights) -> their dense gradients (b's is the head's: zero here; the lookup gradients of id 0 are dropped, padding_idx = 0)
   torch.ops.kge.interacte_body(key, e, r, row0, seed, offset, weights) -> (x float32 [N, k], saved)   the body of InteractE.forward (models/projection.py:425-442) up to the head; weights = its 12 tensors in state-dict order (bias and conv_filt first); the chequer permutations are the model's; row0 and the running-buffer write as in hyper_body: eager execution only
   torch.ops.kge.interacte_body_backward(key, e, r, row0, seed, offset, dx, saved, weights) -> their dense gradients (bias's is the head's: zero here)
+  torch.ops.kge.acre_body(key, e, r, row0, seed, offset, weights) -> (x float32 [N, 200], saved)   the body of AcrE.forward (models/projection.py:706-734) up to the head; weights = its parameters in state-dict order (bias first); the way and the dilations are the model's; row0 and the running-buffer write as in hyper_body: eager execution only
+  torch.ops.kge.acre_body_backward(key, e, r, row0, seed, offset, dx, saved, weights) -> their dense gradients (bias's is the head's: zero here)
   torch.ops.kge.one_to_n_scores(x, ent, bias, bf16) -> float32 [B, E]  the projection models' 1-N head (models/projection.py:100-102)
   torch.ops.kge.one_to_n_scores_backward(x, ent, preds, dpreds, need_bias) -> (dx, g_ent, g_bias)
 
@@ -389,6 +391,58 @@ def _interacte_backward(ctx, dx, _dsaved):
 
 
 interacte_body.register_autograd(_interacte_backward, setup_context=_interacte_setup)
+
+
+# AcrE's body (include/kge_hip.h: kge_acre_body_*).  As in kge::interacte_body there is one relation table, row0 = 0 for the tail
+# direction and n for the head direction, offset < 0 = the eval form, and the training form updates the model's running buffers, a
+# write outside the op's schema: eager execution only.  weights: the model's parameters in state-dict order (bias first; the conv
+# biases only with acre_bias, the gate only in the parallel way); the way and the dilations are the model's (found through `key`).
+@torch.library.custom_op("kge::acre_body", mutates_args=(), device_types="cuda")
+def acre_body(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
+    m = _model(key)
+    return K.acre_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                               r.contiguous(), row0=row0)
+
+
+@acre_body.register_fake
+def _(key, e, r, row0, seed, offset, weights):
+    n, k, C = e.numel(), weights[1].shape[1], weights[5].shape[0]
+    return weights[1].new_empty((n, k)), weights[1].new_empty((n * (3 * weights[9].shape[1] + k + C) + 2 + 2 * C + 2 * k,))
+
+
+@acre_body.register_kernel("cpu")
+def _(key, e, r, row0, seed, offset, weights):
+    raise L.KgeHipError("kge::acre_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
+
+
+@torch.library.custom_op("kge::acre_body_backward", mutates_args=(), device_types="cuda")
+def acre_body_backward(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
+                       weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.acre_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
+                         r.contiguous(), dx.contiguous(), saved, row0=row0)
+    return grads
+
+
+@acre_body_backward.register_fake
+def _(key, e, r, row0, seed, offset, dx, saved, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _acre_setup(ctx, inputs, output):
+    key, e, r, row0, seed, offset, weights = inputs
+    ctx.key, ctx.row0, ctx.seed, ctx.offset = key, row0, seed, offset
+    ctx.save_for_backward(e, r, output[1], *weights)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _acre_backward(ctx, dx, _dsaved):
+    e, r, saved, *weights = ctx.saved_tensors
+    return None, None, None, None, None, None, acre_body_backward(ctx.key, e, r, ctx.row0, ctx.seed, ctx.offset, dx, saved, weights)
+
+
+acre_body.register_autograd(_acre_backward, setup_context=_acre_setup)
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

@@ -5,8 +5,9 @@ ConvE: batch norm, a 3 x 3 convolution, a fully connected layer on the matrix co
 front of the head with its bias b; its torch layers are holders of parameters and buffers only.  HypER: the same stack with a
 convolution filter that a second linear layer computes per row from the relation embedding, and padding_idx = 0 on both tables
 (csrc/kge_hyper.hip).  InteractE: chequer permutations of [ent[e] | rel[r]], a depthwise convolution with circular padding whose
-filters the permutations share, and the same fc / batch-norm tail (csrc/kge_interacte.hip).  AcrE keeps its PyTorch layers and calls
-the head itself."""
+filters the permutations share, and the same fc / batch-norm tail (csrc/kge_interacte.hip).  AcrE: three dilated 3 x 3 convolutions
+chained with a residual, the two channel-mixing ones as implicit GEMMs on the matrix cores, and the same tail (csrc/kge_acre.hip); its
+parallel way is refused by the library."""
 import torch
 
 from . import _lib as L  # noqa: F401
@@ -385,6 +386,117 @@ class InteractE(ProjectionModel):
                 self.dropout_offset += 1
         x, _saved = torch.ops.kge.interacte_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
                                                  self.trainable_tensors())
+        if self.training:
+            self._count_batches(1)
+        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.bias, False)
+
+    def predict_tail_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
+        return rank
+
+    def predict_head_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
+        return rank
+
+
+class AcrE(ProjectionModel):
+    """projection.py:621-746.  forward(e, r, direction) = sigmoid(x @ ent.T + bias) with x = relu(bn2(hdrop(fc(flatten(fdrop(relu(bn1(
+    c))))))), y0 = idrop(bn0(img)), img the [10, 20] view of ent[e] stacked on that of rel[r] (hidden_size is 200 by construction), and
+    c = conv3(conv2(conv1(y0))) + y0 in the "serial" way: three 3 x 3 convolutions with dilations first / second / third_atrous and as
+    much zero padding, 1 -> in_channels -> in_channels -> in_channels, with no nonlinearity between them.  The "parallel" way (three
+    1 -> in_channels convolutions of y0 and a shared 1600 -> 400 gate) constructs, holds the reference's state and loads its
+    checkpoints, but its arithmetic is not built on this path: the library refuses it by name.  There is one relation table of
+    2 tot_relation rows: `direction` selects no relation row, only the mask rows.  The torch layers (bn0, bn1, bn2, fc, conv1, conv2,
+    conv3, W_gate_e) hold parameters and buffers only, so state_dict() has the reference's keys, order and shapes (the bare parameter
+    bias first) and loads a reference checkpoint; the arithmetic is csrc/kge_acre.hip.  Under train() a forward normalises with the
+    statistics of its own rows, updates the six running buffers and the three num_batches_tracked counters as torch does, and draws
+    the Philox masks of (dropout_seed, dropout_offset), the mask rows of the "head" direction following those of the "tail"
+    direction; with any rate > 0 it then advances dropout_offset by one.  Under eval() all three batch norms use the running buffers,
+    nothing is drawn and nothing is written."""
+    kernel_name = "acre"
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        param_list = ["tot_entity", "tot_relation", "hidden_size", "input_dropout", "hidden_dropout", "feature_map_dropout",
+                      "in_channels", "way", "first_atrous", "second_atrous", "third_atrous", "acre_bias"]
+        self.__dict__.update(self.load_params(param_list, kwargs))
+        k, C = int(self.hidden_size), int(self.in_channels)
+        # (the reference replaces the three rates by nn.Dropout modules inp_drop / feature_map_drop / hidden_drop; here they stay numbers)
+        self.dropouts = (float(self.input_dropout), float(self.feature_map_dropout), float(self.hidden_dropout))
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, k, padding_idx=None)
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation * 2, k, padding_idx=None)
+        self.bn0 = torch.nn.BatchNorm2d(1)
+        self.bn1 = torch.nn.BatchNorm2d(C)
+        self.bn2 = torch.nn.BatchNorm1d(k)
+        self.fc = torch.nn.Linear(C * 400, k)
+        self.padding = 0
+        a1, a2, a3, cb = int(self.first_atrous), int(self.second_atrous), int(self.third_atrous), bool(self.acre_bias)
+        Cin = C if self.way == "serial" else 1   # (as the reference: every way but "serial" is the parallel one)
+        self.conv1 = torch.nn.Conv2d(1, C, (3, 3), 1, a1, bias=cb, dilation=a1)
+        self.conv2 = torch.nn.Conv2d(Cin, C, (3, 3), 1, a2, bias=cb, dilation=a2)
+        self.conv3 = torch.nn.Conv2d(Cin, C, (3, 3), 1, a3, bias=cb, dilation=a3)
+        if self.way != "serial":
+            self.W_gate_e = torch.nn.Linear(1600, 400)
+        self.register_parameter("bias", torch.nn.Parameter(torch.zeros(self.tot_entity)))
+        torch.nn.init.xavier_uniform_(self.ent_embeddings.weight.data)
+        torch.nn.init.xavier_uniform_(self.rel_embeddings.weight.data)
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings]
+        self.loss = Criterion.multi_class_bce
+        self.dropout_seed = int(kwargs.get("seed", 0) or 0)
+        self.dropout_offset = 0
+
+    def _norms(self):
+        return (self.bn0, self.bn1, self.bn2)
+
+    def trainable_tensors(self):
+        """The parameters in state-dict order: the conv biases only with acre_bias, the gate only in the parallel way."""
+        t = [self.bias, self.ent_embeddings.weight, self.rel_embeddings.weight, self.bn0.weight, self.bn0.bias, self.bn1.weight,
+             self.bn1.bias, self.bn2.weight, self.bn2.bias, self.fc.weight, self.fc.bias]
+        for conv in (self.conv1, self.conv2, self.conv3):
+            t.append(conv.weight)
+            if conv.bias is not None:
+                t.append(conv.bias)
+        if self.way != "serial":
+            t += [self.W_gate_e.weight, self.W_gate_e.bias]
+        return t
+
+    def running_buffers(self):
+        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+
+    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        return K.acre_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
+                           tot_relation=self.tot_relation, hidden_size=int(self.hidden_size), in_channels=int(self.in_channels),
+                           way=0 if self.way == "serial" else 1, first_atrous=int(self.first_atrous),
+                           second_atrous=int(self.second_atrous), third_atrous=int(self.third_atrous), acre_bias=bool(self.acre_bias),
+                           dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()], momentum=[bn.momentum for bn in self._norms()],
+                           train=self.training if train is None else train, seed=self.dropout_seed if seed is None else seed,
+                           offset=self.dropout_offset if offset is None else offset)
+
+    def _count_batches(self, calls):
+        for bn in self._norms():
+            bn.num_batches_tracked += calls
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        K.acre_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
+        self._count_batches(2)   # the step is two training forwards
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def embed2(self, e, r):
+        return self.ent_embeddings(e), self.rel_embeddings(r)
+
+    def forward(self, e, r, direction="tail"):
+        assert direction in ("head", "tail"), "Unknown forward direction"
+        offset = -1   # eval(): running statistics, no dropout
+        if self.training:
+            offset = self.dropout_offset
+            if any(p > 0.0 for p in self.dropouts):
+                self.dropout_offset += 1
+        x, _saved = torch.ops.kge.acre_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
+                                            self.trainable_tensors())
         if self.training:
             self._count_batches(1)
         return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.bias, False)
