@@ -36,12 +36,13 @@ struct PullSampleArgs {
 };
 
 // one pair of the sampled batch: draw the corruption (same Philox counters as kge_sample_batch / the fused push kernels:
-// offset + pair index) and register the pair with the corrupting entity
+// offset + pair index) and register the pair with the corrupting entity.  The membership test takes a group of slots per round trip:
+// a sampler workgroup lives as long as the slowest lane of its slowest wave probes (profiles/r17_sampler_probe.md)
 __device__ __forceinline__ void pull_sample_one(const PullSampleArgs& sa, int64_t i) {
     const unsigned long long off = sa.cursor ? sa.offset + (unsigned long long)sa.cursor[1] : sa.offset;
     const int4 p = sa.pairs[i];
     int64_t nh, nt;
-    corrupt_one(p.x, p.y, p.z, sa.E, sa.bern, sa.slots, sa.mask, sa.seed, off + (unsigned long long)i, nh, nt);
+    corrupt_one<kSamplerProbeW>(p.x, p.y, p.z, sa.E, sa.bern, sa.slots, sa.mask, sa.seed, off + (unsigned long long)i, nh, nt);
     const bool tail = nh == p.x;
     const int c = (int)(tail ? nt : nh);
     const int pos = atomicAdd(sa.out.count + c, 1);

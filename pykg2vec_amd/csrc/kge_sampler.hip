@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_sample(SampleArgs a) {
         h = a.ph[i]; r = a.pr[i]; t = a.pt[i];
     }
     int64_t oh, ot;
-    corrupt_one(h, r, t, a.E, a.bern, a.slots, a.mask, a.seed, offset + (unsigned long long)j, oh, ot);
+    corrupt_one<kSamplerProbeW>(h, r, t, a.E, a.bern, a.slots, a.mask, a.seed, offset + (unsigned long long)j, oh, ot);
     if (a.layout == 0) {
         if (k == 0 && a.o0) { a.o0[i] = h; a.o1[i] = r; a.o2[i] = t; }
         a.o3[j] = oh; a.o4[j] = r; a.o5[j] = ot;

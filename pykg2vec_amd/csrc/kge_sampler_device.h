@@ -19,8 +19,9 @@ __host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long 
     return x;
 }
 
-__device__ __forceinline__ bool set_contains(const unsigned long long* __restrict__ slots, unsigned long long mask,
-                                             unsigned long long key) {
+// membership test, one slot per dependent load (the fused push kernels, which have no registers to spare for a wider one)
+__host__ __device__ __forceinline__ bool set_contains(const unsigned long long* __restrict__ slots, unsigned long long mask,
+                                                      unsigned long long key) {
     unsigned long long s = mix64(key) & mask;
     for (;;) {
         const unsigned long long v = slots[s];
@@ -29,6 +30,50 @@ __device__ __forceinline__ bool set_contains(const unsigned long long* __restric
         s = (s + 1) & mask;
     }
 }
+
+// The same test over the same table, one ALIGNED group of W slots per dependent round trip (W / 2 16-byte loads in flight together;
+// W = 8 is one 64-byte line).  The group is scanned in registers in probe order: slots in front of the home slot are ignored in the
+// first group only, the first slot equal to the key answers true, the first empty one false, otherwise the next group (wrapping with
+// the mask).  A run of linear probing is contiguous modulo the table size, so this visits the slots set_contains visits, in its
+// order, and returns what it returns for every table k_set_insert can produce.  The table is a power of two >= 16 slots and its
+// base is 16-byte aligned (an allocation of its own), so an aligned group of W <= 16 slots never leaves it.
+constexpr int kProbeMaxW = 16;
+template <int W>
+__host__ __device__ __forceinline__ bool set_contains_wide(const unsigned long long* __restrict__ slots, unsigned long long mask,
+                                                           unsigned long long key) {
+    static_assert(W >= 2 && W <= kProbeMaxW && (W & (W - 1)) == 0, "a group is a power of two of slots, at most the smallest table");
+    const unsigned long long home = mix64(key) & mask;
+    unsigned long long base = home & ~(unsigned long long)(W - 1);
+    unsigned live = ~0u << (unsigned)(home - base);   // bit j: slot j of the group takes part in the scan
+    for (;;) {
+        const ulonglong2* __restrict__ g = reinterpret_cast<const ulonglong2*>(slots + base);
+        ulonglong2 v[W / 2];
+#pragma unroll
+        for (int j = 0; j < W / 2; ++j) v[j] = g[j];   // all loads of the group before any compare
+        unsigned hit = 0u, stop = 0u;                  // bit j: slot j holds the key / ends the run (key or empty)
+#pragma unroll
+        for (int j = 0; j < W / 2; ++j) {
+            hit |= (v[j].x == key ? 1u : 0u) << (2 * j) | (v[j].y == key ? 2u : 0u) << (2 * j);
+            stop |= (v[j].x == kEmpty ? 1u : 0u) << (2 * j) | (v[j].y == kEmpty ? 2u : 0u) << (2 * j);
+        }
+        stop = (stop | hit) & live;
+        if (stop) return (hit & stop & (0u - stop)) != 0u;   // the first slot in probe order that ends the run
+        base = (base + W) & mask;
+        live = ~0u;
+    }
+}
+
+// W = 1: the one-slot probe; otherwise the grouped one
+template <int W>
+__host__ __device__ __forceinline__ bool set_probe(const unsigned long long* __restrict__ slots, unsigned long long mask,
+                                                   unsigned long long key) {
+    if constexpr (W == 1) return set_contains(slots, mask, key);
+    else return set_contains_wide<W>(slots, mask, key);
+}
+// group width of the kernels whose sampler is the whole kernel or a rider with registers to spare (k_sample, pull_sample_one).
+// Measured on the C1 step at 2 / 4 / 8 / 16 (profiles/r17_sampler_probe.md): 2, 4 and 8 are within 0.15 us of each other with 4 the
+// lowest in every round, 16 gives back 0.4 us of the 1.05 us gained.
+constexpr int kSamplerProbeW = 4;
 
 struct Philox {
     uint32_t c[4];
@@ -54,7 +99,8 @@ __host__ __device__ __forceinline__ Philox philox4x32_10(uint32_t c0, uint32_t c
 }
 
 // one corrupted triple for negative slot `ctr` of positive (h, r, t): Philox block a = 0, 1, 2, ... per attempt,
-// word 0 of block 0 decides head/tail, word 1 of each block is the candidate entity
+// word 0 of block 0 decides head/tail, word 1 of each block is the candidate entity.  W: slots per round trip of the membership test
+template <int W = 1>
 __device__ __forceinline__ void corrupt_one(int64_t h, int64_t r, int64_t t, int64_t E, const float* __restrict__ bern,
                                             const unsigned long long* __restrict__ slots, unsigned long long mask,
                                             unsigned long long seed, unsigned long long ctr, int64_t& oh, int64_t& ot) {
@@ -68,7 +114,7 @@ __device__ __forceinline__ void corrupt_one(int64_t h, int64_t r, int64_t t, int
     for (;;) {
         e = (int64_t)(((unsigned long long)x.c[1] * (unsigned long long)E) >> 32);  // uniform in [0,E)
         const unsigned long long key = corrupt_tail ? pack_triple(h, r, e) : pack_triple(e, r, t);
-        if (slots == nullptr || !set_contains(slots, mask, key)) break;
+        if (slots == nullptr || !set_probe<W>(slots, mask, key)) break;
         ++attempt;
         x = philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), attempt, 0u, k0, k1);
     }
