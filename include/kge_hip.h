@@ -1194,8 +1194,8 @@ int kge_interacte_eval_ranks(const kge_interacte_desc* d, const int64_t* triples
  * gradients, non-positive sizes, hidden_size != 200, way outside {0, 1}, a dilation below 1 or above KGE_ACRE_MAX_ATROUS,
  * in_channels above KGE_ACRE_MAX_CHANNELS (a layer of C x 400 values is held in static LDS), conv-bias or gate pointers inconsistent
  * with acre_bias / way, a momentum outside (0, 1], a negative eps, n = 1 with train = 1, a dropout rate outside [0, 1), an offset of
- * 2^62 or more, a workspace that is too small; the backward and the fused step also refuse train = 0.  The parallel way (way = 1)
- * is described here but not built: every entry point refuses it with a sentence that names it. */
+ * 2^62 or more, a workspace that is too small; the backward and the fused step also refuse train = 0.  Both ways are built
+ * behind the same entry points; kge_acre_saved_floats and the workspace sizes depend on the way. */
 #define KGE_ACRE_MAX_CHANNELS 32
 #define KGE_ACRE_MAX_ATROUS 4
 typedef struct kge_acre_desc {
@@ -1204,7 +1204,7 @@ typedef struct kge_acre_desc {
      * 72 offset, 80 eps, 92 momentum, 104 .. 248 the 19 tables, 256 .. 296 the six buffers, 304 .. 448 the 19 gradients; sizeof 456 */
     int64_t tot_entity, tot_relation;
     int32_t hidden_size, in_channels;
-    int32_t way;                                              /* 0 = serial, 1 = parallel */
+    int32_t way;                                              /* 0 = serial, 1 = parallel (both built) */
     int32_t first_atrous, second_atrous, third_atrous;
     int32_t acre_bias;                                        /* 0 / 1 */
     float input_dropout, feature_map_dropout, hidden_dropout; /* sites 0, 1, 2 */

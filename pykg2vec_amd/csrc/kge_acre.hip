@@ -1,6 +1,7 @@
 // kge_acre.hip -- the body of AcrE (models/projection.py:621-746) in front of the 1-N head of kge_head.hip.
 // K = hidden_size = 200, the image is always H x W = 20 x 20 (HW = 400 = 2K), C = in_channels, a1 / a2 / a3 the three dilations,
-// F = 400 C.  For a row with entity e and relation r, in the SERIAL way (way = 0; the parallel way is refused, see ac_check):
+// F = 400 C.  For a row with entity e and relation r, in the SERIAL way (way = 0; the PARALLEL way, way = 1, shares everything before
+// z1 and after c and is described at its kernels, k_acrp_*, below):
 //     img = [ent[e] | rel[r]] viewed [20, 20]                  ONE relation table [2R, K]; a direction selects nothing
 //     y0  = bn0(img) * m0                                      input dropout, site 0; res = y0
 //     z1  = conv1(y0)   1 -> C, 3 x 3, dilation a1, zero padding a1      VALU from y0 in LDS (k_acre_conv1), STORED
@@ -27,6 +28,10 @@
 //     k_acre_rowsum     g += the per-row partials: 16 row classes (row mod 16) each in row order, then the 16 sums as a fixed tree
 //     k_acre_bn0_fin / k_acre_dcomb / k_acre_scatter    bn0's backward, d ent | d rel rows, the ordered scatter (every id, 0 included)
 // z1 and z2 are SAVED by the forward, not recomputed: they pass through global memory between the launches anyway.
+// The parallel way replaces the chain and the residual by z_i = conv_i(y0), i = 1 .. 3 (k_acre_conv1 three times) and the gate
+//     c[ch] = [y0 | z_1[ch] | z_2[ch] | z_3[ch]] gate_w^T + gate_b        a GEMM over the (row, channel) pairs (k_acrp_gate)
+// and its backward by k_acrp_chsum / k_acrp_gate_gw / k_acrp_gw_fin (g_gate_w, g_gate_b), k_acrp_gate (dres, dz_i) and
+// k_acrp_conv_bwd (the three convolutions of y0 at once).  It SAVES c, z_1, z_2, z_3.
 // No kernel of this file uses atomics.
 //
 // The dropout draw is the shared one (kge_projection.h spells the Philox counters out), with
@@ -785,6 +790,276 @@ __global__ void __launch_bounds__(256) k_acre_scatter(const int64_t* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ the parallel way
+// (kernels k_acrp_*; everything before z_1 and after c is the serial way's.)  A PAIR is (row, channel): pair p = row C + ch, M = N C of
+// them; the stored layers [N, F] are [M, 400].  The gate c[p] = g_in[p] gate_w^T + gate_b has g_in[p] = [y0[row] | z_1[p] | z_2[p] | z_3[p]]:
+// the y0 block of the contraction is the same for the C pairs of a row, so it is formed once per row (yg [N, 400], gate_b included) and
+// added in the epilogue of the pairs' product, whose contraction is then 1200.
+constexpr int kApNB = 2;            // column blocks of 16 per wave of k_acrp_gate: a workgroup owns 64 rows x 128 columns
+constexpr int kApGW = 4 * kAcHW;    // row length of gate_w
+constexpr int kApSub = 32;          // contraction length of one accumulation chain of k_acrp_gate
+constexpr int kApPJ = (kAcHW + 63) / 64;   // positions lane + 64 j of a lane of k_acrp_conv_bwd
+constexpr int kApPB = 5;            // position blocks of 16 per wave of k_acrp_gate_gw: 25 = 5 x 5
+static_assert(kAcHW / 16 == kApPB * kApPB && kAcLS > kAcHW, "gate tiles, zero slot");
+enum { kGateY0 = 0, kGateZ = 1, kGateDres = 2, kGateDz = 3 };
+
+// y0d[row][pix] = bn0(img) * m0 as ac_load_y0 forms it: the A operand of the y0 block of the gate (kGateY0) and the B operand of the y0
+// block of its weight gradient, which would otherwise draw the mask per use
+__global__ void __launch_bounds__(256) k_acrp_y0(AcArgs a, const int64_t* __restrict__ e, const int64_t* __restrict__ r, float* __restrict__ y0d) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n * a.dirs * kAcHW) return;
+    const int64_t gr = i / kAcHW;
+    const int pix = (int)(i - gr * kAcHW);
+    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    const float mean0 = st[0], g0 = st[1] * a.w0[0], b0 = a.b0[0];
+    y0d[i] = ((ac_comb(a, a.ent + e[gr] * a.K, a.rel + r[gr] * a.K, pix) - mean0) * g0 + b0) * ac_factor(a, 0, pix, gr);
+}
+
+// out[m][col] = sum_k A[m][k] B[k][col] on v_mfma_f32_16x16x4_f32, grid (ceil(M / 64), ceil(cols / 128)): the A tile of 64 m x 128 k is
+// staged in LDS as k_acre_fc stages it, wave w owns the column blocks (4 blockIdx.y + w) kApNB + {0, 1}, B comes from gate_w directly.
+//   kGateY0    m = row,  A = y0d (src),                    k < 400,  B[k][pos] = gate_w[pos][k],        yg[row][pos] = . + gate_b[pos]
+//   kGateZ     m = pair, A = [z_1 | z_2 | z_3][pair] (src), k < 1200, B[k][pos] = gate_w[pos][400 + k],  c[pair][pos] = . + yg[row][pos] (add)
+//   kGateDres  m = row,  A = sum_ch dc (src),              k < 400,  B[k][q] = gate_w[k][q],            dres[row][q]
+//   kGateDz    m = pair, A = dc (src),                     k < 400,  B[k][col] = gate_w[k][400 + col],  dz_i[pair][q], col = 400 i + q < 1200
+// The three layers of src (kGateZ) and of out (kGateDz) lie M x 400 floats apart.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_acrp_gate(AcArgs a, const float* __restrict__ gw, const float* __restrict__ gb,
+                                                   const float* __restrict__ src, const float* __restrict__ add, float* __restrict__ out) {
+    __shared__ float As[kAcKC * kAcStride];
+    constexpr bool PAIRS = MODE == kGateZ || MODE == kGateDz, FWD = MODE == kGateY0 || MODE == kGateZ;
+    constexpr int KT = MODE == kGateZ ? 3 * kAcHW : kAcHW, COLS = MODE == kGateDz ? 3 * kAcHW : kAcHW, OFF = PAIRS ? kAcHW : 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int64_t M = a.n * a.dirs * (PAIRS ? a.C : 1), m0 = (int64_t)blockIdx.x * kAcRows, LAYER = M * kAcHW;
+    int col[kApNB];
+    bool live[kApNB];
+#pragma unroll
+    for (int nb = 0; nb < kApNB; ++nb) {
+        const int ct = ((int)blockIdx.y * 4 + wave) * kApNB + nb;
+        live[nb] = 16 * ct < COLS;   // (wave-uniform)
+        col[nb] = live[nb] ? 16 * ct + l : 0;
+    }
+    // two levels of accumulation: a chain of v_mfma_f32_16x16x4_f32 over kApSub k, then added to the total.  One chain over the gate's
+    // 1600 terms carries about four times the rounding error of this order, and c feeds batch norms that amplify it
+    f32x4v acc[4][kApNB], sub[4][kApNB];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < kApNB; ++nb) acc[mb][nb] = sub[mb][nb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int k0 = 0; k0 < KT; k0 += kAcKC) {
+        const int kn = min(kAcKC, KT - k0), kn4 = (kn + 3) & ~3;
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < kAcKC * kAcRows; idx += 256) {
+            const int kl = idx & (kAcKC - 1), rl = idx >> 7;   // consecutive threads: consecutive k of one m
+            if (kl >= kn4) continue;
+            float v = 0.0f;
+            if (m0 + rl < M && kl < kn) {
+                const int64_t m = m0 + rl;
+                const int k = k0 + kl;
+                if constexpr (MODE == kGateZ) v = src[(int64_t)(k / kAcHW) * LAYER + m * kAcHW + k % kAcHW];
+                else v = src[m * kAcHW + k];
+            }
+            As[kl * kAcStride + 4 * (rl & 15) + (rl >> 4)] = v;
+        }
+        __syncthreads();
+        if (live[0])
+            for (int s0 = 0; s0 < kn4; s0 += kApSub) {
+                const int ns = min(kApSub, kn4 - s0) / 4;   // steps of this chain: all of its B operands are requested before the first product
+                float b[kApSub / 4][kApNB];
+#pragma unroll
+                for (int i = 0; i < kApSub / 4; ++i) {
+                    const int k = min(k0 + s0 + 4 * i + g, KT - 1);   // (rows of As beyond the chunk are zero)
+#pragma unroll
+                    for (int nb = 0; nb < kApNB; ++nb) b[i][nb] = FWD ? gw[(int64_t)col[nb] * kApGW + OFF + k] : gw[(int64_t)k * kApGW + OFF + col[nb]];
+                }
+#pragma unroll
+                for (int i = 0; i < kApSub / 4; ++i) {
+                    if (i >= ns) continue;
+                    float av[4];
+                    read_blocks<4>(&As[(s0 + 4 * i + g) * kAcStride], l, av);
+#pragma unroll
+                    for (int nb = 0; nb < kApNB; ++nb)
+                        if (live[nb])
+#pragma unroll
+                            for (int mb = 0; mb < 4; ++mb) sub[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], b[i][nb], sub[mb][nb], 0, 0, 0);
+                }
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                    for (int nb = 0; nb < kApNB; ++nb) {
+                        acc[mb][nb] += sub[mb][nb];
+                        sub[mb][nb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+                    }
+            }
+    }
+#pragma unroll
+    for (int nb = 0; nb < kApNB; ++nb) {
+        if (!live[nb]) continue;
+        const int c = col[nb];
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t m = m0 + 16 * mb + 4 * g + q;
+                if (m >= M) continue;
+                const float v = acc[mb][nb][q];
+                if constexpr (MODE == kGateY0) out[m * kAcHW + c] = v + gb[c];
+                else if constexpr (MODE == kGateZ) out[m * kAcHW + c] = v + add[(m / a.C) * kAcHW + c];
+                else if constexpr (MODE == kGateDres) out[m * kAcHW + c] = v;
+                else out[(int64_t)(c / kAcHW) * LAYER + m * kAcHW + c % kAcHW] = v;
+            }
+    }
+}
+
+// dcs[row][pos] = sum over the channels, ascending, of dc[row][ch][pos]: the A operand of kGateDres and of the y0 block of g_gate_w, and
+// (through k_acre_rowsum) g_gate_b
+__global__ void __launch_bounds__(256) k_acrp_chsum(AcArgs a, const float* __restrict__ dc, float* __restrict__ dcs) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n * a.dirs * kAcHW) return;
+    const int64_t gr = i / kAcHW;
+    const int pos = (int)(i - gr * kAcHW);
+    float s = 0.0f;
+    for (int ch = 0; ch < a.C; ++ch) s += dc[gr * a.F + (int64_t)ch * kAcHW + pos];
+    dcs[i] = s;
+}
+
+// the gate's weight gradient, the contraction read from global memory as k_acre_fc_gw reads it.  grid (q tiles / 4, 5, splits): wave w owns
+// the 16 q of tile 4 blockIdx.x + w for the 80 positions of blockIdx.y (5 accumulator blocks).
+//   ZB = false  the y0 block: g_gate_w[pos][q] += sum over the rows, ascending, of dcs[row][pos] y0d[row][q], q < 400 (z = y0d)
+//   ZB = true   the z blocks: part[split][pos][col] = sum over the split's pairs [split per, ...), ascending, of dc[pair][pos]
+//               z_i[pair][q], col = 400 i + q < 1200; k_acrp_gw_fin adds the splits in order
+template <bool ZB>
+__global__ void __launch_bounds__(256) k_acrp_gate_gw(AcArgs a, const float* __restrict__ dcx, const float* __restrict__ z, int64_t per,
+                                                      float* __restrict__ out) {
+    constexpr int QT = (ZB ? 3 : 1) * kAcHW / 16;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
+    const int qt = (int)blockIdx.x * 4 + wave;
+    if (qt >= QT) return;   // (wave-uniform)
+    const int64_t M = a.n * a.dirs * (ZB ? a.C : 1), lo = (int64_t)blockIdx.z * per, hi = min(M, lo + per);
+    const int p0 = 16 * kApPB * (int)blockIdx.y;
+    const float* __restrict__ zl = z + (int64_t)(qt / (kAcHW / 16)) * M * kAcHW + 16 * (qt % (kAcHW / 16)) + l;   // (ZB = false: z = y0d, one layer)
+    f32x4v acc[kApPB];
+#pragma unroll
+    for (int kb = 0; kb < kApPB; ++kb) acc[kb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t m0 = lo; m0 < hi; m0 += 4) {
+        const int64_t m = m0 + g;
+        const bool ok = m < hi;
+        const int64_t mc = ok ? m : hi - 1;
+        const float bv = ok ? zl[mc * kAcHW] : 0.0f;
+        const float* __restrict__ dp = dcx + mc * kAcHW + p0 + l;
+#pragma unroll
+        for (int kb = 0; kb < kApPB; ++kb) acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ok ? dp[16 * kb] : 0.0f, bv, acc[kb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int kb = 0; kb < kApPB; ++kb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int pos = p0 + 16 * kb + 4 * g + q;
+            if constexpr (ZB) out[((int64_t)blockIdx.z * kAcHW + pos) * (3 * kAcHW) + 16 * qt + l] = acc[kb][q];
+            else out[(int64_t)pos * kApGW + 16 * qt + l] += acc[kb][q];
+        }
+}
+
+// g_gate_w[pos][400 + col] += the partial tiles of k_acrp_gate_gw<true> in split order
+__global__ void __launch_bounds__(256) k_acrp_gw_fin(const float* __restrict__ part, int splits, float* __restrict__ g_gw) {
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= kAcHW * 3 * kAcHW) return;
+    float s = 0.0f;
+    for (int sp = 0; sp < splits; ++sp) s += part[(int64_t)sp * (kAcHW * 3 * kAcHW) + i];
+    g_gw[(int64_t)(i / (3 * kAcHW)) * kApGW + kAcHW + i % (3 * kAcHW)] += s;
+}
+
+// one workgroup per row: the backward of the three 1 -> C convolutions of y0, the layers i = 0, 1, 2 in turn through ONE dz buffer in
+// LDS.  The layer's tap table (a tap in the padding points at a zero slot) sits in LDS, the shifted y0 of a lane's positions in
+// registers.  Per layer, as k_acre_c1_bwd: one wave per channel o, gwp[i][row][o 9 + t] = sum_pos dz_i[o, pos] y0[pos + tap t] and
+// gbp[i][row][o] = sum_pos dz_i[o, pos]; then a thread per pixel adds conv_i^T dz_i (o ascending) to the pixel's register.  At the end
+// dy0 = (the three layers' sum, i ascending, + dres) * m0 -> dimg[row][400]; (sum dy0, sum dy0 xh0) -> pt0[row]
+__global__ void __launch_bounds__(256) k_acrp_conv_bwd(AcArgs a, const int64_t* __restrict__ e, const int64_t* __restrict__ r,
+                                                       const float* __restrict__ dz, const float* __restrict__ dres, float* __restrict__ gwp,
+                                                       float* __restrict__ gbp, float* __restrict__ dimg, float2* __restrict__ pt0) {
+    __shared__ float dzs[kAcMaxC * kAcLS];
+    __shared__ float y0s[kAcHW + 1];
+    __shared__ int tap[9 * kAcHW];
+    __shared__ float wl[kAcMaxC * 9];
+    __shared__ float red[8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gr = blockIdx.x, N = a.n * a.dirs;
+    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    const int C = a.C;
+    if (threadIdx.x < C) dzs[threadIdx.x * kAcLS + kAcHW] = 0.0f;   // a zero behind each channel's 400 values (the stride leaves room)
+    if (threadIdx.x == 0) y0s[kAcHW] = 0.0f;                        // ... and behind y0's
+    ac_load_y0(a, st, e, r, gr, y0s);
+    float acc[2] = {0.0f, 0.0f};   // pixels threadIdx.x and threadIdx.x + 256
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {
+        const int d = a.dil[i];
+        if (i) __syncthreads();   // every thread is done with the previous layer's dzs and wl
+        for (int j = threadIdx.x; j < 9 * C; j += 256) wl[j] = a.cw[i][j];
+        for (int j = threadIdx.x; j < 9 * kAcHW; j += 256) {   // the layer's tap table; in the padding: the zero slot
+            const int q = ac_tap(j % kAcHW, j / kAcHW, d);
+            tap[j] = q >= 0 ? q : kAcHW;
+        }
+        ac_load_layer(a, dz + (int64_t)i * N * a.F, gr, dzs);
+        float ys[9][kApPJ];   // y0 at tap t of the lane's positions lane + 64 j: the same for every channel of the layer
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int j = 0; j < kApPJ; ++j) ys[t][j] = y0s[lane + 64 * j < kAcHW ? tap[t * kAcHW + lane + 64 * j] : kAcHW];
+        for (int o = wave; o < C; o += 4) {
+            const float* __restrict__ drow = dzs + o * kAcLS;
+            float dv[kApPJ], sb = 0.0f;
+#pragma unroll
+            for (int j = 0; j < kApPJ; ++j) {
+                dv[j] = lane + 64 * j < kAcHW ? drow[lane + 64 * j] : 0.0f;
+                sb += dv[j];
+            }
+            sb = wave_sum_xor(sb);
+            if (lane == 0 && gbp) gbp[((int64_t)i * N + gr) * C + o] = sb;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                float s = 0.0f;
+#pragma unroll
+                for (int j = 0; j < kApPJ; ++j) s += dv[j] * ys[t][j];
+                s = wave_sum_xor(s);
+                if (lane == 0) gwp[((int64_t)i * N + gr) * (9 * C) + o * 9 + t] = s;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int pix = threadIdx.x + 256 * j;
+            if (pix >= kAcHW) continue;
+            int sp[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) sp[t] = tap[(8 - t) * kAcHW + pix];   // pix - tap t; in the padding: the channel's zero slot
+            float v = 0.0f;
+            for (int o = 0; o < C; ++o) {
+                float s = 0.0f;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) s += wl[o * 9 + t] * dzs[o * kAcLS + sp[t]];
+                v += s;
+            }
+            acc[j] += v;
+        }
+    }
+    const float mean0 = st[0], rstd0 = st[1];
+    const float* __restrict__ er = a.ent + e[gr] * a.K;
+    const float* __restrict__ rr = a.rel + r[gr] * a.K;
+    float t1 = 0.0f, t2 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int pix = threadIdx.x + 256 * j;
+        if (pix >= kAcHW) continue;
+        const float v = (acc[j] + dres[gr * kAcHW + pix]) * ac_factor(a, 0, pix, gr);
+        dimg[gr * kAcHW + pix] = v;
+        t1 += v;
+        t2 += v * ((ac_comb(a, er, rr, pix) - mean0) * rstd0);
+    }
+    t1 = wave_sum_xor(t1);
+    t2 = wave_sum_xor(t2);
+    if (lane == 0) { red[wave] = t1; red[4 + wave] = t2; }
+    __syncthreads();
+    if (threadIdx.x == 0) pt0[gr] = make_float2(((red[0] + red[1]) + red[2]) + red[3], ((red[4] + red[5]) + red[6]) + red[7]);
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host side
 static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
     if (!d) { set_error("%s: null descriptor", who); return -1; }
@@ -822,10 +1097,6 @@ static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
         set_error("%s: the gate pointers must both be set in the parallel way and both be NULL in the serial way", who);
         return -1;
     }
-    if (d->way == 1) {
-        set_error("%s: the parallel way (way = 1) has not been built on this path; the serial way is", who);
-        return -1;
-    }
     for (int i = 0; i < 3; ++i) {
         if (!(d->momentum[i] > 0.0f && d->momentum[i] <= 1.0f)) {
             set_error("%s: momentum %d must be in (0, 1] (got %g; the cumulative average is not built)", who, i, (double)d->momentum[i]);
@@ -840,7 +1111,7 @@ static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
                            d->g_fc_b, d->g_conv1_w, d->g_conv2_w, d->g_conv3_w};
         for (const void* q : g)
             if (!q) { set_error("%s: null gradient buffers (one per parameter of the way is required)", who); return -1; }
-        if (d->acre_bias && (!d->g_conv1_b || !d->g_conv2_b || !d->g_conv3_b)) {
+        if ((d->acre_bias && (!d->g_conv1_b || !d->g_conv2_b || !d->g_conv3_b)) || (d->way == 1 && (!d->g_gate_w || !d->g_gate_b))) {
             set_error("%s: null gradient buffers (one per parameter of the way is required)", who);
             return -1;
         }
@@ -894,16 +1165,22 @@ static int ac_f_per(int F, int64_t n, int dirs) {
 }
 static int ac_splits(int F, int per) { return (F + per - 1) / per; }
 
-// saved (floats): c [N, F] | z1 [N, F] | z2 [N, F] | u [N, K] | m1f [N, C] | stats [dirs][2 + 2C + 2K]
+// saved (floats): c [N, F] | z1 [N, F] | z2 [N, F] | u [N, K] | m1f [N, C] | stats [dirs][2 + 2C + 2K]; the parallel way keeps a
+// third layer, c | z_1 | z_2 | z_3 | u | m1f | stats: the z_i are saved, not recomputed (the backward reads them twice, as the
+// gate's input and never as a convolution's)
+static int ac_layers(const kge_acre_desc* d) { return d->way ? 4 : 3; }
 static size_t ac_saved_floats(const kge_acre_desc* d, int64_t n, int dirs) {
-    return (size_t)dirs * ((size_t)n * ((size_t)3 * ac_f(d) + kAcK + d->in_channels) + ac_ss(d));
+    return (size_t)dirs * ((size_t)n * ((size_t)ac_layers(d) * ac_f(d) + kAcK + d->in_channels) + ac_ss(d));
 }
 static size_t ac_part_bytes(const kge_acre_desc* d, size_t N) { return align256(N * (d->in_channels > 2 ? d->in_channels : 2) * sizeof(float2)); }
-// forward: row partials float2 [N, max(C, 2)] (bn0's are double2 [N]) | upart [splits, N, K]
+// forward: row partials float2 [N, max(C, 2)] (bn0's are double2 [N]) | upart [splits, N, K] | the parallel way: yg [N, 400] | y0d [N, 400]
+static size_t ac_upart_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
+    const int F = ac_f(d);
+    return align256((size_t)ac_splits(F, ac_f_per(F, n, dirs)) * (size_t)n * dirs * kAcK * sizeof(float));
+}
 static size_t ac_fwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
     const size_t N = (size_t)n * dirs;
-    const int F = ac_f(d);
-    return ac_part_bytes(d, N) + align256((size_t)ac_splits(F, ac_f_per(F, n, dirs)) * N * kAcK * sizeof(float));
+    return ac_part_bytes(d, N) + ac_upart_bytes(d, n, dirs) + (d->way ? 2 * align256(N * kAcHW * sizeof(float)) : 0);
 }
 // backward: du [N, K] | dy1 = dc [N, F] | dza [N, F] | dzb [N, F] | part1 float2 [N, C] | sums float2 [dirs, C] | gwp3 [N, 9 C C] |
 // gwp2 [N, 9 C C] | gwp1 [N, 9 C] | gbp [3][N, C] | dimg [N, 400] | dent [N, K] | drel [N, K] | pt0 float2 [N] | t0 float2 [dirs]
@@ -932,11 +1209,53 @@ static AcBwdPlan ac_bwd_plan(const kge_acre_desc* d, int64_t n, int dirs) {
     return p;
 }
 
+// pairs of one split of the gate's weight gradient: a function of the shapes alone (the split order is the summation order), a
+// multiple of 4, every split non-empty
+static int64_t ap_gw_per(int64_t M) {
+    int64_t splits = (M + 1023) / 1024;
+    if (splits > 16) splits = 16;
+    const int64_t per = ((M + splits - 1) / splits + 3) & ~(int64_t)3;
+    return per;
+}
+static int ap_gw_splits(int64_t M) { return (int)((M + ap_gw_per(M) - 1) / ap_gw_per(M)); }
+
+// backward of the parallel way: du [N, K] | dc [N, F] | dz [3][N, F] | part1 float2 [N, C] | sums float2 [dirs, C] | dcs [N, 400] |
+// dres [N, 400] | y0d [N, 400] | gpart [splits][400][1200] | gwp [3][N, 9 C] | gbp [3][N, C] | dimg [N, 400] | dent [N, K] | drel [N, K] |
+// pt0 float2 [N] | t0 float2 [dirs]
+struct ApBwdPlan {
+    size_t du, dc, dz, part1, sums, dcs, dres, y0d, gpart, gwp, gbp, dimg, dent, drel, pt0, t0, total;
+};
+static ApBwdPlan ap_bwd_plan(const kge_acre_desc* d, int64_t n, int dirs) {
+    const size_t N = (size_t)n * dirs, C = (size_t)d->in_channels, F = (size_t)ac_f(d);
+    ApBwdPlan p{};
+    p.du = 0;
+    p.dc = p.du + align256(N * kAcK * sizeof(float));
+    p.dz = p.dc + align256(N * F * sizeof(float));
+    p.part1 = p.dz + align256(3 * N * F * sizeof(float));
+    p.sums = p.part1 + align256(N * C * sizeof(float2));
+    p.dcs = p.sums + align256((size_t)dirs * C * sizeof(float2));
+    p.dres = p.dcs + align256(N * kAcHW * sizeof(float));
+    p.y0d = p.dres + align256(N * kAcHW * sizeof(float));
+    p.gpart = p.y0d + align256(N * kAcHW * sizeof(float));
+    p.gwp = p.gpart + align256((size_t)ap_gw_splits((int64_t)(N * C)) * kAcHW * 3 * kAcHW * sizeof(float));
+    p.gbp = p.gwp + align256(3 * N * 9 * C * sizeof(float));
+    p.dimg = p.gbp + align256(3 * N * C * sizeof(float));
+    p.dent = p.dimg + align256(N * kAcHW * sizeof(float));
+    p.drel = p.dent + align256(N * kAcK * sizeof(float));
+    p.pt0 = p.drel + align256(N * kAcK * sizeof(float));
+    p.t0 = p.pt0 + align256(N * sizeof(float2));
+    p.total = p.t0 + align256((size_t)dirs * sizeof(float2));
+    return p;
+}
+static size_t ac_bwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
+    return d->way ? ap_bwd_plan(d, n, dirs).total : ac_bwd_plan(d, n, dirs).total;
+}
+
 static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int64_t row0, float* x, float* saved,
                       void* ws, hipStream_t st) {
     const int64_t N = n * dirs;
     const int C = d->in_channels, F = ac_f(d);
-    float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + N * F, *m1f = u + N * kAcK, *stats = m1f + N * C;
+    float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + (ac_layers(d) - 2) * N * F, *m1f = u + N * kAcK, *stats = m1f + N * C;
     const AcArgs a = ac_args(d, n, dirs, row0, stats);
     float2* part = (float2*)ws;
     float* upart = (float*)((char*)ws + ac_part_bytes(d, (size_t)N));
@@ -949,10 +1268,23 @@ static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r
         hipLaunchKernelGGL(k_acre_stats_eval, dim3((unsigned)((1 + C + kAcK + 255) / 256)), dim3(256), 0, st, a, d->eps[0], d->eps[1], d->eps[2],
                            d->bn0_mean, d->bn0_var, d->bn1_mean, d->bn1_var, d->bn2_mean, d->bn2_var);
     }
-    hipLaunchKernelGGL(k_acre_conv1, dim3((unsigned)N), dim3(256), 0, st, a, 0, e, r, z1);
-    hipLaunchKernelGGL((k_acre_cc<false>), dim3((unsigned)N), dim3(256), 0, st, a, 1, 0, e, r, z1, z2);
-    hipLaunchKernelGGL((k_acre_cc<false>), dim3((unsigned)N), dim3(256), 0, st, a, 2, 1, e, r, z2, c);
-    if (int rc = check_launch("k_acre_row_stats / k_acre_bn0_stats / k_acre_conv1 / k_acre_cc")) return rc;
+    if (d->way) {
+        // z_i = conv_i(y0) into three consecutive layers; yg = y0's block of the gate once per row; c = the pairs' product + yg
+        float* yg = (float*)((char*)ws + ac_part_bytes(d, (size_t)N) + ac_upart_bytes(d, n, dirs));
+        float* y0d = (float*)((char*)yg + align256((size_t)N * kAcHW * sizeof(float)));
+        hipLaunchKernelGGL(k_acrp_y0, dim3((unsigned)((N * kAcHW + 255) / 256)), dim3(256), 0, st, a, e, r, y0d);
+        for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k_acre_conv1, dim3((unsigned)N), dim3(256), 0, st, a, i, e, r, z1 + i * N * F);
+        hipLaunchKernelGGL((k_acrp_gate<kGateY0>), dim3((unsigned)((N + kAcRows - 1) / kAcRows), 4), dim3(256), 0, st, a, d->gate_w, d->gate_b,
+                           (const float*)y0d, (const float*)nullptr, yg);
+        hipLaunchKernelGGL((k_acrp_gate<kGateZ>), dim3((unsigned)((N * C + kAcRows - 1) / kAcRows), 4), dim3(256), 0, st, a, d->gate_w,
+                           d->gate_b, (const float*)z1, (const float*)yg, c);
+        if (int rc = check_launch("k_acre_row_stats / k_acre_bn0_stats / k_acrp_y0 / k_acre_conv1 / k_acrp_gate")) return rc;
+    } else {
+        hipLaunchKernelGGL(k_acre_conv1, dim3((unsigned)N), dim3(256), 0, st, a, 0, e, r, z1);
+        hipLaunchKernelGGL((k_acre_cc<false>), dim3((unsigned)N), dim3(256), 0, st, a, 1, 0, e, r, z1, z2);
+        hipLaunchKernelGGL((k_acre_cc<false>), dim3((unsigned)N), dim3(256), 0, st, a, 2, 1, e, r, z2, c);
+        if (int rc = check_launch("k_acre_row_stats / k_acre_bn0_stats / k_acre_conv1 / k_acre_cc")) return rc;
+    }
     if (train) {
         hipLaunchKernelGGL(k_acre_c_stats, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, part, m1f);
         hipLaunchKernelGGL(k_acre_bn_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part, C, C, kAcHW, a.o1, a.o1 + C, d->eps[1],
@@ -973,12 +1305,70 @@ static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r
     return check_launch("k_acre_c_stats / k_acre_fc / k_acre_fc_finish");
 }
 
+// the parallel way's backward: the serial tail down to dc, the gate (weight, bias and input gradients), the three convolutions of y0 at
+// once, then bn0's backward and the scatter as in the serial way
+static int ap_backward(const kge_acre_desc* d, const AcArgs& a, const int64_t* e, const int64_t* r, int64_t n, int dirs, const float* dx,
+                       const float* c, const float* z, const float* u, const float* m1f, void* ws, hipStream_t st) {
+    const int64_t N = n * dirs;
+    const int C = d->in_channels, F = ac_f(d);
+    const int64_t M = N * C;
+    const ApBwdPlan p = ap_bwd_plan(d, n, dirs);
+    char* w = (char*)ws;
+    float *du = (float*)(w + p.du), *dc = (float*)(w + p.dc), *dz = (float*)(w + p.dz), *dcs = (float*)(w + p.dcs), *dres = (float*)(w + p.dres);
+    float *y0d = (float*)(w + p.y0d), *gpart = (float*)(w + p.gpart), *gwp = (float*)(w + p.gwp), *gbp = d->acre_bias ? (float*)(w + p.gbp) : nullptr;
+    float *dimg = (float*)(w + p.dimg), *dent = (float*)(w + p.dent), *drel = (float*)(w + p.drel);
+    float2 *part1 = (float2*)(w + p.part1), *sums = (float2*)(w + p.sums), *pt0 = (float2*)(w + p.pt0), *t0 = (float2*)(w + p.t0);
+    const unsigned row_blocks = (unsigned)((N + 3) / 4), col_blocks = (unsigned)((kAcK + 3) / 4);
+    const int tiles = ac_tiles(n);
+    const int chan_groups = (C + 3) / 4 < 8 ? (C + 3) / 4 : 8;
+    hipLaunchKernelGGL(k_acre_bn2_bwd, dim3(col_blocks), dim3(256), 0, st, a, dx, u, du, d->g_bn2_w, d->g_bn2_b, d->g_fc_b);
+    hipLaunchKernelGGL(k_acre_fc_gw, dim3((unsigned)((F + 63) / 64), (unsigned)((kAcK + 127) / 128)), dim3(256), 0, st, a, c, m1f, du, d->g_fc_w);
+    hipLaunchKernelGGL(k_acre_fc_da, dim3((unsigned)(dirs * tiles), (unsigned)((F + 63) / 64)), dim3(256), 0, st, a, c, m1f, du, tiles, dc);
+    if (int rc = check_launch("k_acre_bn2_bwd / k_acre_fc_gw / k_acre_fc_da")) return rc;
+    hipLaunchKernelGGL(k_acre_bn1_part, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dc, part1);
+    hipLaunchKernelGGL(k_acre_bn1_bwd_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part1, sums, d->g_bn1_w, d->g_bn1_b);
+    hipLaunchKernelGGL(k_acre_bn1_dc, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dc, sums);
+    if (int rc = check_launch("k_acre_bn1_part / k_acre_bn1_bwd_fin / k_acre_bn1_dc")) return rc;
+    // the gate: dcs = the channel sum of dc; g_gate_b; g_gate_w's y0 block over the rows and its z blocks over the pairs in splits;
+    // dres = dcs gate_w[:, :400] and dz_i = dc gate_w[:, 400 (i + 1) ...]
+    const int64_t per = ap_gw_per(M);
+    const int splits = ap_gw_splits(M);
+    hipLaunchKernelGGL(k_acrp_chsum, dim3((unsigned)((N * kAcHW + 255) / 256)), dim3(256), 0, st, a, (const float*)dc, dcs);
+    hipLaunchKernelGGL(k_acrp_y0, dim3((unsigned)((N * kAcHW + 255) / 256)), dim3(256), 0, st, a, e, r, y0d);
+    hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((kAcHW + 15) / 16)), dim3(256), 0, st, dcs, N, kAcHW, d->g_gate_b);
+    hipLaunchKernelGGL((k_acrp_gate_gw<false>), dim3((unsigned)((kAcHW / 16 + 3) / 4), kApPB, 1), dim3(256), 0, st, a, (const float*)dcs,
+                       (const float*)y0d, N, d->g_gate_w);
+    hipLaunchKernelGGL((k_acrp_gate_gw<true>), dim3((unsigned)((3 * kAcHW / 16 + 3) / 4), kApPB, (unsigned)splits), dim3(256), 0, st, a,
+                       (const float*)dc, z, per, gpart);
+    hipLaunchKernelGGL(k_acrp_gw_fin, dim3((unsigned)((kAcHW * 3 * kAcHW + 255) / 256)), dim3(256), 0, st, (const float*)gpart, splits, d->g_gate_w);
+    if (int rc = check_launch("k_acrp_chsum / k_acrp_y0 / k_acre_rowsum / k_acrp_gate_gw / k_acrp_gw_fin")) return rc;
+    hipLaunchKernelGGL((k_acrp_gate<kGateDres>), dim3((unsigned)((N + kAcRows - 1) / kAcRows), 4), dim3(256), 0, st, a, d->gate_w, d->gate_b,
+                       (const float*)dcs, (const float*)nullptr, dres);
+    hipLaunchKernelGGL((k_acrp_gate<kGateDz>), dim3((unsigned)((M + kAcRows - 1) / kAcRows), (unsigned)((3 * kAcHW + 127) / 128)), dim3(256), 0, st, a,
+                       d->gate_w, d->gate_b, (const float*)dc, (const float*)nullptr, dz);
+    hipLaunchKernelGGL(k_acrp_conv_bwd, dim3((unsigned)N), dim3(256), 0, st, a, e, r, (const float*)dz, (const float*)dres, gwp, gbp, dimg, pt0);
+    if (int rc = check_launch("k_acrp_gate / k_acrp_conv_bwd")) return rc;
+    float* gw[3] = {d->g_conv1_w, d->g_conv2_w, d->g_conv3_w};
+    float* gb[3] = {d->g_conv1_b, d->g_conv2_b, d->g_conv3_b};
+    for (int i = 0; i < 3; ++i) {
+        hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((9 * C + 15) / 16)), dim3(256), 0, st, gwp + (int64_t)i * N * 9 * C, N, 9 * C, gw[i]);
+        if (gbp) hipLaunchKernelGGL(k_acre_rowsum, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, gbp + (int64_t)i * N * C, N, C, gb[i]);
+    }
+    hipLaunchKernelGGL(k_acre_bn0_fin, dim3(1), dim3(64), 0, st, a, pt0, t0, d->g_bn0_w, d->g_bn0_b);
+    hipLaunchKernelGGL(k_acre_dcomb, dim3((unsigned)N), dim3(256), 0, st, a, e, r, dimg, t0, dent, drel);
+    if (int rc = check_launch("k_acre_rowsum / k_acre_bn0_fin / k_acre_dcomb")) return rc;
+    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, e, N, kAcK, dent, d->g_ent);
+    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, r, N, kAcK, drel, d->g_rel);
+    return check_launch("k_acre_scatter");
+}
+
 static int ac_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int64_t row0, const float* dx,
                        const float* saved, void* ws, hipStream_t st) {
     const int64_t N = n * dirs;
     const int C = d->in_channels, F = ac_f(d);
-    const float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + N * F, *m1f = u + N * kAcK;
+    const float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + (ac_layers(d) - 2) * N * F, *m1f = u + N * kAcK;
     const AcArgs a = ac_args(d, n, dirs, row0, const_cast<float*>(m1f + N * C));
+    if (d->way) return ap_backward(d, a, e, r, n, dirs, dx, c, z1, u, m1f, ws, st);
     const AcBwdPlan p = ac_bwd_plan(d, n, dirs);
     char* w = (char*)ws;
     float *du = (float*)(w + p.du), *dy1 = (float*)(w + p.dy1), *dza = (float*)(w + p.dza), *dzb = (float*)(w + p.dzb);
@@ -1041,7 +1431,7 @@ static AcStepPlan ac_step_plan(const kge_acre_desc* d, int64_t B, int64_t n_hr, 
     p.saved = p.dx + xb;
     p.rest = p.saved + align256(ac_saved_floats(d, B, 2) * sizeof(float));
     size_t rest = ac_fwd_bytes(d, B, 2);
-    if (ac_bwd_plan(d, B, 2).total > rest) rest = ac_bwd_plan(d, B, 2).total;
+    if (ac_bwd_bytes(d, B, 2) > rest) rest = ac_bwd_bytes(d, B, 2);
     const size_t h1 = kge_head_1n_bce_workspace_bytes(B, d->tot_entity, n_hr), h2 = kge_head_1n_bce_workspace_bytes(B, d->tot_entity, n_tr);
     if (h1 > rest) rest = h1;
     if (h2 > rest) rest = h2;
@@ -1093,7 +1483,7 @@ int kge_acre_body_forward(const kge_acre_desc* d, const int64_t* e, const int64_
 }
 
 size_t kge_acre_body_backward_workspace_bytes(const kge_acre_desc* d, int64_t n) {
-    return ac_check(d, "kge_acre_body_backward_workspace_bytes", false) || n < 0 ? 0 : ac_bwd_plan(d, n > 0 ? n : 1, 1).total;
+    return ac_check(d, "kge_acre_body_backward_workspace_bytes", false) || n < 0 ? 0 : ac_bwd_bytes(d, n > 0 ? n : 1, 1);
 }
 
 int kge_acre_body_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, const float* dx,
@@ -1106,7 +1496,7 @@ int kge_acre_body_backward(const kge_acre_desc* d, const int64_t* e, const int64
     }
     if (!d->train) { set_error("%s: the eval form (train = 0) has no backward", who); return -1; }
     if (ac_check_rows(d, who, n)) return -1;
-    if (ws_check(who, workspace, workspace_bytes, ac_bwd_plan(d, n > 0 ? n : 1, 1).total)) return -1;
+    if (ws_check(who, workspace, workspace_bytes, ac_bwd_bytes(d, n > 0 ? n : 1, 1))) return -1;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ac_check_ids(who, d, e, r, n, s)) return rc;

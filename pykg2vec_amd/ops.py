@@ -407,7 +407,8 @@ def acre_body(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int,
 @acre_body.register_fake
 def _(key, e, r, row0, seed, offset, weights):
     n, k, C = e.numel(), weights[1].shape[1], weights[5].shape[0]
-    return weights[1].new_empty((n, k)), weights[1].new_empty((n * (3 * weights[9].shape[1] + k + C) + 2 + 2 * C + 2 * k,))
+    layers = 4 if tuple(weights[-1].shape) == (400,) and weights[-2].dim() == 2 else 3   # the parallel way (the gate comes last) saves z_3 too
+    return weights[1].new_empty((n, k)), weights[1].new_empty((n * (layers * weights[9].shape[1] + k + C) + 2 + 2 * C + 2 * k,))
 
 
 @acre_body.register_kernel("cpu")

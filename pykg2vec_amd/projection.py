@@ -6,8 +6,8 @@ front of the head with its bias b; its torch layers are holders of parameters an
 convolution filter that a second linear layer computes per row from the relation embedding, and padding_idx = 0 on both tables
 (csrc/kge_hyper.hip).  InteractE: chequer permutations of [ent[e] | rel[r]], a depthwise convolution with circular padding whose
 filters the permutations share, and the same fc / batch-norm tail (csrc/kge_interacte.hip).  AcrE: three dilated 3 x 3 convolutions
-chained with a residual, the two channel-mixing ones as implicit GEMMs on the matrix cores, and the same tail (csrc/kge_acre.hip); its
-parallel way is refused by the library."""
+chained with a residual, the two channel-mixing ones as implicit GEMMs on the matrix cores, and the same tail (csrc/kge_acre.hip); in
+its parallel way three convolutions of the same input feed a shared 1600 -> 400 gate, a GEMM over the (row, channel) pairs."""
 import torch
 
 from . import _lib as L  # noqa: F401
@@ -404,8 +404,8 @@ class AcrE(ProjectionModel):
     c))))))), y0 = idrop(bn0(img)), img the [10, 20] view of ent[e] stacked on that of rel[r] (hidden_size is 200 by construction), and
     c = conv3(conv2(conv1(y0))) + y0 in the "serial" way: three 3 x 3 convolutions with dilations first / second / third_atrous and as
     much zero padding, 1 -> in_channels -> in_channels -> in_channels, with no nonlinearity between them.  The "parallel" way (three
-    1 -> in_channels convolutions of y0 and a shared 1600 -> 400 gate) constructs, holds the reference's state and loads its
-    checkpoints, but its arithmetic is not built on this path: the library refuses it by name.  There is one relation table of
+    1 -> in_channels convolutions of y0 and a shared 1600 -> 400 gate, c[ch] = [y0 | z1[ch] | z2[ch] | z3[ch]] W_gate_e^T + b, in
+    place of the chain and the residual) runs on the same kernels before z1 and after c.  There is one relation table of
     2 tot_relation rows: `direction` selects no relation row, only the mask rows.  The torch layers (bn0, bn1, bn2, fc, conv1, conv2,
     conv3, W_gate_e) hold parameters and buffers only, so state_dict() has the reference's keys, order and shapes (the bare parameter
     bias first) and loads a reference checkpoint; the arithmetic is csrc/kge_acre.hip.  Under train() a forward normalises with the
