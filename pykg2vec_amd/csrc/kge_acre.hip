@@ -11,15 +11,12 @@
 //                                                              C is padded to the tile by zero operands (nothing padded in memory)
 //     c   = z3 + res (res broadcast over the channels)         added in k_acre_cc's epilogue; z2 and c STORED
 //     A   = relu(bn1(c)) * m1                                  feature-map dropout, site 1: a whole channel of a row; never stored
-//     u   = A fc_w^T + fc_b                                    [n, F] x [F, K] on the matrix cores, F split over workgroups (k_acre_fc),
-//                                                              the partial tiles added in split order (k_acre_fc_finish)
-//     x   = relu(bn2(u * m2))                                  hidden dropout, site 2; bn2 in BOTH forms
+//     u   = A fc_w^T + fc_b,  x = relu(bn2(u * m2))             the shared tail (kge_conv_tail.h); bn2 in BOTH forms
 // Every convolution has a bias iff acre_bias.  There is no nonlinearity between the three convolutions.  Batch norm, the two forms,
-// the statistics as fixed-order (mean, M2) sums and `dirs` are those of kge_interacte.hip, whose tail (fc, bn2, bn1, scatter) this
-// file repeats with P = 1.
+// the statistics as fixed-order (mean, M2) sums and `dirs` are those of kge_interacte.hip.
 //
 // Backward (training form only), dx the gradient at x:
-//     k_acre_bn2_bwd / k_acre_fc_gw / k_acre_fc_da / k_acre_bn1_part / k_acre_bn1_bwd_fin     as InteractE's
+//     the shared tail   du, g_bn2, g_fc_b, g_fc, dy1 = (du x fc_w) * m1 [bn1 > 0] and the two sums of bn1's backward with g_bn1
 //     k_acre_bn1_dc     dc = d loss / d c through bn1, in place of dy1; dz3 = dc and d res = sum over the channels of dc, ascending
 //     k_acre_cc_gw      per row: gwp[row][o, i, t] = sum_pos dz[o, pos] in[i, pos + tap t] on the matrix cores (M = o, N = i, the 400
 //                       positions are the contraction; both layers in LDS) and the bias partial gbp[row][o] = sum_pos dz[o, pos]
@@ -37,8 +34,7 @@
 // The dropout draw is the shared one (kge_projection.h spells the Philox counters out), with
 //     site 0: elem = pixel in [0, 400), entity half first;   site 1: elem = channel in [0, C);   site 2: elem = j in [0, K)
 //     row = row0 + position in the call's row list.  The fused step numbers the h rows 0 .. B-1 and the t rows B .. 2B-1.
-#include "kge_projection.h"
-#include "kge_mfma_blocks.h"
+#include "kge_conv_tail.h"
 
 namespace kge {
 
@@ -47,9 +43,6 @@ constexpr int kAcW = 20;            // image width and height
 constexpr int kAcHW = 400;
 constexpr int kAcMaxC = KGE_ACRE_MAX_CHANNELS;
 constexpr int kAcLS = 404;          // LDS stride of a channel's 400 values: 16 channels at one position fall on 16 distinct banks
-constexpr int kAcRows = 64;         // batch rows of a matrix-core tile of the fc kernels
-constexpr int kAcKC = 128;
-constexpr int kAcStride = 68;
 constexpr int kAcPT = 7;            // position tiles (of 16) per wave of k_acre_cc: 25 tiles over 4 waves
 static_assert(kAcMaxC % 16 == 0 && 4 * kAcPT >= kAcHW / 16 && kAcHW % 16 == 0, "tiles");
 
@@ -68,10 +61,26 @@ struct AcArgs {
     float* stats;                   // [dirs][SS]: mean0, rstd0, mean1[C], rstd1[C], mean2[K], rstd2[K]
     int SS, o1, o2;                 // SS = 2 + 2C + 2K, o1 = 2, o2 = 2 + 2C
 };
-__device__ __forceinline__ const float* ac_stats(const AcArgs& a, int d) { return a.stats + (size_t)d * a.SS; }
-__device__ __forceinline__ float ac_factor(const AcArgs& a, int site, int elem, int64_t gr) {
-    return a.on[site] ? drop_row_factor(a.key, site, elem, (int64_t)a.row0 + gr, a.thr[site], a.scale[site]) : 1.0f;
-}
+
+// the tail's policy (kge_conv_tail.h), both ways
+struct AcTail : TailReluM1f<AcArgs> {
+    using Desc = kge_acre_desc;
+    static constexpr const char* kBadArgs = "row0 + n below 2^32";
+    static int check(const Desc* d, const char* who, bool grads);
+    static int dim(const Desc*) { return kAcK; }
+    static int64_t rel_rows(const Desc* d) { return 2 * d->tot_relation; }   // (the relation table has 2 tot_relation rows, every one an ordinary row)
+    static const float* bias(const Desc* d) { return d->bias; }
+    static float* g_bias(const Desc* d) { return d->g_bias; }
+    static size_t saved_floats(const Desc* d, int64_t n, int dirs);
+    static size_t fwd_bytes(const Desc* d, int64_t n, int dirs);
+    static size_t bwd_bytes(const Desc* d, int64_t n, int dirs);
+    static int forward(const Desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int side, int64_t row0, float* x, float* saved, void* ws,
+                       hipStream_t st);
+    static int backward(const Desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int side, int64_t row0, const float* dx,
+                        const float* saved, void* ws, hipStream_t st);
+};
+KGE_CONV_TAIL_KERNELS(acre, AcTail, false)
+
 __device__ __forceinline__ float ac_comb(const AcArgs& a, const float* __restrict__ er, const float* __restrict__ rr, int c) {
     return c < a.K ? er[c] : rr[c - a.K];
 }
@@ -130,33 +139,6 @@ __global__ void __launch_bounds__(64) k_acre_bn0_stats(AcArgs a, const double2* 
     }
 }
 
-// one wave per channel: the statistics of every direction from the per-row partials part[row * pstride + c] (each over cnt values),
-// the tail direction first; mean / rstd -> stats, running buffers updated (momentum, unbiased variance)
-__global__ void __launch_bounds__(256) k_acre_bn_fin(AcArgs a, const float2* __restrict__ part, int chans, int pstride, int cnt, int mean_at,
-                                                     int rstd_at, float eps, float mom, float* __restrict__ run_mean,
-                                                     float* __restrict__ run_var) {
-    const int lane = threadIdx.x & 63;
-    const int c = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= chans) return;
-    for (int d = 0; d < a.dirs; ++d) {
-        const float2* __restrict__ p = part + (size_t)d * a.n * pstride + c;
-        float s = 0.0f;
-        for (int64_t b = lane; b < a.n; b += 64) s += p[b * pstride].x;
-        const float mean = wave_sum_xor(s) / (float)a.n;
-        float m2 = 0.0f;
-        for (int64_t b = lane; b < a.n; b += 64) { const float2 v = p[b * pstride]; const float dv = v.x - mean; m2 += v.y + (float)cnt * (dv * dv); }
-        m2 = wave_sum_xor(m2);
-        const float tot = (float)a.n * (float)cnt;
-        if (lane == 0) {
-            float* st = a.stats + (size_t)d * a.SS;
-            st[mean_at + c] = mean;
-            st[rstd_at + c] = 1.0f / sqrtf(m2 / tot + eps);
-            run_mean[c] = (1.0f - mom) * run_mean[c] + mom * mean;
-            run_var[c] = (1.0f - mom) * run_var[c] + mom * (m2 / (tot - 1.0f));
-        }
-    }
-}
-
 // eval form: bn0, bn1 and bn2 normalise with the running buffers
 __global__ void __launch_bounds__(256) k_acre_stats_eval(AcArgs a, float eps0, float eps1, float eps2, const float* __restrict__ rm0,
                                                          const float* __restrict__ rv0, const float* __restrict__ rm1,
@@ -180,7 +162,7 @@ __device__ __forceinline__ void ac_load_y0(const AcArgs& a, const float* __restr
     const float* __restrict__ er = a.ent + e[gr] * a.K;
     const float* __restrict__ rr = a.rel + r[gr] * a.K;
     for (int pix = threadIdx.x; pix < kAcHW; pix += 256)
-        y0s[pix] = ((ac_comb(a, er, rr, pix) - mean0) * g0 + b0) * ac_factor(a, 0, pix, gr);
+        y0s[pix] = ((ac_comb(a, er, rr, pix) - mean0) * g0 + b0) * tail_factor(a, 0, pix, gr);
     __syncthreads();
 }
 // the C channels of row gr of a stored layer [N, F] into LDS with channel stride kAcLS.  All 256 threads; ends with a barrier
@@ -196,7 +178,7 @@ __global__ void __launch_bounds__(256) k_acre_conv1(AcArgs a, int L, const int64
     __shared__ float y0s[kAcHW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gr = blockIdx.x;
-    ac_load_y0(a, ac_stats(a, (int)(gr / a.n)), e, r, gr, y0s);
+    ac_load_y0(a, tail_stats<AcTail>(a, (int)(gr / a.n)), e, r, gr, y0s);
     const int d = a.dil[L];
     for (int o = wave; o < a.C; o += 4) {
         float w[9];
@@ -229,7 +211,7 @@ __global__ void __launch_bounds__(256) k_acre_cc(AcArgs a, int L, int addres, co
     __shared__ float y0s[kAcHW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
     const int64_t gr = blockIdx.x;
-    if (addres) ac_load_y0(a, ac_stats(a, (int)(gr / a.n)), e, r, gr, y0s);
+    if (addres) ac_load_y0(a, tail_stats<AcTail>(a, (int)(gr / a.n)), e, r, gr, y0s);
     ac_load_layer(a, in, gr, ls);
     const int d = a.dil[L], C = a.C;
     const float* __restrict__ w = a.cw[L];
@@ -295,289 +277,12 @@ __global__ void __launch_bounds__(256) k_acre_c_stats(AcArgs a, const float* __r
         m2 = wave_sum_xor(m2);
         if (lane == 0) {
             part[gr * a.C + ch] = make_float2(mean, m2);
-            m1f[gr * a.C + ch] = ac_factor(a, 1, ch, gr);
-        }
-    }
-}
-
-// y1 = bn1(c) before the relu, and A[row][f] = relu(y1) * m1, formed from the stored c
-__device__ __forceinline__ float ac_bn1(const AcArgs& a, const float* __restrict__ st, const float* __restrict__ conv, int64_t gr, int f, int ch) {
-    return (conv[gr * a.F + f] - st[a.o1 + ch]) * (st[a.o1 + a.C + ch] * a.w1[ch]) + a.b1[ch];
-}
-template <bool TRAIN>
-__device__ __forceinline__ float ac_feature(const AcArgs& a, const float* __restrict__ st, const float* __restrict__ conv,
-                                            const float* __restrict__ m1f, int64_t gr, int f) {
-    const int ch = f / a.HW;
-    float v = fmaxf(ac_bn1(a, st, conv, gr, f, ch), 0.0f);
-    if constexpr (TRAIN) v *= m1f[gr * a.C + ch];
-    return v;
-}
-
-// upart[split][row][j] = sum over the split's f of A[row][f] fc_w[j][f].  grid (dirs x row tiles, tiles of 64 j, splits of F): wave w
-// owns columns 16 (4 blockIdx.y + w) + l; the A tile of 64 rows x 128 f is staged in LDS in the layout read_blocks<4> reads.
-// (k_acre_fc, k_acre_fc_gw and k_acre_fc_da are the third copy of InteractE's fc kernels; DESIGN.md section 21 notes it.)
-template <bool TRAIN>
-__global__ void __launch_bounds__(256) k_acre_fc(AcArgs a, const float* __restrict__ conv, const float* __restrict__ m1f, int tiles, int f_per,
-                                                 float* __restrict__ upart) {
-    __shared__ float As[kAcKC * kAcStride];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
-    const int d = (int)blockIdx.x / tiles;
-    const int64_t b0 = (int64_t)((int)blockIdx.x % tiles) * kAcRows, gr0 = (int64_t)d * a.n + b0;
-    const float* __restrict__ st = ac_stats(a, d);
-    const int j = 16 * ((int)blockIdx.y * 4 + wave) + l, jc = min(j, a.K - 1);
-    const int f_lo = (int)blockIdx.z * f_per, f_hi = min(a.F, f_lo + f_per);
-    const float* __restrict__ wp = a.fcw + (int64_t)jc * a.F;
-    f32x4v acc[4];
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) acc[mb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int fc0 = f_lo; fc0 < f_hi; fc0 += kAcKC) {
-        const int kn = min(kAcKC, f_hi - fc0), kn4 = (kn + 3) & ~3;
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < kAcKC * kAcRows; idx += 256) {
-            const int kl = idx & (kAcKC - 1), rl = idx >> 7;   // consecutive threads: consecutive f of one row
-            if (kl >= kn4) continue;
-            float v = 0.0f;
-            if (b0 + rl < a.n && kl < kn) v = ac_feature<TRAIN>(a, st, conv, m1f, gr0 + rl, fc0 + kl);
-            As[kl * kAcStride + 4 * (rl & 15) + (rl >> 4)] = v;
-        }
-        __syncthreads();
-        for (int s = 0; s < kn4; s += 4) {
-            const float b = wp[min(fc0 + s + g, a.F - 1)];   // (rows of As beyond the chunk are zero)
-            float av[4];
-            read_blocks<4>(&As[(s + g) * kAcStride], l, av);
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], b, acc[mb], 0, 0, 0);
-        }
-    }
-    if (j >= a.K) return;
-    float* __restrict__ dst = upart + (int64_t)blockIdx.z * a.n * a.dirs * a.K;
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t b = b0 + 16 * mb + 4 * g + q;
-            if (b < a.n) dst[((int64_t)d * a.n + b) * a.K + j] = acc[mb][q];
-        }
-}
-
-// one wave per column j: u = fc_b + the partial tiles in split order (kept for the backward); training form: the column's bn2
-// statistics per direction over u * m2 (tail first, running buffers updated); x = relu(bn2(u * m2)), in the eval form with the
-// running statistics k_acre_stats_eval left in `stats`
-template <bool TRAIN>
-__global__ void __launch_bounds__(256) k_acre_fc_finish(AcArgs a, const float* __restrict__ upart, int splits, float eps, float mom,
-                                                        float* __restrict__ run_mean, float* __restrict__ run_var, float* __restrict__ u,
-                                                        float* __restrict__ x) {
-    const int lane = threadIdx.x & 63;
-    const int j = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= a.K) return;
-    const int64_t N = a.n * a.dirs;
-    const float bias = a.fcb[j];
-    for (int d = 0; d < a.dirs; ++d) {
-        float* st = a.stats + (size_t)d * a.SS;
-        float s = 0.0f;
-        for (int64_t b = lane; b < a.n; b += 64) {
-            const int64_t gr = (int64_t)d * a.n + b;
-            float v = bias;
-            for (int sp = 0; sp < splits; ++sp) v += upart[((int64_t)sp * N + gr) * a.K + j];
-            u[gr * a.K + j] = v;
-            if constexpr (TRAIN) s += v * ac_factor(a, 2, j, gr);
-        }
-        float mean, rstd;
-        if constexpr (TRAIN) {
-            mean = wave_sum_xor(s) / (float)a.n;
-            float m2 = 0.0f;
-            for (int64_t b = lane; b < a.n; b += 64) {
-                const int64_t gr = (int64_t)d * a.n + b;
-                const float dv = u[gr * a.K + j] * ac_factor(a, 2, j, gr) - mean;   // (u: written by this lane above)
-                m2 += dv * dv;
-            }
-            m2 = wave_sum_xor(m2);
-            rstd = 1.0f / sqrtf(m2 / (float)a.n + eps);
-            if (lane == 0) {
-                st[a.o2 + j] = mean;
-                st[a.o2 + a.K + j] = rstd;
-                run_mean[j] = (1.0f - mom) * run_mean[j] + mom * mean;
-                run_var[j] = (1.0f - mom) * run_var[j] + mom * (m2 / ((float)a.n - 1.0f));
-            }
-        } else {
-            mean = st[a.o2 + j];
-            rstd = st[a.o2 + a.K + j];
-        }
-        const float gj = rstd * a.w2[j], bj = a.b2[j];
-        for (int64_t b = lane; b < a.n; b += 64) {
-            const int64_t gr = (int64_t)d * a.n + b;
-            float v = u[gr * a.K + j];
-            if constexpr (TRAIN) v *= ac_factor(a, 2, j, gr);
-            x[gr * a.K + j] = fmaxf((v - mean) * gj + bj, 0.0f);
+            m1f[gr * a.C + ch] = tail_factor(a, 1, ch, gr);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ backward
-// one wave per column j, the directions in order: dy2 = dx [bn2 > 0]; S1 = sum dy2, S2 = sum dy2 xh2; du = w2 rstd (dy2 - S1 / n - xh2 S2 / n) m2
-__global__ void __launch_bounds__(256) k_acre_bn2_bwd(AcArgs a, const float* __restrict__ dx, const float* __restrict__ u, float* __restrict__ du,
-                                                      float* __restrict__ g_w2, float* __restrict__ g_b2, float* __restrict__ g_fcb) {
-    const int lane = threadIdx.x & 63;
-    const int j = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= a.K) return;
-    const float w2 = a.w2[j], b2 = a.b2[j];
-    for (int d = 0; d < a.dirs; ++d) {
-        const float* __restrict__ st = ac_stats(a, d);
-        const float mean = st[a.o2 + j], rstd = st[a.o2 + a.K + j];
-        float s1 = 0.0f, s2 = 0.0f;
-        for (int64_t b = lane; b < a.n; b += 64) {
-            const int64_t gr = (int64_t)d * a.n + b;
-            const float xh = (u[gr * a.K + j] * ac_factor(a, 2, j, gr) - mean) * rstd;
-            const float dy = xh * w2 + b2 > 0.0f ? dx[gr * a.K + j] : 0.0f;
-            s1 += dy;
-            s2 += dy * xh;
-        }
-        s1 = wave_sum_xor(s1);
-        s2 = wave_sum_xor(s2);
-        const float inv = 1.0f / (float)a.n;
-        float sb = 0.0f;
-        for (int64_t b = lane; b < a.n; b += 64) {
-            const int64_t gr = (int64_t)d * a.n + b;
-            const float m = ac_factor(a, 2, j, gr);
-            const float xh = (u[gr * a.K + j] * m - mean) * rstd;
-            const float dy = xh * w2 + b2 > 0.0f ? dx[gr * a.K + j] : 0.0f;
-            const float v = (w2 * rstd) * (dy - s1 * inv - xh * (s2 * inv)) * m;
-            du[gr * a.K + j] = v;
-            sb += v;
-        }
-        sb = wave_sum_xor(sb);
-        if (lane == 0) { g_w2[j] += s2; g_b2[j] += s1; g_fcb[j] += sb; }
-    }
-}
-
-// g_fc[j][f] += sum over ALL rows (both directions, in row order) of du[row][j] A[row][f].  grid (ceil(F / 64), ceil(K / 128)): wave w
-// owns the 16 f of block 4 blockIdx.x + w for the 128 j of blockIdx.y (8 accumulator blocks); the batch is the contraction.
-__global__ void __launch_bounds__(256) k_acre_fc_gw(AcArgs a, const float* __restrict__ conv, const float* __restrict__ m1f,
-                                                    const float* __restrict__ du, float* __restrict__ g_fc) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
-    const int f = 16 * ((int)blockIdx.x * 4 + wave) + l;
-    if (f - l >= a.F) return;   // (wave-uniform)
-    const bool fok = f < a.F;
-    const int fcl = min(f, a.F - 1);
-    const int k0 = (int)blockIdx.y * 128;
-    const int nkb = min(8, (a.K - k0 + 15) / 16);
-    const int64_t N = a.n * a.dirs;
-    f32x4v acc[8];
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb) acc[kb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int64_t r0 = 0; r0 < N; r0 += 4) {
-        const int64_t gr = r0 + g;
-        const bool ok = gr < N;
-        const int64_t grc = ok ? gr : N - 1;
-        const float v1 = ac_feature<true>(a, ac_stats(a, (int)(grc / a.n)), conv, m1f, grc, fcl);
-        const float A = ok && fok ? v1 : 0.0f;
-        const float* __restrict__ dp = du + grc * a.K;
-#pragma unroll
-        for (int kb = 0; kb < 8; ++kb)
-            if (kb < nkb) {
-                const int j = k0 + 16 * kb + l;
-                const float v = ok && j < a.K ? dp[min(j, a.K - 1)] : 0.0f;
-                acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(v, A, acc[kb], 0, 0, 0);
-            }
-    }
-    if (!fok) return;
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = k0 + 16 * kb + 4 * g + q;
-            if (kb < nkb && j < a.K) g_fc[(int64_t)j * a.F + f] += acc[kb][q];
-        }
-}
-
-// dy1[row][f] = (sum_j du[row][j] fc_w[j][f]) * m1 [bn1 > 0]: the gradient at bn1's output.  grid (dirs x row tiles, ceil(F / 64))
-__global__ void __launch_bounds__(256) k_acre_fc_da(AcArgs a, const float* __restrict__ conv, const float* __restrict__ m1f,
-                                                    const float* __restrict__ du, int tiles, float* __restrict__ dy1) {
-    __shared__ float As[kAcKC * kAcStride];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
-    const int d = (int)blockIdx.x / tiles;
-    const int64_t b0 = (int64_t)((int)blockIdx.x % tiles) * kAcRows, gr0 = (int64_t)d * a.n + b0;
-    const float* __restrict__ st = ac_stats(a, d);
-    const int f = 16 * ((int)blockIdx.y * 4 + wave) + l;
-    const bool live = f - l < a.F;   // (wave-uniform)
-    const int fcl = min(f, a.F - 1);
-    f32x4v acc[4];
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) acc[mb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int j0 = 0; j0 < a.K; j0 += kAcKC) {
-        const int kn = min(kAcKC, a.K - j0), kn4 = (kn + 3) & ~3;
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < kAcKC * kAcRows; idx += 256) {
-            const int kl = idx & (kAcKC - 1), rl = idx >> 7;
-            if (kl >= kn4) continue;
-            float v = 0.0f;
-            if (b0 + rl < a.n && kl < kn) v = du[(gr0 + rl) * a.K + j0 + kl];
-            As[kl * kAcStride + 4 * (rl & 15) + (rl >> 4)] = v;
-        }
-        __syncthreads();
-        if (live)
-            for (int s = 0; s < kn4; s += 4) {
-                const float b = a.fcw[(int64_t)min(j0 + s + g, a.K - 1) * a.F + fcl];   // (rows of As beyond the chunk are zero)
-                float av[4];
-                read_blocks<4>(&As[(s + g) * kAcStride], l, av);
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], b, acc[mb], 0, 0, 0);
-            }
-    }
-    if (!live || f >= a.F) return;
-    const int ch = f / a.HW;
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t b = b0 + 16 * mb + 4 * g + q;
-            if (b >= a.n) continue;
-            const int64_t gr = (int64_t)d * a.n + b;
-            const float keep = ac_bn1(a, st, conv, gr, f, ch) > 0.0f ? m1f[gr * a.C + ch] : 0.0f;
-            dy1[gr * a.F + f] = acc[mb][q] * keep;
-        }
-}
-
-// one wave per (row, channel): S1 = sum dy1, S2 = sum dy1 xh1 over the row's 400 outputs
-__global__ void __launch_bounds__(256) k_acre_bn1_part(AcArgs a, const float* __restrict__ conv, const float* __restrict__ dy1,
-                                                       float2* __restrict__ part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t gr = blockIdx.x;
-    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
-    for (int ch = (int)blockIdx.y * 4 + wave; ch < a.C; ch += 4 * (int)gridDim.y) {
-        const float mean = st[a.o1 + ch], rstd = st[a.o1 + a.C + ch];
-        const int64_t base = gr * a.F + (int64_t)ch * a.HW;
-        float s1 = 0.0f, s2 = 0.0f;
-        for (int pos = lane; pos < a.HW; pos += 64) {
-            const float dy = dy1[base + pos];
-            s1 += dy;
-            s2 += dy * ((conv[base + pos] - mean) * rstd);
-        }
-        s1 = wave_sum_xor(s1);
-        s2 = wave_sum_xor(s2);
-        if (lane == 0) part[gr * a.C + ch] = make_float2(s1, s2);
-    }
-}
-
-// one wave per channel, the directions in order: the two sums over the direction's rows -> sums[d][C], g_bn1
-__global__ void __launch_bounds__(256) k_acre_bn1_bwd_fin(AcArgs a, const float2* __restrict__ part, float2* __restrict__ sums,
-                                                          float* __restrict__ g_w1, float* __restrict__ g_b1) {
-    const int lane = threadIdx.x & 63;
-    const int ch = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ch >= a.C) return;
-    for (int d = 0; d < a.dirs; ++d) {
-        float s1 = 0.0f, s2 = 0.0f;
-        for (int64_t b = lane; b < a.n; b += 64) {
-            const float2 v = part[((int64_t)d * a.n + b) * a.C + ch];
-            s1 += v.x;
-            s2 += v.y;
-        }
-        s1 = wave_sum_xor(s1);
-        s2 = wave_sum_xor(s2);
-        if (lane == 0) { sums[d * a.C + ch] = make_float2(s1, s2); g_w1[ch] += s2; g_b1[ch] += s1; }
-    }
-}
-
 // one wave per (row, channel): dc = w1 rstd1 (dy1 - S1 / N1 - xh1 S2 / N1), written over dy1 IN PLACE (a lane reads and writes its own
 // positions)
 __global__ void __launch_bounds__(256) k_acre_bn1_dc(AcArgs a, const float* __restrict__ conv, float* __restrict__ dy1,
@@ -585,7 +290,7 @@ __global__ void __launch_bounds__(256) k_acre_bn1_dc(AcArgs a, const float* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gr = blockIdx.x;
     const int d = (int)(gr / a.n);
-    const float* __restrict__ st = ac_stats(a, d);
+    const float* __restrict__ st = tail_stats<AcTail>(a, d);
     const float invN1 = 1.0f / ((float)a.n * (float)a.HW);
     for (int ch = (int)blockIdx.y * 4 + wave; ch < a.C; ch += 4 * (int)gridDim.y) {
         const float mean = st[a.o1 + ch], rstd = st[a.o1 + a.C + ch], gain = a.w1[ch] * rstd;
@@ -653,7 +358,7 @@ __global__ void __launch_bounds__(256) k_acre_c1_bwd(AcArgs a, int L, const int6
     __shared__ float red[8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gr = blockIdx.x;
-    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    const float* __restrict__ st = tail_stats<AcTail>(a, (int)(gr / a.n));
     const int d = a.dil[L], C = a.C;
     for (int i = threadIdx.x; i < 9 * C; i += 256) wl[i] = a.cw[L][i];
     ac_load_y0(a, st, e, r, gr, y0s);
@@ -694,7 +399,7 @@ __global__ void __launch_bounds__(256) k_acre_c1_bwd(AcArgs a, int L, const int6
             for (int ch = 0; ch < C; ++ch) rs += dc[gr * a.F + (int64_t)ch * kAcHW + pix];
             v += rs;
         }
-        v *= ac_factor(a, 0, pix, gr);
+        v *= tail_factor(a, 0, pix, gr);
         dimg[gr * kAcHW + pix] = v;
         t1 += v;
         t2 += v * ((ac_comb(a, er, rr, pix) - mean0) * rstd0);
@@ -748,7 +453,7 @@ __global__ void __launch_bounds__(256) k_acre_dcomb(AcArgs a, const int64_t* __r
                                                     float* __restrict__ drel) {
     const int64_t gr = blockIdx.x;
     const int d = (int)(gr / a.n);
-    const float* __restrict__ st = ac_stats(a, d);
+    const float* __restrict__ st = tail_stats<AcTail>(a, d);
     const float* __restrict__ er = a.ent + e[gr] * a.K;
     const float* __restrict__ rr = a.rel + r[gr] * a.K;
     const float inv = 1.0f / ((float)a.n * (float)a.HW);
@@ -759,34 +464,6 @@ __global__ void __launch_bounds__(256) k_acre_dcomb(AcArgs a, const int64_t* __r
         const float v = (a.w0[0] * rstd0) * (dimg[gr * a.HW + j] - T.x * inv - xh * (T.y * inv));
         if (j < a.K) dent[gr * a.K + j] = v;
         else drel[gr * a.K + j - a.K] = v;
-    }
-}
-
-// dst[ids[b]][0 .. width) += src[b * width .. + width) for every row b (id 0 included: no padding_idx), in row order and without
-// atomics: the wave of the FIRST row that names an id owns that id, walks the later rows 64 at a time (ballot) and adds their shares
-// in order
-__global__ void __launch_bounds__(256) k_acre_scatter(const int64_t* __restrict__ ids, int64_t n, int width, const float* __restrict__ src,
-                                                      float* __restrict__ dst) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    const int64_t id = ids[row];
-    bool dup = false;
-    for (int64_t b = lane; b < row; b += 64) dup |= ids[b] == id;
-    if (__any(dup)) return;   // (wave-uniform)
-    for (int c0 = 0; c0 < width; c0 += 64) {
-        const int c = c0 + lane;
-        float sum = 0.0f;
-        for (int64_t b0 = row & ~(int64_t)63; b0 < n; b0 += 64) {
-            const int64_t b = b0 + lane;
-            unsigned long long m = __ballot(b >= row && b < n && ids[b] == id);
-            while (m) {
-                const int64_t s = b0 + __builtin_ctzll(m);
-                m &= m - 1;
-                if (c < width) sum += src[s * width + c];
-            }
-        }
-        if (c < width) dst[id * width + c] += sum;
     }
 }
 
@@ -810,9 +487,9 @@ __global__ void __launch_bounds__(256) k_acrp_y0(AcArgs a, const int64_t* __rest
     if (i >= a.n * a.dirs * kAcHW) return;
     const int64_t gr = i / kAcHW;
     const int pix = (int)(i - gr * kAcHW);
-    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    const float* __restrict__ st = tail_stats<AcTail>(a, (int)(gr / a.n));
     const float mean0 = st[0], g0 = st[1] * a.w0[0], b0 = a.b0[0];
-    y0d[i] = ((ac_comb(a, a.ent + e[gr] * a.K, a.rel + r[gr] * a.K, pix) - mean0) * g0 + b0) * ac_factor(a, 0, pix, gr);
+    y0d[i] = ((ac_comb(a, a.ent + e[gr] * a.K, a.rel + r[gr] * a.K, pix) - mean0) * g0 + b0) * tail_factor(a, 0, pix, gr);
 }
 
 // out[m][col] = sum_k A[m][k] B[k][col] on v_mfma_f32_16x16x4_f32, grid (ceil(M / 64), ceil(cols / 128)): the A tile of 64 m x 128 k is
@@ -825,11 +502,11 @@ __global__ void __launch_bounds__(256) k_acrp_y0(AcArgs a, const int64_t* __rest
 template <int MODE>
 __global__ void __launch_bounds__(256) k_acrp_gate(AcArgs a, const float* __restrict__ gw, const float* __restrict__ gb,
                                                    const float* __restrict__ src, const float* __restrict__ add, float* __restrict__ out) {
-    __shared__ float As[kAcKC * kAcStride];
+    __shared__ float As[kTailKC * kTailStride];
     constexpr bool PAIRS = MODE == kGateZ || MODE == kGateDz, FWD = MODE == kGateY0 || MODE == kGateZ;
     constexpr int KT = MODE == kGateZ ? 3 * kAcHW : kAcHW, COLS = MODE == kGateDz ? 3 * kAcHW : kAcHW, OFF = PAIRS ? kAcHW : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 15, g = lane >> 4;
-    const int64_t M = a.n * a.dirs * (PAIRS ? a.C : 1), m0 = (int64_t)blockIdx.x * kAcRows, LAYER = M * kAcHW;
+    const int64_t M = a.n * a.dirs * (PAIRS ? a.C : 1), m0 = (int64_t)blockIdx.x * kTailRows, LAYER = M * kAcHW;
     int col[kApNB];
     bool live[kApNB];
 #pragma unroll
@@ -845,11 +522,11 @@ __global__ void __launch_bounds__(256) k_acrp_gate(AcArgs a, const float* __rest
     for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
         for (int nb = 0; nb < kApNB; ++nb) acc[mb][nb] = sub[mb][nb] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int k0 = 0; k0 < KT; k0 += kAcKC) {
-        const int kn = min(kAcKC, KT - k0), kn4 = (kn + 3) & ~3;
+    for (int k0 = 0; k0 < KT; k0 += kTailKC) {
+        const int kn = min(kTailKC, KT - k0), kn4 = (kn + 3) & ~3;
         __syncthreads();
-        for (int idx = threadIdx.x; idx < kAcKC * kAcRows; idx += 256) {
-            const int kl = idx & (kAcKC - 1), rl = idx >> 7;   // consecutive threads: consecutive k of one m
+        for (int idx = threadIdx.x; idx < kTailKC * kTailRows; idx += 256) {
+            const int kl = idx & (kTailKC - 1), rl = idx >> 7;   // consecutive threads: consecutive k of one m
             if (kl >= kn4) continue;
             float v = 0.0f;
             if (m0 + rl < M && kl < kn) {
@@ -858,7 +535,7 @@ __global__ void __launch_bounds__(256) k_acrp_gate(AcArgs a, const float* __rest
                 if constexpr (MODE == kGateZ) v = src[(int64_t)(k / kAcHW) * LAYER + m * kAcHW + k % kAcHW];
                 else v = src[m * kAcHW + k];
             }
-            As[kl * kAcStride + 4 * (rl & 15) + (rl >> 4)] = v;
+            As[kl * kTailStride + 4 * (rl & 15) + (rl >> 4)] = v;
         }
         __syncthreads();
         if (live[0])
@@ -875,7 +552,7 @@ __global__ void __launch_bounds__(256) k_acrp_gate(AcArgs a, const float* __rest
                 for (int i = 0; i < kApSub / 4; ++i) {
                     if (i >= ns) continue;
                     float av[4];
-                    read_blocks<4>(&As[(s0 + 4 * i + g) * kAcStride], l, av);
+                    read_blocks<4>(&As[(s0 + 4 * i + g) * kTailStride], l, av);
 #pragma unroll
                     for (int nb = 0; nb < kApNB; ++nb)
                         if (live[nb])
@@ -983,7 +660,7 @@ __global__ void __launch_bounds__(256) k_acrp_conv_bwd(AcArgs a, const int64_t* 
     __shared__ float red[8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gr = blockIdx.x, N = a.n * a.dirs;
-    const float* __restrict__ st = ac_stats(a, (int)(gr / a.n));
+    const float* __restrict__ st = tail_stats<AcTail>(a, (int)(gr / a.n));
     const int C = a.C;
     if (threadIdx.x < C) dzs[threadIdx.x * kAcLS + kAcHW] = 0.0f;   // a zero behind each channel's 400 values (the stride leaves room)
     if (threadIdx.x == 0) y0s[kAcHW] = 0.0f;                        // ... and behind y0's
@@ -1048,7 +725,7 @@ __global__ void __launch_bounds__(256) k_acrp_conv_bwd(AcArgs a, const int64_t* 
     for (int j = 0; j < 2; ++j) {
         const int pix = threadIdx.x + 256 * j;
         if (pix >= kAcHW) continue;
-        const float v = (acc[j] + dres[gr * kAcHW + pix]) * ac_factor(a, 0, pix, gr);
+        const float v = (acc[j] + dres[gr * kAcHW + pix]) * tail_factor(a, 0, pix, gr);
         dimg[gr * kAcHW + pix] = v;
         t1 += v;
         t2 += v * ((ac_comb(a, er, rr, pix) - mean0) * rstd0);
@@ -1061,7 +738,7 @@ __global__ void __launch_bounds__(256) k_acrp_conv_bwd(AcArgs a, const int64_t* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
-static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
+int AcTail::check(const kge_acre_desc* d, const char* who, bool grads) {
     if (!d) { set_error("%s: null descriptor", who); return -1; }
     const void* t[] = {d->bias, d->ent, d->rel, d->bn0_w, d->bn0_b, d->bn1_w, d->bn1_b, d->bn2_w, d->bn2_b, d->fc_w, d->fc_b,
                        d->conv1_w, d->conv2_w, d->conv3_w, d->bn0_mean, d->bn0_var, d->bn1_mean, d->bn1_var, d->bn2_mean, d->bn2_var};
@@ -1097,15 +774,7 @@ static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
         set_error("%s: the gate pointers must both be set in the parallel way and both be NULL in the serial way", who);
         return -1;
     }
-    for (int i = 0; i < 3; ++i) {
-        if (!(d->momentum[i] > 0.0f && d->momentum[i] <= 1.0f)) {
-            set_error("%s: momentum %d must be in (0, 1] (got %g; the cumulative average is not built)", who, i, (double)d->momentum[i]);
-            return -1;
-        }
-        if (!(d->eps[i] >= 0.0f)) { set_error("%s: eps %d must not be negative (got %g)", who, i, (double)d->eps[i]); return -1; }
-    }
-    const float p[3] = {d->input_dropout, d->feature_map_dropout, d->hidden_dropout};
-    if (drop_check(who, p, 3, d->offset)) return -1;
+    if (tail_check_rates(d, who)) return -1;
     if (grads) {
         const void* g[] = {d->g_bias, d->g_ent, d->g_rel, d->g_bn0_w, d->g_bn0_b, d->g_bn1_w, d->g_bn1_b, d->g_bn2_w, d->g_bn2_b, d->g_fc_w,
                            d->g_fc_b, d->g_conv1_w, d->g_conv2_w, d->g_conv3_w};
@@ -1118,67 +787,35 @@ static int ac_check(const kge_acre_desc* d, const char* who, bool grads) {
     }
     return 0;
 }
-// rows per direction of a call in training form
-static int ac_check_rows(const kge_acre_desc* d, const char* who, int64_t n) {
-    if (d->train && n == 1) {
-        set_error("%s: batch norm in training form needs more than one row per direction (got n = 1)", who);
-        return -1;
-    }
-    return 0;
-}
 
 static int ac_ss(const kge_acre_desc* d) { return 2 + 2 * d->in_channels + 2 * kAcK; }
 static int ac_f(const kge_acre_desc* d) { return d->in_channels * kAcHW; }
 
 static AcArgs ac_args(const kge_acre_desc* d, int64_t n, int dirs, int64_t row0, float* stats) {
     AcArgs a{};
-    a.ent = d->ent; a.rel = d->rel; a.w0 = d->bn0_w; a.b0 = d->bn0_b; a.w1 = d->bn1_w; a.b1 = d->bn1_b; a.w2 = d->bn2_w; a.b2 = d->bn2_b;
-    a.fcw = d->fc_w; a.fcb = d->fc_b;
+    tail_fill(a, d, n, dirs, row0, stats);
+    a.ent = d->ent; a.rel = d->rel; a.w0 = d->bn0_w; a.b0 = d->bn0_b;
     a.cw[0] = d->conv1_w; a.cw[1] = d->conv2_w; a.cw[2] = d->conv3_w;
     a.cb[0] = d->conv1_b; a.cb[1] = d->conv2_b; a.cb[2] = d->conv3_b;
     a.dil[0] = d->first_atrous; a.dil[1] = d->second_atrous; a.dil[2] = d->third_atrous;
     a.K = kAcK; a.HW = kAcHW; a.C = d->in_channels; a.F = ac_f(d);
     a.SS = ac_ss(d); a.o1 = 2; a.o2 = 2 + 2 * a.C;
-    a.dirs = dirs; a.n = n; a.row0 = (uint32_t)row0;
-    a.key = drop_key(d->seed, d->offset);
-    const float p[3] = {d->input_dropout, d->feature_map_dropout, d->hidden_dropout};
-    for (int i = 0; i < 3; ++i) {
-        a.on[i] = d->train != 0 && p[i] > 0.0f;
-        a.thr[i] = drop_thr(p[i]);
-        a.scale[i] = drop_scale(p[i]);
-    }
-    a.stats = stats;
     return a;
 }
-
-static int ac_tiles(int64_t n) { return (int)((n + kAcRows - 1) / kAcRows); }
-// f handled by one workgroup of the fc forward: enough workgroups to fill the device, a function of the shapes alone (the split order
-// is the summation order); a multiple of 4
-static int ac_f_per(int F, int64_t n, int dirs) {
-    const int64_t base = (int64_t)dirs * ac_tiles(n) * ((kAcK + 63) / 64);
-    int64_t splits = (512 + base - 1) / base;
-    if (splits > 64) splits = 64;
-    if (splits < 1) splits = 1;
-    int per = (int)((F + splits - 1) / splits);
-    per = (per + 3) & ~3;
-    return per < 4 ? 4 : per;
-}
-static int ac_splits(int F, int per) { return (F + per - 1) / per; }
 
 // saved (floats): c [N, F] | z1 [N, F] | z2 [N, F] | u [N, K] | m1f [N, C] | stats [dirs][2 + 2C + 2K]; the parallel way keeps a
 // third layer, c | z_1 | z_2 | z_3 | u | m1f | stats: the z_i are saved, not recomputed (the backward reads them twice, as the
 // gate's input and never as a convolution's)
 static int ac_layers(const kge_acre_desc* d) { return d->way ? 4 : 3; }
-static size_t ac_saved_floats(const kge_acre_desc* d, int64_t n, int dirs) {
+size_t AcTail::saved_floats(const kge_acre_desc* d, int64_t n, int dirs) {
     return (size_t)dirs * ((size_t)n * ((size_t)ac_layers(d) * ac_f(d) + kAcK + d->in_channels) + ac_ss(d));
 }
 static size_t ac_part_bytes(const kge_acre_desc* d, size_t N) { return align256(N * (d->in_channels > 2 ? d->in_channels : 2) * sizeof(float2)); }
 // forward: row partials float2 [N, max(C, 2)] (bn0's are double2 [N]) | upart [splits, N, K] | the parallel way: yg [N, 400] | y0d [N, 400]
 static size_t ac_upart_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
-    const int F = ac_f(d);
-    return align256((size_t)ac_splits(F, ac_f_per(F, n, dirs)) * (size_t)n * dirs * kAcK * sizeof(float));
+    return tail_upart_bytes(kAcK, ac_f(d), n, dirs);
 }
-static size_t ac_fwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
+size_t AcTail::fwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
     const size_t N = (size_t)n * dirs;
     return ac_part_bytes(d, N) + ac_upart_bytes(d, n, dirs) + (d->way ? 2 * align256(N * kAcHW * sizeof(float)) : 0);
 }
@@ -1247,12 +884,12 @@ static ApBwdPlan ap_bwd_plan(const kge_acre_desc* d, int64_t n, int dirs) {
     p.total = p.t0 + align256((size_t)dirs * sizeof(float2));
     return p;
 }
-static size_t ac_bwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
+size_t AcTail::bwd_bytes(const kge_acre_desc* d, int64_t n, int dirs) {
     return d->way ? ap_bwd_plan(d, n, dirs).total : ac_bwd_plan(d, n, dirs).total;
 }
 
-static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int64_t row0, float* x, float* saved,
-                      void* ws, hipStream_t st) {
+int AcTail::forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int, int64_t row0, float* x, float* saved,
+                    void* ws, hipStream_t st) {
     const int64_t N = n * dirs;
     const int C = d->in_channels, F = ac_f(d);
     float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + (ac_layers(d) - 2) * N * F, *m1f = u + N * kAcK, *stats = m1f + N * C;
@@ -1274,9 +911,9 @@ static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r
         float* y0d = (float*)((char*)yg + align256((size_t)N * kAcHW * sizeof(float)));
         hipLaunchKernelGGL(k_acrp_y0, dim3((unsigned)((N * kAcHW + 255) / 256)), dim3(256), 0, st, a, e, r, y0d);
         for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(k_acre_conv1, dim3((unsigned)N), dim3(256), 0, st, a, i, e, r, z1 + i * N * F);
-        hipLaunchKernelGGL((k_acrp_gate<kGateY0>), dim3((unsigned)((N + kAcRows - 1) / kAcRows), 4), dim3(256), 0, st, a, d->gate_w, d->gate_b,
+        hipLaunchKernelGGL((k_acrp_gate<kGateY0>), dim3((unsigned)((N + kTailRows - 1) / kTailRows), 4), dim3(256), 0, st, a, d->gate_w, d->gate_b,
                            (const float*)y0d, (const float*)nullptr, yg);
-        hipLaunchKernelGGL((k_acrp_gate<kGateZ>), dim3((unsigned)((N * C + kAcRows - 1) / kAcRows), 4), dim3(256), 0, st, a, d->gate_w,
+        hipLaunchKernelGGL((k_acrp_gate<kGateZ>), dim3((unsigned)((N * C + kTailRows - 1) / kTailRows), 4), dim3(256), 0, st, a, d->gate_w,
                            d->gate_b, (const float*)z1, (const float*)yg, c);
         if (int rc = check_launch("k_acre_row_stats / k_acre_bn0_stats / k_acrp_y0 / k_acre_conv1 / k_acrp_gate")) return rc;
     } else {
@@ -1287,22 +924,10 @@ static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r
     }
     if (train) {
         hipLaunchKernelGGL(k_acre_c_stats, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, part, m1f);
-        hipLaunchKernelGGL(k_acre_bn_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part, C, C, kAcHW, a.o1, a.o1 + C, d->eps[1],
+        hipLaunchKernelGGL(k_acre_bn_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part, C, C, 1, kAcHW, a.o1, a.o1 + C, d->eps[1],
                            d->momentum[1], d->bn1_mean, d->bn1_var);
     }
-    const int per = ac_f_per(F, n, dirs), splits = ac_splits(F, per), tiles = ac_tiles(n);
-    const dim3 grid((unsigned)(dirs * tiles), (unsigned)((kAcK + 63) / 64), (unsigned)splits);
-    const unsigned col_blocks = (unsigned)((kAcK + 3) / 4);
-    if (train) {
-        hipLaunchKernelGGL((k_acre_fc<true>), grid, dim3(256), 0, st, a, c, m1f, tiles, per, upart);
-        hipLaunchKernelGGL((k_acre_fc_finish<true>), dim3(col_blocks), dim3(256), 0, st, a, upart, splits, d->eps[2], d->momentum[2], d->bn2_mean,
-                           d->bn2_var, u, x);
-    } else {
-        hipLaunchKernelGGL((k_acre_fc<false>), grid, dim3(256), 0, st, a, c, m1f, tiles, per, upart);
-        hipLaunchKernelGGL((k_acre_fc_finish<false>), dim3(col_blocks), dim3(256), 0, st, a, upart, splits, d->eps[2], d->momentum[2],
-                           d->bn2_mean, d->bn2_var, u, x);
-    }
-    return check_launch("k_acre_c_stats / k_acre_fc / k_acre_fc_finish");
+    return tail_fc_forward<AcTail>(d, a, c, m1f, upart, u, x, st);   // (its check covers k_acre_c_stats and k_acre_bn_fin)
 }
 
 // the parallel way's backward: the serial tail down to dc, the gate (weight, bias and input gradients), the three convolutions of y0 at
@@ -1310,7 +935,7 @@ static int ac_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r
 static int ap_backward(const kge_acre_desc* d, const AcArgs& a, const int64_t* e, const int64_t* r, int64_t n, int dirs, const float* dx,
                        const float* c, const float* z, const float* u, const float* m1f, void* ws, hipStream_t st) {
     const int64_t N = n * dirs;
-    const int C = d->in_channels, F = ac_f(d);
+    const int C = d->in_channels;
     const int64_t M = N * C;
     const ApBwdPlan p = ap_bwd_plan(d, n, dirs);
     char* w = (char*)ws;
@@ -1318,15 +943,8 @@ static int ap_backward(const kge_acre_desc* d, const AcArgs& a, const int64_t* e
     float *y0d = (float*)(w + p.y0d), *gpart = (float*)(w + p.gpart), *gwp = (float*)(w + p.gwp), *gbp = d->acre_bias ? (float*)(w + p.gbp) : nullptr;
     float *dimg = (float*)(w + p.dimg), *dent = (float*)(w + p.dent), *drel = (float*)(w + p.drel);
     float2 *part1 = (float2*)(w + p.part1), *sums = (float2*)(w + p.sums), *pt0 = (float2*)(w + p.pt0), *t0 = (float2*)(w + p.t0);
-    const unsigned row_blocks = (unsigned)((N + 3) / 4), col_blocks = (unsigned)((kAcK + 3) / 4);
-    const int tiles = ac_tiles(n);
     const int chan_groups = (C + 3) / 4 < 8 ? (C + 3) / 4 : 8;
-    hipLaunchKernelGGL(k_acre_bn2_bwd, dim3(col_blocks), dim3(256), 0, st, a, dx, u, du, d->g_bn2_w, d->g_bn2_b, d->g_fc_b);
-    hipLaunchKernelGGL(k_acre_fc_gw, dim3((unsigned)((F + 63) / 64), (unsigned)((kAcK + 127) / 128)), dim3(256), 0, st, a, c, m1f, du, d->g_fc_w);
-    hipLaunchKernelGGL(k_acre_fc_da, dim3((unsigned)(dirs * tiles), (unsigned)((F + 63) / 64)), dim3(256), 0, st, a, c, m1f, du, tiles, dc);
-    if (int rc = check_launch("k_acre_bn2_bwd / k_acre_fc_gw / k_acre_fc_da")) return rc;
-    hipLaunchKernelGGL(k_acre_bn1_part, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dc, part1);
-    hipLaunchKernelGGL(k_acre_bn1_bwd_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part1, sums, d->g_bn1_w, d->g_bn1_b);
+    if (int rc = tail_backward<AcTail>(d, a, dx, c, m1f, u, du, dc, part1, sums, chan_groups, st)) return rc;
     hipLaunchKernelGGL(k_acre_bn1_dc, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dc, sums);
     if (int rc = check_launch("k_acre_bn1_part / k_acre_bn1_bwd_fin / k_acre_bn1_dc")) return rc;
     // the gate: dcs = the channel sum of dc; g_gate_b; g_gate_w's y0 block over the rows and its z blocks over the pairs in splits;
@@ -1342,9 +960,9 @@ static int ap_backward(const kge_acre_desc* d, const AcArgs& a, const int64_t* e
                        (const float*)dc, z, per, gpart);
     hipLaunchKernelGGL(k_acrp_gw_fin, dim3((unsigned)((kAcHW * 3 * kAcHW + 255) / 256)), dim3(256), 0, st, (const float*)gpart, splits, d->g_gate_w);
     if (int rc = check_launch("k_acrp_chsum / k_acrp_y0 / k_acre_rowsum / k_acrp_gate_gw / k_acrp_gw_fin")) return rc;
-    hipLaunchKernelGGL((k_acrp_gate<kGateDres>), dim3((unsigned)((N + kAcRows - 1) / kAcRows), 4), dim3(256), 0, st, a, d->gate_w, d->gate_b,
+    hipLaunchKernelGGL((k_acrp_gate<kGateDres>), dim3((unsigned)((N + kTailRows - 1) / kTailRows), 4), dim3(256), 0, st, a, d->gate_w, d->gate_b,
                        (const float*)dcs, (const float*)nullptr, dres);
-    hipLaunchKernelGGL((k_acrp_gate<kGateDz>), dim3((unsigned)((M + kAcRows - 1) / kAcRows), (unsigned)((3 * kAcHW + 127) / 128)), dim3(256), 0, st, a,
+    hipLaunchKernelGGL((k_acrp_gate<kGateDz>), dim3((unsigned)((M + kTailRows - 1) / kTailRows), (unsigned)((3 * kAcHW + 127) / 128)), dim3(256), 0, st, a,
                        d->gate_w, d->gate_b, (const float*)dc, (const float*)nullptr, dz);
     hipLaunchKernelGGL(k_acrp_conv_bwd, dim3((unsigned)N), dim3(256), 0, st, a, e, r, (const float*)dz, (const float*)dres, gwp, gbp, dimg, pt0);
     if (int rc = check_launch("k_acrp_gate / k_acrp_conv_bwd")) return rc;
@@ -1357,13 +975,13 @@ static int ap_backward(const kge_acre_desc* d, const AcArgs& a, const int64_t* e
     hipLaunchKernelGGL(k_acre_bn0_fin, dim3(1), dim3(64), 0, st, a, pt0, t0, d->g_bn0_w, d->g_bn0_b);
     hipLaunchKernelGGL(k_acre_dcomb, dim3((unsigned)N), dim3(256), 0, st, a, e, r, dimg, t0, dent, drel);
     if (int rc = check_launch("k_acre_rowsum / k_acre_bn0_fin / k_acre_dcomb")) return rc;
-    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, e, N, kAcK, dent, d->g_ent);
-    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, r, N, kAcK, drel, d->g_rel);
+    tail_scatter<AcTail>(e, N, kAcK, dent, kAcK, d->g_ent, st);   // (every id is scattered, id 0 included: no padding_idx)
+    tail_scatter<AcTail>(r, N, kAcK, drel, kAcK, d->g_rel, st);
     return check_launch("k_acre_scatter");
 }
 
-static int ac_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int64_t row0, const float* dx,
-                       const float* saved, void* ws, hipStream_t st) {
+int AcTail::backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int dirs, int, int64_t row0, const float* dx,
+                     const float* saved, void* ws, hipStream_t st) {
     const int64_t N = n * dirs;
     const int C = d->in_channels, F = ac_f(d);
     const float *c = saved, *z1 = c + N * F, *z2 = z1 + N * F, *u = z2 + (ac_layers(d) - 2) * N * F, *m1f = u + N * kAcK;
@@ -1379,15 +997,8 @@ static int ac_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* 
     if (d->acre_bias)
         for (int i = 0; i < 3; ++i) gbp[i] = (float*)(w + p.gbp + i * gbs);
     float2 *part1 = (float2*)(w + p.part1), *sums = (float2*)(w + p.sums), *pt0 = (float2*)(w + p.pt0), *t0 = (float2*)(w + p.t0);
-    const unsigned row_blocks = (unsigned)((N + 3) / 4), col_blocks = (unsigned)((kAcK + 3) / 4);
-    const int tiles = ac_tiles(n);
     const int chan_groups = (C + 3) / 4 < 8 ? (C + 3) / 4 : 8;
-    hipLaunchKernelGGL(k_acre_bn2_bwd, dim3(col_blocks), dim3(256), 0, st, a, dx, u, du, d->g_bn2_w, d->g_bn2_b, d->g_fc_b);
-    hipLaunchKernelGGL(k_acre_fc_gw, dim3((unsigned)((F + 63) / 64), (unsigned)((kAcK + 127) / 128)), dim3(256), 0, st, a, c, m1f, du, d->g_fc_w);
-    hipLaunchKernelGGL(k_acre_fc_da, dim3((unsigned)(dirs * tiles), (unsigned)((F + 63) / 64)), dim3(256), 0, st, a, c, m1f, du, tiles, dy1);
-    if (int rc = check_launch("k_acre_bn2_bwd / k_acre_fc_gw / k_acre_fc_da")) return rc;
-    hipLaunchKernelGGL(k_acre_bn1_part, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dy1, part1);
-    hipLaunchKernelGGL(k_acre_bn1_bwd_fin, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, a, part1, sums, d->g_bn1_w, d->g_bn1_b);
+    if (int rc = tail_backward<AcTail>(d, a, dx, c, m1f, u, du, dy1, part1, sums, chan_groups, st)) return rc;
     hipLaunchKernelGGL(k_acre_bn1_dc, dim3((unsigned)N, (unsigned)chan_groups), dim3(256), 0, st, a, c, dy1, sums);
     if (int rc = check_launch("k_acre_bn1_part / k_acre_bn1_bwd_fin / k_acre_bn1_dc")) return rc;
     // dz3 = dc: conv3's partials against z2, dz2 = conv3^T dz3; conv2's against z1, dz1 = conv2^T dz2; conv1's against y0
@@ -1408,48 +1019,9 @@ static int ac_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* 
     hipLaunchKernelGGL(k_acre_bn0_fin, dim3(1), dim3(64), 0, st, a, pt0, t0, d->g_bn0_w, d->g_bn0_b);
     hipLaunchKernelGGL(k_acre_dcomb, dim3((unsigned)N), dim3(256), 0, st, a, e, r, dimg, t0, dent, drel);
     if (int rc = check_launch("k_acre_rowsum / k_acre_bn0_fin / k_acre_dcomb")) return rc;
-    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, e, N, kAcK, dent, d->g_ent);
-    hipLaunchKernelGGL(k_acre_scatter, dim3(row_blocks), dim3(256), 0, st, r, N, kAcK, drel, d->g_rel);
+    tail_scatter<AcTail>(e, N, kAcK, dent, kAcK, d->g_ent, st);   // (every id is scattered, id 0 included: no padding_idx)
+    tail_scatter<AcTail>(r, N, kAcK, drel, kAcK, d->g_rel, st);
     return check_launch("k_acre_scatter");
-}
-
-// the relation table has 2 tot_relation rows, every one an ordinary row
-static int ac_check_ids(const char* who, const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, hipStream_t s) {
-    return check_er_ids(who, d->tot_entity, 2 * d->tot_relation, e, r, n, s);
-}
-
-// fused step: ids [4B int64] | x [2B, K] | dx [2B, K] | saved | max(forward, backward, head)
-struct AcStepPlan {
-    size_t ids, x, dx, saved, rest, total;
-};
-static AcStepPlan ac_step_plan(const kge_acre_desc* d, int64_t B, int64_t n_hr, int64_t n_tr) {
-    AcStepPlan p{};
-    const size_t xb = align256((size_t)2 * B * kAcK * sizeof(float));
-    p.ids = 0;
-    p.x = align256((size_t)4 * B * sizeof(int64_t));
-    p.dx = p.x + xb;
-    p.saved = p.dx + xb;
-    p.rest = p.saved + align256(ac_saved_floats(d, B, 2) * sizeof(float));
-    size_t rest = ac_fwd_bytes(d, B, 2);
-    if (ac_bwd_bytes(d, B, 2) > rest) rest = ac_bwd_bytes(d, B, 2);
-    const size_t h1 = kge_head_1n_bce_workspace_bytes(B, d->tot_entity, n_hr), h2 = kge_head_1n_bce_workspace_bytes(B, d->tot_entity, n_tr);
-    if (h1 > rest) rest = h1;
-    if (h2 > rest) rest = h2;
-    p.total = p.rest + align256(rest);
-    return p;
-}
-
-// the rank pass's body (kge_projection.hip): the eval form on the rows [h; t] as two directions; ws = saved | the forward's workspace
-static int ac_eval_body(const void* desc, const int64_t* e, const int64_t* r, int64_t n, float* x, void* ws, size_t, hipStream_t s) {
-    kge_acre_desc ev = *(const kge_acre_desc*)desc;
-    ev.train = 0;
-    const size_t saved = align256(ac_saved_floats(&ev, n, 2) * sizeof(float));
-    return ac_forward(&ev, e, r, n, 2, 0, x, (float*)ws, (char*)ws + saved, s);
-}
-static ProjectionEval ac_eval(const kge_acre_desc* d, int64_t n) {
-    const int64_t rows = n > 0 ? n : 1;
-    return ProjectionEval{kAcK, d->tot_entity, d->tot_relation, d->ent,
-                          align256(ac_saved_floats(d, rows, 2) * sizeof(float)) + ac_fwd_bytes(d, rows, 2), ac_eval_body, d->bias};
 }
 
 }  // namespace kge
@@ -1459,106 +1031,47 @@ using namespace kge;
 extern "C" {
 
 size_t kge_acre_saved_floats(const kge_acre_desc* d, int64_t n) {
-    return ac_check(d, "kge_acre_saved_floats", false) || n < 0 ? 0 : ac_saved_floats(d, n > 0 ? n : 1, 1);
+    return tail_bytes<AcTail, AcTail::saved_floats>("kge_acre_saved_floats", d, n);
 }
 
 size_t kge_acre_body_forward_workspace_bytes(const kge_acre_desc* d, int64_t n) {
-    return ac_check(d, "kge_acre_body_forward_workspace_bytes", false) || n < 0 ? 0 : ac_fwd_bytes(d, n > 0 ? n : 1, 1);
+    return tail_bytes<AcTail, AcTail::fwd_bytes>("kge_acre_body_forward_workspace_bytes", d, n);
 }
 
 int kge_acre_body_forward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, float* x, float* saved,
                           void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "kge_acre_body_forward";
-    if (ac_check(d, who, false)) return -1;
-    if (n < 0 || (n > 0 && (!e || !r || !x || !saved)) || row0 < 0 || row0 + n > 0xffffffffLL) {
-        set_error("%s: bad arguments (row0 + n below 2^32)", who);
-        return -1;
-    }
-    if (ac_check_rows(d, who, n)) return -1;
-    if (ws_check(who, workspace, workspace_bytes, ac_fwd_bytes(d, n > 0 ? n : 1, 1))) return -1;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ac_check_ids(who, d, e, r, n, s)) return rc;
-    return ac_forward(d, e, r, n, 1, row0, x, saved, workspace, s);
+    return tail_body_forward<AcTail>("kge_acre_body_forward", d, e, r, n, 0, row0, x, saved, workspace, workspace_bytes, stream);
 }
 
 size_t kge_acre_body_backward_workspace_bytes(const kge_acre_desc* d, int64_t n) {
-    return ac_check(d, "kge_acre_body_backward_workspace_bytes", false) || n < 0 ? 0 : ac_bwd_bytes(d, n > 0 ? n : 1, 1);
+    return tail_bytes<AcTail, AcTail::bwd_bytes>("kge_acre_body_backward_workspace_bytes", d, n);
 }
 
 int kge_acre_body_backward(const kge_acre_desc* d, const int64_t* e, const int64_t* r, int64_t n, int64_t row0, const float* dx,
                            const float* saved, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "kge_acre_body_backward";
-    if (ac_check(d, who, true)) return -1;
-    if (n < 0 || (n > 0 && (!e || !r || !dx || !saved)) || row0 < 0 || row0 + n > 0xffffffffLL) {
-        set_error("%s: bad arguments (row0 + n below 2^32)", who);
-        return -1;
-    }
-    if (!d->train) { set_error("%s: the eval form (train = 0) has no backward", who); return -1; }
-    if (ac_check_rows(d, who, n)) return -1;
-    if (ws_check(who, workspace, workspace_bytes, ac_bwd_bytes(d, n > 0 ? n : 1, 1))) return -1;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ac_check_ids(who, d, e, r, n, s)) return rc;
-    return ac_backward(d, e, r, n, 1, row0, dx, saved, workspace, s);
+    return tail_body_backward<AcTail>("kge_acre_body_backward", d, e, r, n, 0, row0, dx, saved, workspace, workspace_bytes, stream);
 }
 
 size_t kge_acre_train_bce_workspace_bytes(const kge_acre_desc* d, int64_t batch, int64_t n_hr, int64_t n_tr) {
-    if (ac_check(d, "kge_acre_train_bce_workspace_bytes", false) || batch < 0 || n_hr < 0 || n_tr < 0) return 0;
-    return ac_step_plan(d, batch > 0 ? batch : 1, n_hr, n_tr).total;
+    return tail_train_bce_bytes<AcTail>("kge_acre_train_bce_workspace_bytes", d, batch, n_hr, n_tr);
 }
 
 int kge_acre_train_bce(const kge_acre_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t batch, const int64_t* hr_off,
                        const int32_t* hr_ids, int64_t n_hr, const int64_t* tr_off, const int32_t* tr_ids, int64_t n_tr, float label_smoothing,
                        void* workspace, size_t workspace_bytes, float* loss, void* stream) {
-    const char* who = "kge_acre_train_bce";
-    if (ac_check(d, who, true)) return -1;
-    if (batch < 0 || n_hr < 0 || n_tr < 0 || !loss || (batch > 0 && (!h || !r || !t || !hr_off || !tr_off)) || (n_hr > 0 && !hr_ids) ||
-        (n_tr > 0 && !tr_ids) || 2 * batch > 0xffffffffLL) {
-        set_error("%s: bad arguments", who);
-        return -1;
-    }
-    if (!d->train) { set_error("%s: the step is the training form (train = 0 has no backward)", who); return -1; }
-    if (ac_check_rows(d, who, batch)) return -1;
-    const AcStepPlan p = ac_step_plan(d, batch > 0 ? batch : 1, n_hr, n_tr);
-    if (ws_check(who, workspace, workspace_bytes, p.total)) return -1;
-    if (batch == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t B = batch, n = 2 * B;
-    const int k = kAcK;
-    char* ws = (char*)workspace;
-    int64_t* e = (int64_t*)(ws + p.ids);
-    int64_t* rr = e + n;
-    float *x = (float*)(ws + p.x), *dx = (float*)(ws + p.dx), *saved = (float*)(ws + p.saved);
-    void* rest = ws + p.rest;
-    const size_t rest_bytes = p.total - p.rest;
-    const size_t idb = (size_t)B * sizeof(int64_t);
-    if (hipMemcpyAsync(e, h, idb, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemcpyAsync(e + B, t, idb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(rr, r, idb, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemcpyAsync(rr + B, r, idb, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-        set_error("%s: copying the row ids failed: %s", who, hipGetErrorString(hipGetLastError()));
-        return -2;
-    }
-    if (int rc = ac_check_ids(who, d, e, rr, n, s)) return rc;
-    // tail direction = forward(h, r, "tail") on rows 0 .. B-1, head direction = forward(t, r, "head") on rows B .. 2B-1, in the same launches
-    if (int rc = ac_forward(d, e, rr, B, 2, 0, x, saved, rest, s)) return rc;
-    if (int rc = kge_head_1n_bce(x, B, k, d->ent, d->tot_entity, d->bias, hr_off, hr_ids, n_hr, label_smoothing, rest, rest_bytes, loss, dx, d->g_ent,
-                                 d->g_bias, stream)) return rc;
-    if (int rc = kge_head_1n_bce(x + B * k, B, k, d->ent, d->tot_entity, d->bias, tr_off, tr_ids, n_tr, label_smoothing, rest, rest_bytes, loss,
-                                 dx + B * k, d->g_ent, d->g_bias, stream)) return rc;
-    return ac_backward(d, e, rr, B, 2, 0, dx, saved, rest, s);
+    return tail_train_bce<AcTail>("kge_acre_train_bce", d, h, r, t, batch, hr_off, hr_ids, n_hr, tr_off, tr_ids, n_tr, label_smoothing, workspace,
+                                  workspace_bytes, loss, stream);
 }
 
 size_t kge_acre_eval_ranks_workspace_bytes(const kge_acre_desc* d, int64_t n) {
-    return ac_check(d, "kge_acre_eval_ranks_workspace_bytes", false) || n < 0 ? 0 : projection_eval_workspace_bytes(ac_eval(d, n), n);
+    return tail_eval_ranks_bytes<AcTail>("kge_acre_eval_ranks_workspace_bytes", d, n);
 }
 
 int kge_acre_eval_ranks(const kge_acre_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
                         const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks, int32_t* ties,
                         void* stream) {
-    const char* who = "kge_acre_eval_ranks";
-    if (ac_check(d, who, false)) return -1;
-    return projection_eval_ranks(who, ac_eval(d, n), d, triples, n, tail_off, tail_ids, head_off, head_ids, workspace, workspace_bytes, ranks,
-                                 ties, stream);
+    return tail_eval_ranks<AcTail>("kge_acre_eval_ranks", d, triples, n, tail_off, tail_ids, head_off, head_ids, workspace, workspace_bytes, ranks,
+                                   ties, stream);
 }
 
 }  // extern "C"
