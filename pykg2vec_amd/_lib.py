@@ -166,17 +166,22 @@ CONVE_BUFFERS = ("bn0_mean", "bn0_var", "bn1_mean", "bn1_var", "bn2_mean", "bn2_
 CONVE_MAX_HIDDEN = 1024
 
 
+def _conv_1n_fields(geometry, tables, pad=False, index_tables=()):
+    """The _fields_ of a conv 1-N descriptor (ConvE, HypER, InteractE, AcrE): the model's geometry, then the part the four structs
+    share -- three dropout rates, train (and a reserved int32 where the geometry leaves seed misaligned), seed, offset, eps[3],
+    momentum[3] -- then the index tables (InteractE's permutations), the tables, the six running buffers and the tables' gradients."""
+    return [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64)] + [(n, ctypes.c_int32) for n in geometry] \
+        + [(n, ctypes.c_float) for n in ("input_dropout", "feature_map_dropout", "hidden_dropout")] \
+        + [("train", ctypes.c_int32)] + ([("reserved", ctypes.c_int32)] if pad else []) \
+        + [("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
+        + [(n, ctypes.c_void_p) for n in tuple(index_tables) + tuple(tables) + CONVE_BUFFERS] \
+        + [("g_" + n, ctypes.c_void_p) for n in tables]
+
+
 class ConveDesc(ctypes.Structure):
     """struct kge_conve_desc"""
-    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("hidden_size", ctypes.c_int32),
-                ("hidden_size_1", ctypes.c_int32), ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float),
-                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
-                ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
-        + [(n, ctypes.c_void_p) for n in CONVE_TABLES] + [(n, ctypes.c_void_p) for n in CONVE_BUFFERS] \
-        + [("g_" + n, ctypes.c_void_p) for n in CONVE_TABLES]
+    _fields_ = _conv_1n_fields(("hidden_size", "hidden_size_1"), CONVE_TABLES)
 
-
-_CVD = ctypes.POINTER(ConveDesc)
 
 # HypER's 13 parameters in state-dict (= descriptor) order (the bare parameter b comes first), and its six running buffers
 HYPER_TABLES = ("b", "ent", "rel", "bn0_w", "bn0_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "fc_w", "fc_b", "fc1_w", "fc1_b")
@@ -186,15 +191,8 @@ HYPER_MAX_HIDDEN = 1024
 
 class HyperDesc(ctypes.Structure):
     """struct kge_hyper_desc"""
-    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("ent_hidden_size", ctypes.c_int32),
-                ("rel_hidden_size", ctypes.c_int32), ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float),
-                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
-                ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
-        + [(n, ctypes.c_void_p) for n in HYPER_TABLES] + [(n, ctypes.c_void_p) for n in HYPER_BUFFERS] \
-        + [("g_" + n, ctypes.c_void_p) for n in HYPER_TABLES]
+    _fields_ = _conv_1n_fields(("ent_hidden_size", "rel_hidden_size"), HYPER_TABLES)
 
-
-_HYD = ctypes.POINTER(HyperDesc)
 
 # InteractE's 12 parameters in state-dict (= descriptor) order (the bare parameters bias and conv_filt come first), and its six buffers
 INTERACTE_TABLES = ("bias", "conv_filt", "ent", "rel", "bn0_w", "bn0_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "fc_w", "fc_b")
@@ -206,17 +204,9 @@ INTERACTE_MAX_FLAT = 1 << 22
 
 class InteracteDesc(ctypes.Structure):
     """struct kge_interacte_desc"""
-    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("reshape_height", ctypes.c_int32),
-                ("reshape_width", ctypes.c_int32), ("feature_permutation", ctypes.c_int32), ("num_filters", ctypes.c_int32),
-                ("kernel_size", ctypes.c_int32), ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float),
-                ("hidden_dropout", ctypes.c_float), ("train", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64),
-                ("offset", ctypes.c_uint64), ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3),
-                ("perm", ctypes.c_void_p), ("inv_perm", ctypes.c_void_p)] \
-        + [(n, ctypes.c_void_p) for n in INTERACTE_TABLES] + [(n, ctypes.c_void_p) for n in INTERACTE_BUFFERS] \
-        + [("g_" + n, ctypes.c_void_p) for n in INTERACTE_TABLES]
+    _fields_ = _conv_1n_fields(("reshape_height", "reshape_width", "feature_permutation", "num_filters", "kernel_size"), INTERACTE_TABLES,
+                               pad=True, index_tables=("perm", "inv_perm"))
 
-
-_ITD = ctypes.POINTER(InteracteDesc)
 
 # AcrE's parameters in state-dict (= descriptor) order (the bare parameter bias comes first): 17 in the serial way, 19 in the parallel
 # (the gate); the descriptor has all 19 slots, the conv biases NULL without acre_bias and the gate NULL in the serial way
@@ -230,75 +220,33 @@ ACRE_MAX_ATROUS = 4
 
 class AcreDesc(ctypes.Structure):
     """struct kge_acre_desc"""
-    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("hidden_size", ctypes.c_int32),
-                ("in_channels", ctypes.c_int32), ("way", ctypes.c_int32), ("first_atrous", ctypes.c_int32),
-                ("second_atrous", ctypes.c_int32), ("third_atrous", ctypes.c_int32), ("acre_bias", ctypes.c_int32),
-                ("input_dropout", ctypes.c_float), ("feature_map_dropout", ctypes.c_float), ("hidden_dropout", ctypes.c_float),
-                ("train", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
-                ("eps", ctypes.c_float * 3), ("momentum", ctypes.c_float * 3)] \
-        + [(n, ctypes.c_void_p) for n in ACRE_TABLES_PARALLEL] + [(n, ctypes.c_void_p) for n in ACRE_BUFFERS] \
-        + [("g_" + n, ctypes.c_void_p) for n in ACRE_TABLES_PARALLEL]
+    _fields_ = _conv_1n_fields(("hidden_size", "in_channels", "way", "first_atrous", "second_atrous", "third_atrous", "acre_bias"),
+                               ACRE_TABLES_PARALLEL, pad=True)
 
 
-_ACD = ctypes.POINTER(AcreDesc)
+_P, _I64 = ctypes.c_void_p, ctypes.c_int64
+
+
+def _conv_1n_signatures(stem, desc, has_side=False):
+    """The nine entry points of a 1-N model with its own descriptor (include/kge_hip.h: kge_<stem>_*).  has_side: ConvE's int32 side
+    in front of row0 in the two body calls."""
+    d = ctypes.POINTER(desc)
+    body = (ctypes.c_int, [d, _P, _P, _I64] + [ctypes.c_int32] * has_side + [_I64, _P, _P, _P, ctypes.c_size_t, _P])
+    sigs = {"saved_floats": (ctypes.c_size_t, [d, _I64]),
+            "body_forward": body,
+            "body_backward": body,
+            "train_bce": (ctypes.c_int, [d, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, ctypes.c_float, _P, ctypes.c_size_t, _P, _P]),
+            "eval_ranks": (ctypes.c_int, [d, _P, _I64] + [_P] * 4 + [_P, ctypes.c_size_t, _P, _P, _P])}
+    sizes = {"body_forward": 1, "body_backward": 1, "train_bce": 3, "eval_ranks": 1}     # the int64 arguments of *_workspace_bytes
+    sigs.update({e + "_workspace_bytes": (ctypes.c_size_t, [d] + [_I64] * k) for e, k in sizes.items()})
+    return {"kge_%s_%s" % (stem, e): sig for e, sig in sigs.items()}
+
 
 _SIGNATURES = {
-    "kge_interacte_saved_floats": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
-    "kge_interacte_body_forward_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
-    "kge_interacte_body_forward": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_interacte_body_backward_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
-    "kge_interacte_body_backward": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_interacte_train_bce_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "kge_interacte_train_bce": (ctypes.c_int, [_ITD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
-                                                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_interacte_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_ITD, ctypes.c_int64]),
-    "kge_interacte_eval_ranks": (ctypes.c_int, [_ITD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
-                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_acre_saved_floats": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
-    "kge_acre_body_forward_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
-    "kge_acre_body_forward": (ctypes.c_int, [_ACD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_acre_body_backward_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
-    "kge_acre_body_backward": (ctypes.c_int, [_ACD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_acre_train_bce_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "kge_acre_train_bce": (ctypes.c_int, [_ACD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
-                                                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_acre_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_ACD, ctypes.c_int64]),
-    "kge_acre_eval_ranks": (ctypes.c_int, [_ACD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
-                            + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_hyper_saved_floats": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
-    "kge_hyper_body_forward_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
-    "kge_hyper_body_forward": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_hyper_body_backward_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
-    "kge_hyper_body_backward": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_hyper_train_bce_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "kge_hyper_train_bce": (ctypes.c_int, [_HYD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
-                                                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_hyper_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_HYD, ctypes.c_int64]),
-    "kge_hyper_eval_ranks": (ctypes.c_int, [_HYD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
-                             + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_conve_saved_floats": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
-    "kge_conve_body_forward_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
-    "kge_conve_body_forward": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_conve_body_backward_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
-    "kge_conve_body_backward": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "kge_conve_train_bce_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "kge_conve_train_bce": (ctypes.c_int, [_CVD] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
-                                                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "kge_conve_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_CVD, ctypes.c_int64]),
-    "kge_conve_eval_ranks": (ctypes.c_int, [_CVD, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
-                             + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    **_conv_1n_signatures("interacte", InteracteDesc),
+    **_conv_1n_signatures("acre", AcreDesc),
+    **_conv_1n_signatures("hyper", HyperDesc),
+    **_conv_1n_signatures("conve", ConveDesc, has_side=True),
     "kge_proje_body_forward_workspace_bytes": (ctypes.c_size_t, [_PJD, ctypes.c_int64]),
     "kge_proje_body_forward": (ctypes.c_int, [_PJD, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

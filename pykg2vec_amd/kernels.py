@@ -1471,6 +1471,80 @@ def _projection_eval_ranks(symbol, desc, triples, tail_off, tail_ids, head_off, 
     return ranks
 
 
+def _train_bce(stem, desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
+    """kge_<stem>_train_bce: the fused BCE step of a 1-N model with its own descriptor (TuckER and the conv 1-N models)."""
+    symbol = "kge_%s_train_bce" % stem
+    B, n_hr, n_tr, args = _label_csr_args(stem + "_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
+    wp, wb = _desc_ws(desc, symbol + "_workspace_bytes", B, n_hr, n_tr)
+    L.check(getattr(L.load(), symbol)(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
+                                      _dev(loss_buf, torch.float32, "loss"), _stream()), symbol)
+
+
+# ---------------------------------------------------------------- shared by the conv 1-N models (ConvE, HypER, InteractE, AcrE)
+def _conv_1n_desc(d, stem, names, tables, buffers, grads, want, skip, dropouts, eps, momentum, train, seed, offset, count_note="",
+                  index_tables=None):
+    """Fills `d`, a fresh descriptor of a conv 1-N model, with everything but its geometry, and returns it.  names: the descriptor
+    fields of `tables`, in order; want: (the shapes of the tables, those of the six buffers) wherever the geometry is one the library
+    accepts, else None (no shape is looked at); skip: the slots of the entity and the relation table, which may have more rows than ids;
+    index_tables: a callable answering the model's int32 index tables as (field, tensor, shape) triples, called once the counts are
+    known to be good.  Refusals in the order the builders always had: the counts, momentum None, the index tables' own, the embedding
+    tables, the other shapes, the device and dtype of each tensor bound, the gradient count, the gradient shapes."""
+    if len(tables) != len(names) or len(buffers) != 6:
+        raise L.KgeHipError("%s: %d tensors and 6 running buffers expected%s, got %d and %d"
+                            % (stem, len(names), count_note, len(tables), len(buffers)))
+    if any(m is None for m in momentum):
+        raise L.KgeHipError("%s: momentum None (the cumulative moving average) is not built" % stem)
+    index = index_tables() if index_tables is not None else ()
+    fields, tensors = tuple(names) + L.CONVE_BUFFERS, list(tables) + list(buffers)
+    if want is not None:
+        i_ent, i_rel = skip
+        _check_embeddings(stem, ("ent_embeddings", tables[i_ent]) + want[0][i_ent], ("rel_embeddings", tables[i_rel]) + want[0][i_rel])
+        for i, (name, t, shape) in enumerate(zip(fields, tensors, want[0] + want[1])):
+            if i not in skip and tuple(t.shape) != shape:
+                raise L.KgeHipError("%s: %s must be %s (got %s)" % (stem, name, shape, tuple(t.shape)))
+        for name, t, shape in index:
+            if tuple(t.shape) != shape:
+                raise L.KgeHipError("%s: %s must be %s (got %s)" % (stem, name, shape, tuple(t.shape)))
+    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
+    _set_rng(d, train, seed, offset)
+    for i in range(3):
+        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
+    for name, t, _ in index:
+        setattr(d, name, _dev(t, torch.int32, name).value)
+    for name, t in zip(fields, tensors):
+        setattr(d, name, _dev(t, torch.float32, name).value)
+    if grads is not None:
+        if len(grads) != len(names):
+            raise L.KgeHipError("%s: %d gradient tensors expected, got %d" % (stem, len(names), len(grads)))
+        _bind_grads(d, ["g_" + n for n in names], ["grad of " + n for n in names], grads, tables)
+    d._keepalive = (tables, buffers, grads) + ((index,) if index else ())
+    d._ws = None
+    return d
+
+
+def _body_forward(stem, desc, e, r, width, side, row0):
+    """kge_<stem>_body_forward -> (x float32 [n, width], saved); side: ConvE's, None for the models with one relation table."""
+    n = e.numel()
+    if r.numel() != n:
+        raise ValueError("e, r must have equal lengths")
+    lib, symbol = L.load(), "kge_%s_body_forward" % stem
+    x = torch.empty((n, width), dtype=torch.float32, device=e.device)
+    wp, wb = _desc_ws(desc, symbol + "_workspace_bytes", n)
+    saved = torch.empty(max(1, int(getattr(lib, "kge_%s_saved_floats" % stem)(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
+    L.check(getattr(lib, symbol)(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, *(() if side is None else (int(side),)), int(row0),
+                                 _dev(x, torch.float32, "x"), _dev(saved, torch.float32, "saved"), wp, wb, _stream()), symbol)
+    return x, saved
+
+
+def _body_backward(stem, desc, e, r, dx, saved, side, row0):
+    """kge_<stem>_body_backward; side as in _body_forward."""
+    n = e.numel()
+    symbol = "kge_%s_body_backward" % stem
+    wp, wb = _desc_ws(desc, symbol + "_workspace_bytes", n)
+    L.check(getattr(L.load(), symbol)(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, *(() if side is None else (int(side),)), int(row0),
+                                      _dev(dx, torch.float32, "dx"), _dev(saved, torch.float32, "saved"), wp, wb, _stream()), symbol)
+
+
 # ---------------------------------------------------------------- ConvKB (csrc/kge_convkb.hip): its own descriptor and entry points
 def _convkb_no_reg(lmbda, reg_type):
     if float(lmbda) != 0.0 and int(reg_type) != L.REG_NONE:
@@ -1627,10 +1701,7 @@ def tucker_body_backward(desc, e, r, dx, saved):
 def tucker_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
     """One train_step_projection: adds to loss_buf and to the descriptor's gradients.  hr_* / tr_*: the label CSRs of the batch
     (off int64 [B + 1], ids int32); label_smoothing None = off."""
-    B, n_hr, n_tr, args = _label_csr_args("tucker_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
-    wp, wb = _desc_ws(desc, "kge_tucker_train_bce_workspace_bytes", B, n_hr, n_tr)
-    L.check(L.load().kge_tucker_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
-                                          _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_tucker_train_bce")
+    _train_bce("tucker", desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf)
 
 
 def tucker_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
@@ -1741,64 +1812,28 @@ def conve_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, hidden_
     by id and by shape without a bounds test) whenever the geometry is one the library accepts; the geometry, the rates, the momenta and
     the offset are checked by the library, which refuses bad ones loudly."""
     E, R, k, h1 = int(tot_entity), int(tot_relation), int(hidden_size), int(hidden_size_1)
-    if len(tables) != 13 or len(buffers) != 6:
-        raise L.KgeHipError("conve: 13 tensors and 6 running buffers expected, got %d and %d" % (len(tables), len(buffers)))
-    if any(m is None for m in momentum):
-        raise L.KgeHipError("conve: momentum None (the cumulative moving average) is not built")
-    if h1 >= 3 and k % h1 == 0 and 2 * (k // h1) >= 3:
-        _check_embeddings("conve", ("ent_embeddings", tables[0], E, k), ("rel_embeddings", tables[1], 2 * R, k))
-        want_t, want_b = conve_shapes(E, R, k, h1)
-        for name, t, shape in zip(L.CONVE_TABLES[2:] + L.CONVE_BUFFERS, list(tables[2:]) + list(buffers), want_t[2:] + want_b):
-            if tuple(t.shape) != shape:
-                raise L.KgeHipError("conve: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
-    d = L.ConveDesc()
+    want = conve_shapes(E, R, k, h1) if h1 >= 3 and k % h1 == 0 and 2 * (k // h1) >= 3 else None
+    d = _conv_1n_desc(L.ConveDesc(), "conve", L.CONVE_TABLES, tables, buffers, grads, want, (0, 1), dropouts, eps, momentum, train, seed,
+                      offset)
     d.tot_entity, d.tot_relation, d.hidden_size, d.hidden_size_1 = E, R, k, h1
-    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
-    _set_rng(d, train, seed, offset)
-    for i in range(3):
-        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
-    for name, t in zip(L.CONVE_TABLES + L.CONVE_BUFFERS, list(tables) + list(buffers)):
-        setattr(d, name, _dev(t, torch.float32, name).value)
-    if grads is not None:
-        if len(grads) != 13:
-            raise L.KgeHipError("conve: 13 gradient tensors expected, got %d" % len(grads))
-        _bind_grads(d, ["g_" + n for n in L.CONVE_TABLES], ["grad of " + n for n in L.CONVE_TABLES], grads, tables)
-    d._keepalive = (tables, buffers, grads)
-    d._ws = None
     return d
 
 
 def conve_body_forward(desc, e, r, side, row0=0):
     """(x float32 [n, k], saved): the body of ConvE.forward on the rows (e_i, r_i) of one direction (side 0 = tail, 1 = head); the
     training form updates the descriptor's running buffers once.  `saved` is what conve_body_backward reads."""
-    n = e.numel()
-    if r.numel() != n:
-        raise ValueError("e, r must have equal lengths")
-    lib = L.load()
-    x = torch.empty((n, desc.hidden_size), dtype=torch.float32, device=e.device)
-    wp, wb = _desc_ws(desc, "kge_conve_body_forward_workspace_bytes", n)
-    saved = torch.empty(max(1, int(lib.kge_conve_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
-    L.check(lib.kge_conve_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(side), int(row0), _dev(x, torch.float32, "x"),
-                                       _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_conve_body_forward")
-    return x, saved
+    return _body_forward("conve", desc, e, r, desc.hidden_size, side, row0)
 
 
 def conve_body_backward(desc, e, r, side, dx, saved, row0=0):
     """g_* of the descriptor += the body's gradients given d loss / d x (same rows, side, row0, seed, offset and `saved` as the forward)."""
-    n = e.numel()
-    wp, wb = _desc_ws(desc, "kge_conve_body_backward_workspace_bytes", n)
-    L.check(L.load().kge_conve_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(side), int(row0),
-                                             _dev(dx, torch.float32, "dx"), _dev(saved, torch.float32, "saved"), wp, wb, _stream()),
-            "kge_conve_body_backward")
+    _body_backward("conve", desc, e, r, dx, saved, side, row0)
 
 
 def conve_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
     """One train_step_projection of ConvE: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice (tail
     direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
-    B, n_hr, n_tr, args = _label_csr_args("conve_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
-    wp, wb = _desc_ws(desc, "kge_conve_train_bce_workspace_bytes", B, n_hr, n_tr)
-    L.check(L.load().kge_conve_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
-                                         _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_conve_train_bce")
+    _train_bce("conve", desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf)
 
 
 def conve_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
@@ -1822,63 +1857,28 @@ def hyper_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, ent_hid
     by shape without a bounds test) whenever the geometry is one the library accepts; the geometry, the rates, the momenta and the
     offset are checked by the library, which refuses bad ones loudly."""
     E, R, D, Dr = int(tot_entity), int(tot_relation), int(ent_hidden_size), int(rel_hidden_size)
-    if len(tables) != 13 or len(buffers) != 6:
-        raise L.KgeHipError("hyper: 13 tensors and 6 running buffers expected, got %d and %d" % (len(tables), len(buffers)))
-    if any(m is None for m in momentum):
-        raise L.KgeHipError("hyper: momentum None (the cumulative moving average) is not built")
-    if D >= 9 and Dr >= 1:
-        _check_embeddings("hyper", ("ent_embeddings", tables[1], E, D), ("rel_embeddings", tables[2], R, Dr))
-        want_t, want_b = hyper_shapes(E, R, D, Dr)
-        for i, (name, t, shape) in enumerate(zip(L.HYPER_TABLES + L.HYPER_BUFFERS, list(tables) + list(buffers), want_t + want_b)):
-            if i not in (1, 2) and tuple(t.shape) != shape:
-                raise L.KgeHipError("hyper: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
-    d = L.HyperDesc()
+    want = hyper_shapes(E, R, D, Dr) if D >= 9 and Dr >= 1 else None
+    d = _conv_1n_desc(L.HyperDesc(), "hyper", L.HYPER_TABLES, tables, buffers, grads, want, (1, 2), dropouts, eps, momentum, train, seed,
+                      offset)
     d.tot_entity, d.tot_relation, d.ent_hidden_size, d.rel_hidden_size = E, R, D, Dr
-    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
-    _set_rng(d, train, seed, offset)
-    for i in range(3):
-        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
-    for name, t in zip(L.HYPER_TABLES + L.HYPER_BUFFERS, list(tables) + list(buffers)):
-        setattr(d, name, _dev(t, torch.float32, name).value)
-    if grads is not None:
-        if len(grads) != 13:
-            raise L.KgeHipError("hyper: 13 gradient tensors expected, got %d" % len(grads))
-        _bind_grads(d, ["g_" + n for n in L.HYPER_TABLES], ["grad of " + n for n in L.HYPER_TABLES], grads, tables)
-    d._keepalive = (tables, buffers, grads)
-    d._ws = None
     return d
 
 
 def hyper_body_forward(desc, e, r, row0=0):
     """(x float32 [n, D], saved): the body of HypER.forward on the rows (e_i, r_i) of one direction; the training form updates the
     descriptor's running buffers once.  `saved` is what hyper_body_backward reads."""
-    n = e.numel()
-    if r.numel() != n:
-        raise ValueError("e, r must have equal lengths")
-    lib = L.load()
-    x = torch.empty((n, desc.ent_hidden_size), dtype=torch.float32, device=e.device)
-    wp, wb = _desc_ws(desc, "kge_hyper_body_forward_workspace_bytes", n)
-    saved = torch.empty(max(1, int(lib.kge_hyper_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
-    L.check(lib.kge_hyper_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(x, torch.float32, "x"),
-                                       _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_hyper_body_forward")
-    return x, saved
+    return _body_forward("hyper", desc, e, r, desc.ent_hidden_size, None, row0)
 
 
 def hyper_body_backward(desc, e, r, dx, saved, row0=0):
     """g_* of the descriptor += the body's gradients given d loss / d x (same rows, row0, seed, offset and `saved` as the forward)."""
-    n = e.numel()
-    wp, wb = _desc_ws(desc, "kge_hyper_body_backward_workspace_bytes", n)
-    L.check(L.load().kge_hyper_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(dx, torch.float32, "dx"),
-                                             _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_hyper_body_backward")
+    _body_backward("hyper", desc, e, r, dx, saved, None, row0)
 
 
 def hyper_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
     """One train_step_projection of HypER: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice (tail
     direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
-    B, n_hr, n_tr, args = _label_csr_args("hyper_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
-    wp, wb = _desc_ws(desc, "kge_hyper_train_bce_workspace_bytes", B, n_hr, n_tr)
-    L.check(L.load().kge_hyper_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
-                                         _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_hyper_train_bce")
+    _train_bce("hyper", desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf)
 
 
 def hyper_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
@@ -1926,72 +1926,36 @@ def interacte_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, res
     E, R, rh, rw = int(tot_entity), int(tot_relation), int(reshape_height), int(reshape_width)
     P, NF, ks = int(feature_permutation), int(num_filters), int(kernel_size)
     k = rh * rw
-    if len(tables) != 12 or len(buffers) != 6:
-        raise L.KgeHipError("interacte: 12 tensors and 6 running buffers expected, got %d and %d" % (len(tables), len(buffers)))
-    if any(m is None for m in momentum):
-        raise L.KgeHipError("interacte: momentum None (the cumulative moving average) is not built")
-    if perms is None:
-        if chequer_perm is None:
+
+    def index_tables():     # (once the counts are good: tables[2] says where the weights live)
+        if perms is None and chequer_perm is None:
             raise L.KgeHipError("interacte: chequer_perm (or the pair interacte_perm made of it) is required")
-        perms = interacte_perm(chequer_perm, P, k, tables[2].device)
-    if min(rh, rw, P, NF) >= 1 and ks >= 3 and ks % 2 == 1:
-        _check_embeddings("interacte", ("ent_embeddings", tables[2], E, k), ("rel_embeddings", tables[3], R, k))
-        want_t, want_b = interacte_shapes(E, R, rh, rw, P, NF, ks)
-        for i, (name, t, shape) in enumerate(zip(L.INTERACTE_TABLES + L.INTERACTE_BUFFERS, list(tables) + list(buffers), want_t + want_b)):
-            if i not in (2, 3) and tuple(t.shape) != shape:
-                raise L.KgeHipError("interacte: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
-        for name, t in zip(("perm", "inv_perm"), perms):
-            if tuple(t.shape) != (P, 2 * k):
-                raise L.KgeHipError("interacte: %s must be %s (got %s)" % (name, (P, 2 * k), tuple(t.shape)))
-    d = L.InteracteDesc()
+        pair = perms if perms is not None else interacte_perm(chequer_perm, P, k, tables[2].device)
+        return [(name, t, (P, 2 * k)) for name, t in zip(("perm", "inv_perm"), pair)]
+
+    want = interacte_shapes(E, R, rh, rw, P, NF, ks) if min(rh, rw, P, NF) >= 1 and ks >= 3 and ks % 2 == 1 else None
+    d = _conv_1n_desc(L.InteracteDesc(), "interacte", L.INTERACTE_TABLES, tables, buffers, grads, want, (2, 3), dropouts, eps, momentum, train,
+                      seed, offset, index_tables=index_tables)
     d.tot_entity, d.tot_relation, d.reshape_height, d.reshape_width = E, R, rh, rw
     d.feature_permutation, d.num_filters, d.kernel_size = P, NF, ks
-    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
-    _set_rng(d, train, seed, offset)
-    for i in range(3):
-        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
-    d.perm, d.inv_perm = (_dev(t, torch.int32, name).value for name, t in zip(("perm", "inv_perm"), perms))
-    for name, t in zip(L.INTERACTE_TABLES + L.INTERACTE_BUFFERS, list(tables) + list(buffers)):
-        setattr(d, name, _dev(t, torch.float32, name).value)
-    if grads is not None:
-        if len(grads) != 12:
-            raise L.KgeHipError("interacte: 12 gradient tensors expected, got %d" % len(grads))
-        _bind_grads(d, ["g_" + n for n in L.INTERACTE_TABLES], ["grad of " + n for n in L.INTERACTE_TABLES], grads, tables)
-    d._keepalive = (tables, buffers, grads, perms)
-    d._ws = None
     return d
 
 
 def interacte_body_forward(desc, e, r, row0=0):
     """(x float32 [n, K], saved): the body of InteractE.forward on the rows (e_i, r_i) of one direction; the training form updates the
     descriptor's running buffers once.  `saved` is what interacte_body_backward reads."""
-    n = e.numel()
-    if r.numel() != n:
-        raise ValueError("e, r must have equal lengths")
-    lib = L.load()
-    x = torch.empty((n, desc.reshape_height * desc.reshape_width), dtype=torch.float32, device=e.device)
-    wp, wb = _desc_ws(desc, "kge_interacte_body_forward_workspace_bytes", n)
-    saved = torch.empty(max(1, int(lib.kge_interacte_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
-    L.check(lib.kge_interacte_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(x, torch.float32, "x"),
-                                           _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_interacte_body_forward")
-    return x, saved
+    return _body_forward("interacte", desc, e, r, desc.reshape_height * desc.reshape_width, None, row0)
 
 
 def interacte_body_backward(desc, e, r, dx, saved, row0=0):
     """g_* of the descriptor += the body's gradients given d loss / d x (same rows, row0, seed, offset and `saved` as the forward)."""
-    n = e.numel()
-    wp, wb = _desc_ws(desc, "kge_interacte_body_backward_workspace_bytes", n)
-    L.check(L.load().kge_interacte_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(dx, torch.float32, "dx"),
-                                                 _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_interacte_body_backward")
+    _body_backward("interacte", desc, e, r, dx, saved, None, row0)
 
 
 def interacte_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
     """One train_step_projection of InteractE: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice
     (tail direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
-    B, n_hr, n_tr, args = _label_csr_args("interacte_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
-    wp, wb = _desc_ws(desc, "kge_interacte_train_bce_workspace_bytes", B, n_hr, n_tr)
-    L.check(L.load().kge_interacte_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
-                                             _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_interacte_train_bce")
+    _train_bce("interacte", desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf)
 
 
 def interacte_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
@@ -2037,64 +2001,29 @@ def acre_desc(tables, buffers, grads=None, *, tot_entity, tot_relation, hidden_s
     if not isinstance(w, int):
         raise L.KgeHipError("acre: way must be 'serial' or 'parallel' (got %r)" % (way,))
     names, shapes, want_b = acre_shapes(E, R, max(C, 1), w, bool(acre_bias))
-    if len(tables) != len(names) or len(buffers) != 6:
-        raise L.KgeHipError("acre: %d tensors and 6 running buffers expected (way %r, acre_bias %r), got %d and %d"
-                            % (len(names), way, bool(acre_bias), len(tables), len(buffers)))
-    if any(m is None for m in momentum):
-        raise L.KgeHipError("acre: momentum None (the cumulative moving average) is not built")
-    if k == 200 and 1 <= C <= L.ACRE_MAX_CHANNELS and w in (0, 1):
-        _check_embeddings("acre", ("ent_embeddings", tables[1], E, k), ("rel_embeddings", tables[2], 2 * R, k))
-        for i, (name, t, shape) in enumerate(zip(names + list(L.ACRE_BUFFERS), list(tables) + list(buffers), shapes + want_b)):
-            if i not in (1, 2) and tuple(t.shape) != shape:
-                raise L.KgeHipError("acre: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
-    d = L.AcreDesc()
+    want = (shapes, want_b) if k == 200 and 1 <= C <= L.ACRE_MAX_CHANNELS and w in (0, 1) else None
+    d = _conv_1n_desc(L.AcreDesc(), "acre", names, tables, buffers, grads, want, (1, 2), dropouts, eps, momentum, train, seed, offset,
+                      count_note=" (way %r, acre_bias %r)" % (way, bool(acre_bias)))
     d.tot_entity, d.tot_relation, d.hidden_size, d.in_channels, d.way = E, R, k, C, w
     d.first_atrous, d.second_atrous, d.third_atrous, d.acre_bias = int(first_atrous), int(second_atrous), int(third_atrous), int(bool(acre_bias))
-    d.input_dropout, d.feature_map_dropout, d.hidden_dropout = (float(p) for p in dropouts)
-    _set_rng(d, train, seed, offset)
-    for i in range(3):
-        d.eps[i], d.momentum[i] = float(eps[i]), float(momentum[i])
-    for name, t in zip(names + list(L.ACRE_BUFFERS), list(tables) + list(buffers)):
-        setattr(d, name, _dev(t, torch.float32, name).value)
-    if grads is not None:
-        if len(grads) != len(names):
-            raise L.KgeHipError("acre: %d gradient tensors expected, got %d" % (len(names), len(grads)))
-        _bind_grads(d, ["g_" + n for n in names], ["grad of " + n for n in names], grads, tables)
-    d._keepalive = (tables, buffers, grads)
-    d._ws = None
     return d
 
 
 def acre_body_forward(desc, e, r, row0=0):
     """(x float32 [n, 200], saved): the body of AcrE.forward on the rows (e_i, r_i) of one direction; the training form updates the
     descriptor's running buffers once.  `saved` is what acre_body_backward reads."""
-    n = e.numel()
-    if r.numel() != n:
-        raise ValueError("e, r must have equal lengths")
-    lib = L.load()
-    x = torch.empty((n, 200), dtype=torch.float32, device=e.device)
-    wp, wb = _desc_ws(desc, "kge_acre_body_forward_workspace_bytes", n)
-    saved = torch.empty(max(1, int(lib.kge_acre_saved_floats(ctypes.byref(desc), n))), dtype=torch.float32, device=e.device)
-    L.check(lib.kge_acre_body_forward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(x, torch.float32, "x"),
-                                      _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_acre_body_forward")
-    return x, saved
+    return _body_forward("acre", desc, e, r, 200, None, row0)
 
 
 def acre_body_backward(desc, e, r, dx, saved, row0=0):
     """g_* of the descriptor += the body's gradients given d loss / d x (same rows, row0, seed, offset and `saved` as the forward)."""
-    n = e.numel()
-    wp, wb = _desc_ws(desc, "kge_acre_body_backward_workspace_bytes", n)
-    L.check(L.load().kge_acre_body_backward(ctypes.byref(desc), _ids(e, "e"), _ids(r, "r"), n, int(row0), _dev(dx, torch.float32, "dx"),
-                                            _dev(saved, torch.float32, "saved"), wp, wb, _stream()), "kge_acre_body_backward")
+    _body_backward("acre", desc, e, r, dx, saved, None, row0)
 
 
 def acre_train_bce(desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf):
     """One train_step_projection of AcrE: adds to loss_buf and to the descriptor's gradients, updates the running buffers twice
     (tail direction, then head).  hr_* / tr_*: the label CSRs of the batch (off int64 [B + 1], ids int32); label_smoothing None = off."""
-    B, n_hr, n_tr, args = _label_csr_args("acre_train_bce", h, r, t, hr_off, hr_ids, tr_off, tr_ids)
-    wp, wb = _desc_ws(desc, "kge_acre_train_bce_workspace_bytes", B, n_hr, n_tr)
-    L.check(L.load().kge_acre_train_bce(ctypes.byref(desc), *args, -1.0 if label_smoothing is None else float(label_smoothing), wp, wb,
-                                        _dev(loss_buf, torch.float32, "loss"), _stream()), "kge_acre_train_bce")
+    _train_bce("acre", desc, h, r, t, hr_off, hr_ids, tr_off, tr_ids, label_smoothing, loss_buf)
 
 
 def acre_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):

@@ -235,215 +235,95 @@ def _proje_backward(ctx, dx):
 proje_body.register_autograd(_proje_backward, setup_context=_proje_setup)
 
 
-# ConvE's body (include/kge_hip.h: kge_conve_body_*).  side 0 = the tail direction, 1 = the head direction; offset < 0 = the eval form
-# (running statistics, no bn2, no draws).  The mask rows of a call start at side * n: the head direction's rows follow the tail
-# direction's, as in the fused step, so that the two forward calls of a training step under one (seed, offset) draw the step's masks.
-# The training form updates the model's running buffers (found through the model handle, not passed as tensors).  That write is not
-# in the op's schema (mutates_args is empty), so the op is for eager execution only: under torch.compile or functionalisation the
-# update is invisible, and a training-form call whose outputs are unused could be dropped together with it.
-@torch.library.custom_op("kge::conve_body", mutates_args=(), device_types="cuda")
-def conve_body(key: int, e: Tensor, r: Tensor, side: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
-    m = _model(key)
-    return K.conve_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                                r.contiguous(), side, row0=side * e.numel())
+# The bodies of the conv 1-N models (include/kge_hip.h: kge_<stem>_body_* for conve, hyper, interacte, acre), one registration for all.
+# offset < 0 = the eval form (running statistics, no draws).  The training form updates the model's running buffers (found through
+# the model handle, not passed as tensors).  That write is not in the op's schema (mutates_args is empty), so the ops are for eager
+# execution only: under torch.compile or functionalisation the update is invisible, and a training-form call whose outputs are
+# unused could be dropped together with it.
+def _register_conv_1n(stem, direction, ent_slot, saved_floats):
+    """Defines kge::<stem>_body and kge::<stem>_body_backward with their fake kernels, CPU refusal and autograd formula, and returns
+    the pair.  direction: the schema's name of the direction argument, "side" (ConvE: 0 / 1, which also picks the relation half; the
+    mask rows start at side * n) or "row0" (the mask row of the call's first row); ent_slot: where the entity table stands in
+    `weights`, its width is x's; saved_floats(n, weights): the size of `saved`, the library's kge_<stem>_saved_floats restated on
+    shapes for the fake kernel (tests/test_conv_1n_host.py holds the two together)."""
+    forward, backward = getattr(K, stem + "_body_forward"), getattr(K, stem + "_body_backward")
+
+    def rows(e, d):     # the direction as K.<stem>_body_* take it: ConvE's side in front, row0 by keyword
+        return ((d,), d * e.numel()) if direction == "side" else ((), d)
+
+    def desc(key, weights, grads, seed, offset):
+        return _model(key).make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0))
+
+    @torch.library.custom_op("kge::%s_body" % stem, mutates_args=(), device_types="cuda",
+                             schema="(SymInt key, Tensor e, Tensor r, SymInt %s, SymInt seed, SymInt offset, Tensor[] weights) -> (Tensor, Tensor)"
+                             % direction)
+    def body(key: int, e: Tensor, r: Tensor, d: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
+        lead, row0 = rows(e, d)
+        return forward(desc(key, weights, None, seed, offset), e.contiguous(), r.contiguous(), *lead, row0=row0)
+
+    @body.register_fake
+    def _(key, e, r, d, seed, offset, weights):
+        ent, n = weights[ent_slot], e.numel()
+        return ent.new_empty((n, ent.shape[1])), ent.new_empty((saved_floats(n, weights),))
+
+    @body.register_kernel("cpu")
+    def _(key, e, r, d, seed, offset, weights):
+        raise L.KgeHipError("kge::%s_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % (stem, e.device))
+
+    @torch.library.custom_op("kge::%s_body_backward" % stem, mutates_args=(), device_types="cuda",
+                             schema="(SymInt key, Tensor e, Tensor r, SymInt %s, SymInt seed, SymInt offset, Tensor dx, Tensor saved, "
+                                    "Tensor[] weights) -> Tensor[]" % direction)
+    def body_backward(key: int, e: Tensor, r: Tensor, d: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
+                      weights: List[Tensor]) -> List[Tensor]:
+        grads = [torch.zeros_like(w) for w in weights]
+        lead, row0 = rows(e, d)
+        backward(desc(key, weights, grads, seed, offset), e.contiguous(), r.contiguous(), *lead, dx.contiguous(), saved, row0=row0)
+        return grads
+
+    @body_backward.register_fake
+    def _(key, e, r, d, seed, offset, dx, saved, weights):
+        return [torch.empty_like(w) for w in weights]
+
+    def setup(ctx, inputs, output):
+        key, e, r, d, seed, offset, weights = inputs
+        ctx.key, ctx.direction, ctx.seed, ctx.offset = key, d, seed, offset
+        ctx.save_for_backward(e, r, output[1], *weights)
+        ctx.mark_non_differentiable(output[1])
+
+    def autograd(ctx, dx, _dsaved):
+        e, r, saved, *weights = ctx.saved_tensors
+        return None, None, None, None, None, None, body_backward(ctx.key, e, r, ctx.direction, ctx.seed, ctx.offset, dx, saved, weights)
+
+    body.register_autograd(autograd, setup_context=setup)
+    return body, body_backward
 
 
-@conve_body.register_fake
-def _(key, e, r, side, seed, offset, weights):
-    n, k = e.numel(), weights[0].shape[1]
-    return weights[0].new_empty((n, k)), weights[0].new_empty((n * (weights[9].shape[1] + k) + 66 + 2 * k,))
+# ConvE: side 0 = the tail direction, 1 = the head direction (rel[r + tot_relation]), and eval skips bn2.  The mask rows of a call start
+# at side * n: the head direction's rows follow the tail direction's, as in the fused step, so that the two forward calls of a training
+# step under one (seed, offset) draw the step's masks.  saved: the fc input [n, F], u [n, k] and the statistics 66 + 2 k.
+conve_body, conve_body_backward = _register_conv_1n(
+    "conve", "side", 0, lambda n, w: n * (w[9].shape[1] + w[0].shape[1]) + 66 + 2 * w[0].shape[1])
 
+# HypER: there is one relation table, so a direction selects nothing but the mask rows: row0 = 0 for the tail direction and n for the
+# head direction, so that the two forward calls of a training step under one (seed, offset) draw the fused step's masks.  Eval uses
+# the running statistics in all three batch norms.  saved: as ConvE's and the per-row filter [n, 288].
+hyper_body, hyper_body_backward = _register_conv_1n(
+    "hyper", "row0", 1, lambda n, w: n * (w[9].shape[1] + w[1].shape[1] + 288) + 66 + 2 * w[1].shape[1])
 
-@conve_body.register_kernel("cpu")
-def _(key, e, r, side, seed, offset, weights):
-    raise L.KgeHipError("kge::conve_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
+# InteractE: row0 as in kge::hyper_body.  The chequer permutations are the model's (found through `key`), not an operand.  saved: the
+# fc input, u, the feature-map factors [n, C] and the statistics 2 P + 2 C + 2 k (P = bn0's width, C = bn1's).
+interacte_body, interacte_body_backward = _register_conv_1n(
+    "interacte", "row0", 2,
+    lambda n, w: n * (w[10].shape[1] + w[2].shape[1] + w[6].shape[0]) + 2 * w[4].shape[0] + 2 * w[6].shape[0] + 2 * w[2].shape[1])
 
-
-@torch.library.custom_op("kge::conve_body_backward", mutates_args=(), device_types="cuda")
-def conve_body_backward(key: int, e: Tensor, r: Tensor, side: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
-                        weights: List[Tensor]) -> List[Tensor]:
-    m = _model(key)
-    grads = [torch.zeros_like(w) for w in weights]
-    K.conve_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                          r.contiguous(), side, dx.contiguous(), saved, row0=side * e.numel())
-    return grads
-
-
-@conve_body_backward.register_fake
-def _(key, e, r, side, seed, offset, dx, saved, weights):
-    return [torch.empty_like(w) for w in weights]
-
-
-def _conve_setup(ctx, inputs, output):
-    key, e, r, side, seed, offset, weights = inputs
-    ctx.key, ctx.side, ctx.seed, ctx.offset = key, side, seed, offset
-    ctx.save_for_backward(e, r, output[1], *weights)
-    ctx.mark_non_differentiable(output[1])
-
-
-def _conve_backward(ctx, dx, _dsaved):
-    e, r, saved, *weights = ctx.saved_tensors
-    return None, None, None, None, None, None, conve_body_backward(ctx.key, e, r, ctx.side, ctx.seed, ctx.offset, dx, saved, weights)
-
-
-conve_body.register_autograd(_conve_backward, setup_context=_conve_setup)
-
-
-# HypER's body (include/kge_hip.h: kge_hyper_body_*).  There is one relation table, so a direction selects nothing but the mask rows:
-# row0 = 0 for the tail direction and n for the head direction, so that the two forward calls of a training step under one (seed,
-# offset) draw the fused step's masks.  offset < 0 = the eval form (running statistics in all three batch norms, no draws).  Like
-# kge::conve_body, the training form updates the model's running buffers, a write outside the op's schema (mutates_args is empty):
-# eager execution only.
-@torch.library.custom_op("kge::hyper_body", mutates_args=(), device_types="cuda")
-def hyper_body(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
-    m = _model(key)
-    return K.hyper_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                                r.contiguous(), row0=row0)
-
-
-@hyper_body.register_fake
-def _(key, e, r, row0, seed, offset, weights):
-    n, D = e.numel(), weights[1].shape[1]
-    return weights[1].new_empty((n, D)), weights[1].new_empty((n * (weights[9].shape[1] + D + 288) + 66 + 2 * D,))
-
-
-@hyper_body.register_kernel("cpu")
-def _(key, e, r, row0, seed, offset, weights):
-    raise L.KgeHipError("kge::hyper_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
-
-
-@torch.library.custom_op("kge::hyper_body_backward", mutates_args=(), device_types="cuda")
-def hyper_body_backward(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
-                        weights: List[Tensor]) -> List[Tensor]:
-    m = _model(key)
-    grads = [torch.zeros_like(w) for w in weights]
-    K.hyper_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                          r.contiguous(), dx.contiguous(), saved, row0=row0)
-    return grads
-
-
-@hyper_body_backward.register_fake
-def _(key, e, r, row0, seed, offset, dx, saved, weights):
-    return [torch.empty_like(w) for w in weights]
-
-
-def _hyper_setup(ctx, inputs, output):
-    key, e, r, row0, seed, offset, weights = inputs
-    ctx.key, ctx.row0, ctx.seed, ctx.offset = key, row0, seed, offset
-    ctx.save_for_backward(e, r, output[1], *weights)
-    ctx.mark_non_differentiable(output[1])
-
-
-def _hyper_backward(ctx, dx, _dsaved):
-    e, r, saved, *weights = ctx.saved_tensors
-    return None, None, None, None, None, None, hyper_body_backward(ctx.key, e, r, ctx.row0, ctx.seed, ctx.offset, dx, saved, weights)
-
-
-hyper_body.register_autograd(_hyper_backward, setup_context=_hyper_setup)
-
-
-# InteractE's body (include/kge_hip.h: kge_interacte_body_*).  As in kge::hyper_body there is one relation table, row0 = 0 for the tail
-# direction and n for the head direction, offset < 0 = the eval form, and the training form updates the model's running buffers, a
-# write outside the op's schema: eager execution only.  The chequer permutations are the model's (found through `key`), not an operand.
-@torch.library.custom_op("kge::interacte_body", mutates_args=(), device_types="cuda")
-def interacte_body(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
-    m = _model(key)
-    return K.interacte_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                                    r.contiguous(), row0=row0)
-
-
-@interacte_body.register_fake
-def _(key, e, r, row0, seed, offset, weights):
-    n, k, P, C = e.numel(), weights[2].shape[1], weights[4].shape[0], weights[6].shape[0]
-    return weights[2].new_empty((n, k)), weights[2].new_empty((n * (weights[10].shape[1] + k + C) + 2 * P + 2 * C + 2 * k,))
-
-
-@interacte_body.register_kernel("cpu")
-def _(key, e, r, row0, seed, offset, weights):
-    raise L.KgeHipError("kge::interacte_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
-
-
-@torch.library.custom_op("kge::interacte_body_backward", mutates_args=(), device_types="cuda")
-def interacte_body_backward(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
-                            weights: List[Tensor]) -> List[Tensor]:
-    m = _model(key)
-    grads = [torch.zeros_like(w) for w in weights]
-    K.interacte_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                              r.contiguous(), dx.contiguous(), saved, row0=row0)
-    return grads
-
-
-@interacte_body_backward.register_fake
-def _(key, e, r, row0, seed, offset, dx, saved, weights):
-    return [torch.empty_like(w) for w in weights]
-
-
-def _interacte_setup(ctx, inputs, output):
-    key, e, r, row0, seed, offset, weights = inputs
-    ctx.key, ctx.row0, ctx.seed, ctx.offset = key, row0, seed, offset
-    ctx.save_for_backward(e, r, output[1], *weights)
-    ctx.mark_non_differentiable(output[1])
-
-
-def _interacte_backward(ctx, dx, _dsaved):
-    e, r, saved, *weights = ctx.saved_tensors
-    return None, None, None, None, None, None, interacte_body_backward(ctx.key, e, r, ctx.row0, ctx.seed, ctx.offset, dx, saved, weights)
-
-
-interacte_body.register_autograd(_interacte_backward, setup_context=_interacte_setup)
-
-
-# AcrE's body (include/kge_hip.h: kge_acre_body_*).  As in kge::interacte_body there is one relation table, row0 = 0 for the tail
-# direction and n for the head direction, offset < 0 = the eval form, and the training form updates the model's running buffers, a
-# write outside the op's schema: eager execution only.  weights: the model's parameters in state-dict order (bias first; the conv
-# biases only with acre_bias, the gate only in the parallel way); the way and the dilations are the model's (found through `key`).
-@torch.library.custom_op("kge::acre_body", mutates_args=(), device_types="cuda")
-def acre_body(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, weights: List[Tensor]) -> Tuple[Tensor, Tensor]:
-    m = _model(key)
-    return K.acre_body_forward(m.make_desc(list(weights), train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                               r.contiguous(), row0=row0)
-
-
-@acre_body.register_fake
-def _(key, e, r, row0, seed, offset, weights):
-    n, k, C = e.numel(), weights[1].shape[1], weights[5].shape[0]
-    layers = 4 if tuple(weights[-1].shape) == (400,) and weights[-2].dim() == 2 else 3   # the parallel way (the gate comes last) saves z_3 too
-    return weights[1].new_empty((n, k)), weights[1].new_empty((n * (layers * weights[9].shape[1] + k + C) + 2 + 2 * C + 2 * k,))
-
-
-@acre_body.register_kernel("cpu")
-def _(key, e, r, row0, seed, offset, weights):
-    raise L.KgeHipError("kge::acre_body: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % e.device)
-
-
-@torch.library.custom_op("kge::acre_body_backward", mutates_args=(), device_types="cuda")
-def acre_body_backward(key: int, e: Tensor, r: Tensor, row0: int, seed: int, offset: int, dx: Tensor, saved: Tensor,
-                       weights: List[Tensor]) -> List[Tensor]:
-    m = _model(key)
-    grads = [torch.zeros_like(w) for w in weights]
-    K.acre_body_backward(m.make_desc(list(weights), grads, train=offset >= 0, seed=seed, offset=max(offset, 0)), e.contiguous(),
-                         r.contiguous(), dx.contiguous(), saved, row0=row0)
-    return grads
-
-
-@acre_body_backward.register_fake
-def _(key, e, r, row0, seed, offset, dx, saved, weights):
-    return [torch.empty_like(w) for w in weights]
-
-
-def _acre_setup(ctx, inputs, output):
-    key, e, r, row0, seed, offset, weights = inputs
-    ctx.key, ctx.row0, ctx.seed, ctx.offset = key, row0, seed, offset
-    ctx.save_for_backward(e, r, output[1], *weights)
-    ctx.mark_non_differentiable(output[1])
-
-
-def _acre_backward(ctx, dx, _dsaved):
-    e, r, saved, *weights = ctx.saved_tensors
-    return None, None, None, None, None, None, acre_body_backward(ctx.key, e, r, ctx.row0, ctx.seed, ctx.offset, dx, saved, weights)
-
-
-acre_body.register_autograd(_acre_backward, setup_context=_acre_setup)
+# AcrE: row0 as in kge::hyper_body.  weights: the model's parameters in state-dict order (bias first; the conv biases only with
+# acre_bias, the gate only in the parallel way); the way and the dilations are the model's (found through `key`).  saved: c, z_1, z_2
+# [n, 400 C] each, in the parallel way z_3 too, then u, the factors [n, C] and the statistics 2 + 2 C + 2 k.  The weight count tells
+# the way: 11 + 3 or 11 + 6 tensors in the serial way, the gate's two more in the parallel way.
+acre_body, acre_body_backward = _register_conv_1n(
+    "acre", "row0", 1,
+    lambda n, w: n * ((4 if len(w) in (16, 19) else 3) * w[9].shape[1] + w[1].shape[1] + w[5].shape[0]) + 2 + 2 * w[5].shape[0]
+    + 2 * w[1].shape[1])
 
 
 @torch.library.custom_op("kge::one_to_n_scores", mutates_args=(), device_types="cuda")

@@ -71,7 +71,75 @@ class TuckER(ProjectionModel):
         return rank
 
 
-class ConvE(ProjectionModel):
+class Conv1NModel(ProjectionModel):
+    """What ConvE, HypER, InteractE and AcrE share on the host: three batch norms bn0 / bn1 / bn2 whose running buffers the training
+    form updates, one descriptor builder K.<kernel_name>_desc fed from make_desc, one body op torch.ops.kge.<kernel_name>_body in front
+    of the 1-N head, one fused step K.<kernel_name>_train_bce.  A subclass supplies its constructor, trainable_tensors() in
+    state-dict order, _geometry() (the model's own keywords of its descriptor builder) and _head_bias(); ConvE also its _direction."""
+
+    def _geometry(self):
+        raise NotImplementedError
+
+    def _head_bias(self):
+        raise NotImplementedError
+
+    def _direction(self, direction, e):
+        """The body op's direction argument: the mask row of the call's first row (the "head" rows follow the "tail" rows)."""
+        return 0 if direction == "tail" else e.numel()
+
+    def _norms(self):
+        return (self.bn0, self.bn1, self.bn2)
+
+    def running_buffers(self):
+        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+
+    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        norms = self._norms()
+        return getattr(K, self.kernel_name + "_desc")(
+            list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
+            tot_relation=self.tot_relation, dropouts=self.dropouts, eps=[bn.eps for bn in norms], momentum=[bn.momentum for bn in norms],
+            train=self.training if train is None else train, seed=self.dropout_seed if seed is None else seed,
+            offset=self.dropout_offset if offset is None else offset, **self._geometry())
+
+    def _count_batches(self, calls):
+        for bn in self._norms():
+            bn.num_batches_tracked += calls
+
+    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
+        getattr(K, self.kernel_name + "_train_bce")(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
+        self._count_batches(2)   # the step is two training forwards
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def embed2(self, e, r):
+        return self.ent_embeddings(e), self.rel_embeddings(r)
+
+    def forward(self, e, r, direction="tail"):
+        assert direction in ("head", "tail"), "Unknown forward direction"
+        offset = -1   # eval(): running statistics, no dropout (ConvE: no bn2 either)
+        if self.training:
+            offset = self.dropout_offset
+            if any(p > 0.0 for p in self.dropouts):
+                self.dropout_offset += 1
+        body = getattr(torch.ops.kge, self.kernel_name + "_body")
+        x, _saved = body(self._kge_op_key, e, r, self._direction(direction, e), self.dropout_seed, offset, self.trainable_tensors())
+        if self.training:
+            self._count_batches(1)
+        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self._head_bias(), False)
+
+    def predict_tail_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
+        return rank
+
+    def predict_head_rank(self, e, r, topk=-1):
+        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
+        return rank
+
+
+class ConvE(Conv1NModel):
     """projection.py:12-125.  forward(e, r, direction) = sigmoid(x @ ent.T + b) with x = relu(bn2(hdrop(fc(flatten(fdrop(relu(bn1(conv(
     idrop(bn0(img)))))))))) and img the [h2, h1] view of ent[e] stacked on that of rel[r] ("tail") or rel[r + tot_relation] ("head").  The
     torch layers (bn0, conv2d_1, bn1, fc, bn2) hold parameters and buffers only, so state_dict() has the reference's keys and shapes and
@@ -108,62 +176,22 @@ class ConvE(ProjectionModel):
         self.dropout_seed = int(kwargs.get("seed", 0) or 0)
         self.dropout_offset = 0
 
-    def _norms(self):
-        return (self.bn0, self.bn1, self.bn2)
-
     def trainable_tensors(self):
         return [self.ent_embeddings.weight, self.rel_embeddings.weight, self.b.weight, self.bn0.weight, self.bn0.bias, self.conv2d_1.weight,
                 self.conv2d_1.bias, self.bn1.weight, self.bn1.bias, self.fc.weight, self.fc.bias, self.bn2.weight, self.bn2.bias]
 
-    def running_buffers(self):
-        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+    def _geometry(self):
+        return dict(hidden_size=int(self.hidden_size), hidden_size_1=int(self.hidden_size_1))
 
-    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
-        if weights is None:
-            weights = self.trainable_tensors()
-        return K.conve_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
-                            tot_relation=self.tot_relation, hidden_size=int(self.hidden_size), hidden_size_1=int(self.hidden_size_1),
-                            dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()], momentum=[bn.momentum for bn in self._norms()],
-                            train=self.training if train is None else train, seed=self.dropout_seed if seed is None else seed,
-                            offset=self.dropout_offset if offset is None else offset)
+    def _head_bias(self):
+        return self.b.weight
 
-    def _count_batches(self, calls):
-        for bn in self._norms():
-            bn.num_batches_tracked += calls
-
-    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
-        K.conve_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
-        self._count_batches(2)   # the step is two training forwards
-
-    def embed(self, h, r, t):
-        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
-
-    def embed2(self, e, r):
-        return self.ent_embeddings(e), self.rel_embeddings(r)
-
-    def forward(self, e, r, direction="tail"):
-        assert direction in ("head", "tail"), "Unknown forward direction"
-        offset = -1   # eval(): running statistics, no bn2, no dropout
-        if self.training:
-            offset = self.dropout_offset
-            if any(p > 0.0 for p in self.dropouts):
-                self.dropout_offset += 1
-        x, _saved = torch.ops.kge.conve_body(self._kge_op_key, e, r, 0 if direction == "tail" else 1, self.dropout_seed, offset,
-                                             self.trainable_tensors())
-        if self.training:
-            self._count_batches(1)
-        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.b.weight, False)
-
-    def predict_tail_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
-        return rank
-
-    def predict_head_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
-        return rank
+    def _direction(self, direction, e):
+        """side: 0 reads rel[r], 1 rel[r + tot_relation]; the mask rows of side 1 follow those of side 0."""
+        return 0 if direction == "tail" else 1
 
 
-class HypER(ProjectionModel):
+class HypER(Conv1NModel):
     """projection.py:508-618.  forward(e, r, direction) = sigmoid(x @ ent.T + b) with x = relu(bn2(hdrop(fc(flatten(fdrop(bn1(conv(
     idrop(bn0(ent[e])), filt)))))))) and filt = fc1(rel[r]) viewed [32, 9]: a 1 x 9 filter per row and channel (the reference's grouped
     convolution and permutes are exactly this).  There is one relation table: `direction` selects no relation row, only the mask rows.
@@ -209,62 +237,18 @@ class HypER(ProjectionModel):
     def device(self):
         return self._device if self._device is not None else self.ent_embeddings.weight.device
 
-    def _norms(self):
-        return (self.bn0, self.bn1, self.bn2)
-
     def trainable_tensors(self):
         return [self.b, self.ent_embeddings.weight, self.rel_embeddings.weight, self.bn0.weight, self.bn0.bias, self.bn1.weight,
                 self.bn1.bias, self.bn2.weight, self.bn2.bias, self.fc.weight, self.fc.bias, self.fc1.weight, self.fc1.bias]
 
-    def running_buffers(self):
-        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+    def _geometry(self):
+        return dict(ent_hidden_size=int(self.ent_hidden_size), rel_hidden_size=int(self.rel_hidden_size))
 
-    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
-        if weights is None:
-            weights = self.trainable_tensors()
-        return K.hyper_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
-                            tot_relation=self.tot_relation, ent_hidden_size=int(self.ent_hidden_size),
-                            rel_hidden_size=int(self.rel_hidden_size), dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()],
-                            momentum=[bn.momentum for bn in self._norms()], train=self.training if train is None else train,
-                            seed=self.dropout_seed if seed is None else seed, offset=self.dropout_offset if offset is None else offset)
-
-    def _count_batches(self, calls):
-        for bn in self._norms():
-            bn.num_batches_tracked += calls
-
-    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
-        K.hyper_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
-        self._count_batches(2)   # the step is two training forwards
-
-    def embed(self, h, r, t):
-        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
-
-    def embed2(self, e, r):
-        return self.ent_embeddings(e), self.rel_embeddings(r)
-
-    def forward(self, e, r, direction="tail"):
-        assert direction in ("head", "tail"), "Unknown forward direction"
-        offset = -1   # eval(): running statistics, no dropout
-        if self.training:
-            offset = self.dropout_offset
-            if any(p > 0.0 for p in self.dropouts):
-                self.dropout_offset += 1
-        x, _saved = torch.ops.kge.hyper_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
-                                             self.trainable_tensors())
-        if self.training:
-            self._count_batches(1)
-        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.b, False)
-
-    def predict_tail_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
-        return rank
-
-    def predict_head_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
-        return rank
+    def _head_bias(self):
+        return self.b
 
 
-class InteractE(ProjectionModel):
+class InteractE(Conv1NModel):
     """projection.py:347-505.  forward(e, r, direction) = sigmoid(x @ ent.T + bias) with x = relu(bn2(hdrop(fc(flatten(fdrop(relu(bn1(
     conv(idrop(bn0(img)))))))))), img the feature_permutation chequer permutations of [ent[e] | rel[r]] viewed [2 reshape_width,
     reshape_height], and conv the depthwise convolution with circular padding whose num_filters filters are shared by the
@@ -342,64 +326,20 @@ class InteractE(ProjectionModel):
             self._perm_cache = (key, cp, K.interacte_perm(cp, int(self.feature_permutation), int(self.hidden_size), dev))
         return self._perm_cache[2]
 
-    def _norms(self):
-        return (self.bn0, self.bn1, self.bn2)
-
     def trainable_tensors(self):
         return [self.bias, self.conv_filt, self.ent_embeddings.weight, self.rel_embeddings.weight, self.bn0.weight, self.bn0.bias,
                 self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias, self.fc.weight, self.fc.bias]
 
-    def running_buffers(self):
-        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+    def _geometry(self):
+        return dict(reshape_height=int(self.reshape_height), reshape_width=int(self.reshape_width),
+                    feature_permutation=int(self.feature_permutation), num_filters=int(self.num_filters),
+                    kernel_size=int(self.kernel_size), perms=self._perms())
 
-    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
-        if weights is None:
-            weights = self.trainable_tensors()
-        return K.interacte_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
-                                tot_relation=self.tot_relation, reshape_height=int(self.reshape_height),
-                                reshape_width=int(self.reshape_width), feature_permutation=int(self.feature_permutation),
-                                num_filters=int(self.num_filters), kernel_size=int(self.kernel_size), perms=self._perms(),
-                                dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()],
-                                momentum=[bn.momentum for bn in self._norms()], train=self.training if train is None else train,
-                                seed=self.dropout_seed if seed is None else seed, offset=self.dropout_offset if offset is None else offset)
-
-    def _count_batches(self, calls):
-        for bn in self._norms():
-            bn.num_batches_tracked += calls
-
-    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
-        K.interacte_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
-        self._count_batches(2)   # the step is two training forwards
-
-    def embed(self, h, r, t):
-        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
-
-    def embed2(self, e, r):
-        return self.ent_embeddings(e), self.rel_embeddings(r)
-
-    def forward(self, e, r, direction="tail"):
-        assert direction in ("head", "tail"), "Unknown forward direction"
-        offset = -1   # eval(): running statistics, no dropout
-        if self.training:
-            offset = self.dropout_offset
-            if any(p > 0.0 for p in self.dropouts):
-                self.dropout_offset += 1
-        x, _saved = torch.ops.kge.interacte_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
-                                                 self.trainable_tensors())
-        if self.training:
-            self._count_batches(1)
-        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.bias, False)
-
-    def predict_tail_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
-        return rank
-
-    def predict_head_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
-        return rank
+    def _head_bias(self):
+        return self.bias
 
 
-class AcrE(ProjectionModel):
+class AcrE(Conv1NModel):
     """projection.py:621-746.  forward(e, r, direction) = sigmoid(x @ ent.T + bias) with x = relu(bn2(hdrop(fc(flatten(fdrop(relu(bn1(
     c))))))), y0 = idrop(bn0(img)), img the [10, 20] view of ent[e] stacked on that of rel[r] (hidden_size is 200 by construction), and
     c = conv3(conv2(conv1(y0))) + y0 in the "serial" way: three 3 x 3 convolutions with dilations first / second / third_atrous and as
@@ -445,9 +385,6 @@ class AcrE(ProjectionModel):
         self.dropout_seed = int(kwargs.get("seed", 0) or 0)
         self.dropout_offset = 0
 
-    def _norms(self):
-        return (self.bn0, self.bn1, self.bn2)
-
     def trainable_tensors(self):
         """The parameters in state-dict order: the conv biases only with acre_bias, the gate only in the parallel way."""
         t = [self.bias, self.ent_embeddings.weight, self.rel_embeddings.weight, self.bn0.weight, self.bn0.bias, self.bn1.weight,
@@ -460,54 +397,13 @@ class AcrE(ProjectionModel):
             t += [self.W_gate_e.weight, self.W_gate_e.bias]
         return t
 
-    def running_buffers(self):
-        return [t for bn in self._norms() for t in (bn.running_mean, bn.running_var)]
+    def _geometry(self):
+        return dict(hidden_size=int(self.hidden_size), in_channels=int(self.in_channels), way=0 if self.way == "serial" else 1,
+                    first_atrous=int(self.first_atrous), second_atrous=int(self.second_atrous), third_atrous=int(self.third_atrous),
+                    acre_bias=bool(self.acre_bias))
 
-    def make_desc(self, weights=None, grads=None, train=None, seed=None, offset=None):
-        if weights is None:
-            weights = self.trainable_tensors()
-        return K.acre_desc(list(weights), self.running_buffers(), None if grads is None else list(grads), tot_entity=self.tot_entity,
-                           tot_relation=self.tot_relation, hidden_size=int(self.hidden_size), in_channels=int(self.in_channels),
-                           way=0 if self.way == "serial" else 1, first_atrous=int(self.first_atrous),
-                           second_atrous=int(self.second_atrous), third_atrous=int(self.third_atrous), acre_bias=bool(self.acre_bias),
-                           dropouts=self.dropouts, eps=[bn.eps for bn in self._norms()], momentum=[bn.momentum for bn in self._norms()],
-                           train=self.training if train is None else train, seed=self.dropout_seed if seed is None else seed,
-                           offset=self.dropout_offset if offset is None else offset)
-
-    def _count_batches(self, calls):
-        for bn in self._norms():
-            bn.num_batches_tracked += calls
-
-    def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
-        K.acre_train_bce(desc, h, r, t, *hr_t_csr, *tr_h_csr, getattr(config, "label_smoothing", None), loss_buf)
-        self._count_batches(2)   # the step is two training forwards
-
-    def embed(self, h, r, t):
-        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
-
-    def embed2(self, e, r):
-        return self.ent_embeddings(e), self.rel_embeddings(r)
-
-    def forward(self, e, r, direction="tail"):
-        assert direction in ("head", "tail"), "Unknown forward direction"
-        offset = -1   # eval(): running statistics, no dropout
-        if self.training:
-            offset = self.dropout_offset
-            if any(p > 0.0 for p in self.dropouts):
-                self.dropout_offset += 1
-        x, _saved = torch.ops.kge.acre_body(self._kge_op_key, e, r, 0 if direction == "tail" else e.numel(), self.dropout_seed, offset,
-                                            self.trainable_tensors())
-        if self.training:
-            self._count_batches(1)
-        return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self.bias, False)
-
-    def predict_tail_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
-        return rank
-
-    def predict_head_rank(self, e, r, topk=-1):
-        _, rank = torch.topk(-self.forward(e, r, direction="head"), k=topk)
-        return rank
+    def _head_bias(self):
+        return self.bias
 
 
 class ProjE_pointwise(ProjectionModel):
