@@ -850,6 +850,67 @@ size_t kge_convkb_sweep_scores_side_workspace_bytes(const kge_convkb_desc* d, in
 int kge_convkb_sweep_scores_side(const kge_convkb_desc* d, const int64_t* triples, int64_t n, int side, void* workspace,
                                  size_t workspace_bytes, float* scores, void* stream);
 
+/* ---- MuRP (models/pointwise.py:1004-1133) as the reference executes it, in float64 throughout: every table, gradient, score and the
+ * loss are double (csrc/kge_murp.hip).  With clip(x) = x / (|x| - 1e-5) where |x| >= 1, else x:
+ *     h', t', r' = clip(ent[h]), clip(ent[t]), clip(rel[r])
+ *     u_e = arsech(c) h' / c,  c = clamp(|h'|, 1e-10, 1 - 1e-5);      u_w = u_e o wu[r]
+ *     u_m = clip((1 / cosh(n)) u_w / n),  n = max(|u_w|, 1e-10);       v_m = clip(p_sum(t', r'))
+ *     preds = -((2 arsech(clamp(|p_sum(-u_m, v_m)|, 1e-10, 1 - 1e-5)))^2 - bs[h] - bo[t])
+ *     p_sum(x, y) = ((1 + 2 x.y + sy) x + (1 - sx) y) / (1 + 2 x.y + sx sy),  sx, sy = clamp(|x|^2, 0, 1 - 1e-5), clamp(|y|^2, ...)
+ * Quirks kept, because they are the maps the reference's checkpoints were trained with: arsech(x) = log((1 + sqrt(1 - x^2)) / x)
+ * stands where the Poincare ball's log map has artanh, and 1 / cosh where its exponential map has tanh.  preds is a logit: higher
+ * means more plausible.  The model has no kge_model id: it has its own descriptor and entry points.
+ *
+ * tables / grads, in state-dict order: wu [tot_relation, dim], bs [tot_entity], bo [tot_entity], ent [>= tot_entity, dim],
+ * rel [>= tot_relation, dim].  The backward follows autograd's conventions: `where` passes the chosen branch's gradient only, clamp
+ * passes it on the closed interval, the 2-norm has gradient 0 at 0; rows 0 of ent and rel receive nothing (padding_idx = 0), index 0
+ * of wu, bs and bo does; a row whose last clamp is saturated gives bs and bo their gradient and wu, ent, rel none.  Gradients are
+ * scattered with float64 atomic adds: sums are not bit-reproducible run to run.
+ *
+ * rank_order: which candidates come before the true one in a rank.  0 = ascending score, the order of the reference's
+ * predict_*_rank lists (the least plausible candidate first): rank = #{e : s_e < s_true}.  1 = most plausible first:
+ * rank = #{e : s_e > s_true}, which is also what the reference's MetricCalculator computes from those lists (it walks them from the
+ * end).  Filtered ranks subtract the known entities that come before the true one.
+ *
+ * Refused loudly (kge_last_error): null tables, dim outside 1..2048, a rank_order other than 0 / 1, ids out of range in the debug
+ * mode (kge_set_debug), a workspace that is too small. */
+typedef struct kge_murp_desc {
+    int64_t tot_entity, tot_relation;
+    int32_t dim;
+    int32_t rank_order;
+    const double* tables[5];
+    double* grads[5];
+} kge_murp_desc;
+
+/* MuRP.forward(h, r, t) -> preds[n] and its autograd backward (g_* += d(sum_i dscore[i] * preds_i) / d tensor). */
+int kge_murp_score_forward(const kge_murp_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, double* preds,
+                           void* stream);
+int kge_murp_score_backward(const kge_murp_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, const double* dscore,
+                            void* stream);
+/* Fused training step on explicit rows: forward, *loss += BCEWithLogitsLoss()(preds, clamp(y, 0, 1)) (the mean over the n rows; y is
+ * +1 / -1 as the generator writes it), and the backward into all five gradient tensors.  loss: one double. */
+int kge_murp_train_bce(const kge_murp_desc* d, const int64_t* h, const int64_t* r, const int64_t* t, const int64_t* y, int64_t n,
+                       double* loss, void* stream);
+/* The optimiser in one launch over all rows of all five tensors (utils/riemannian_optimizer.py).  riemannian != 0: on the rows of ent
+ * and rel  g' = g (1 - clamp(|p|^2, 0, 1 - 1e-5))^2 / 4,  v = -lr g',  p = p_sum(p, tanh(|v| / (1 - clamp(|p|^2))) v / |v|)  with |v|
+ * clamped below at 1e-10 (nothing projects p back into the ball: the forward's clip does); wu, bs, bo: p -= lr g.  riemannian = 0:
+ * p -= lr g everywhere (torch.optim.SGD on float64 tables).  Clears the gradients it consumed; a row (an element) whose gradient is
+ * zero is left unwritten, which equals the reference because p_sum(p, 0) = p exactly. */
+int kge_murp_rsgd_step(const kge_murp_desc* d, double lr, int32_t riemannian, void* stream);
+
+/* Filtered and raw ranks; filter CSR arguments, `ranks` int32 [4, n] and `ties` int32 [2, n] (or NULL) as kge_eval_ranks_ties.  A
+ * (query, candidate) pair is two dot products and the candidate's squared norm, then scalar work in double; the true candidate's score
+ * and the filter lists' scores are accumulated in the sweep's order, so the counts are exact with respect to the scores
+ * kge_murp_sweep_scores_side stores, and candidates that saturate at the last clamp tie bit for bit, as in the reference. */
+size_t kge_murp_eval_ranks_workspace_bytes(const kge_murp_desc* d, int64_t n);
+int kge_murp_eval_ranks(const kge_murp_desc* d, const int64_t* triples, int64_t n, const int64_t* tail_off, const int32_t* tail_ids,
+                        const int64_t* head_off, const int32_t* head_ids, void* workspace, size_t workspace_bytes, int32_t* ranks,
+                        int32_t* ties, void* stream);
+/* scores double [n, E]: side 0 = preds of (h_i, r_i, e) for every e, side 1 = preds of (e, r_i, t_i). */
+size_t kge_murp_sweep_scores_side_workspace_bytes(const kge_murp_desc* d, int64_t n);
+int kge_murp_sweep_scores_side(const kge_murp_desc* d, const int64_t* triples, int64_t n, int32_t side, void* workspace,
+                               size_t workspace_bytes, double* scores, void* stream);
+
 /* ---- TuckER (models/projection.py:259-344): the body in front of the 1-N head (csrc/kge_tucker.hip).  For a row
  * with entity e and relation r:
  *     a = normalize(ent[e]) * m0,   M = sum_k rel[r][k] W[k,:,:] * m1,   z_j = sum_i a_i M_ij,   x = normalize(z) * m2,

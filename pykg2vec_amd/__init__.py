@@ -16,7 +16,7 @@ MODEL_MAP = {  # lower-case name -> "module.Class", same keys as Importer.modelM
     "simple_ignr": "pointwise.SimplE_ignr", "quate": "pointwise.QuatE",
     "slm": "pairwise.SLM", "sme": "pairwise.SME", "sme_bl": "pairwise.SME_BL",
     "kg2e": "pairwise.KG2E", "hole": "pairwise.HoLE", "octonione": "pointwise.OctonionE",
-    "convkb": "pointwise.ConvKB", "tucker": "projection.TuckER",
+    "convkb": "pointwise.ConvKB", "murp": "pointwise.MuRP", "tucker": "projection.TuckER",
     "proje_pointwise": "projection.ProjE_pointwise", "conve": "projection.ConvE",
     "hyper": "projection.HypER", "interacte": "projection.InteractE",
     "acre": "projection.AcrE",

@@ -136,6 +136,15 @@ class ConvKBDesc(ctypes.Structure):
 _CKB = ctypes.POINTER(ConvKBDesc)
 
 
+class MurpDesc(ctypes.Structure):
+    """struct kge_murp_desc (tables / grads: wu, bs, bo, ent, rel -- float64)"""
+    _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("dim", ctypes.c_int32), ("rank_order", ctypes.c_int32),
+                ("tables", ctypes.c_void_p * 5), ("grads", ctypes.c_void_p * 5)]
+
+
+_MRP = ctypes.POINTER(MurpDesc)
+
+
 class TuckerDesc(ctypes.Structure):
     """struct kge_tucker_desc"""
     _fields_ = [("tot_entity", ctypes.c_int64), ("tot_relation", ctypes.c_int64), ("d1", ctypes.c_int32), ("d2", ctypes.c_int32),
@@ -299,6 +308,16 @@ _SIGNATURES = {
     "kge_convkb_eval_ranks": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_convkb_sweep_scores_side_workspace_bytes": (ctypes.c_size_t, [_CKB, ctypes.c_int64]),
+    "kge_murp_score_forward": (ctypes.c_int, [_MRP] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_murp_score_backward": (ctypes.c_int, [_MRP] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_murp_train_bce": (ctypes.c_int, [_MRP] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_murp_rsgd_step": (ctypes.c_int, [_MRP, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p]),
+    "kge_murp_eval_ranks_workspace_bytes": (ctypes.c_size_t, [_MRP, ctypes.c_int64]),
+    "kge_murp_eval_ranks": (ctypes.c_int, [_MRP, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4
+                            + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_murp_sweep_scores_side_workspace_bytes": (ctypes.c_size_t, [_MRP, ctypes.c_int64]),
+    "kge_murp_sweep_scores_side": (ctypes.c_int, [_MRP, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                  ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_convkb_sweep_scores_side": (ctypes.c_int, [_CKB, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_staged_step_bytes": (ctypes.c_size_t, []),

@@ -26,6 +26,10 @@ class Criterion:
         return F.softplus(target * preds).mean()
 
     @staticmethod
+    def pointwise_bce(preds, target):  # criterion.py:37-39 (MuRP): targets arrive as +1 / -1, the -1 rows become label 0
+        return torch.nn.BCEWithLogitsLoss()(preds, torch.clamp(target, min=0.0, max=1.0))
+
+    @staticmethod
     def multi_class_bce(pred_heads, pred_tails, tr_h, hr_t, label_smoothing, tot_entity):  # criterion.py:41-49
         if label_smoothing is not None and tot_entity is not None:
             hr_t = hr_t * (1.0 - label_smoothing) + 1.0 / tot_entity

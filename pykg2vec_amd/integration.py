@@ -12,7 +12,7 @@ import types
 
 PAIRWISE = ("TransE", "TransH", "TransD", "TransM", "TransR", "RotatE", "Rescal", "NTN", "SLM", "SME", "SME_BL", "KG2E",
             "HoLE")
-POINTWISE = ("DistMult", "Complex", "ComplexN3", "ANALOGY", "CP", "SimplE", "SimplE_ignr", "QuatE", "OctonionE", "ConvKB")
+POINTWISE = ("DistMult", "Complex", "ComplexN3", "ANALOGY", "CP", "SimplE", "SimplE_ignr", "QuatE", "OctonionE", "ConvKB", "MuRP")
 
 
 class _Installed:

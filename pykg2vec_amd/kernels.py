@@ -238,6 +238,8 @@ def _workspace(desc, n, device):
 
 
 def score_forward(desc, h, r, t):
+    if isinstance(desc, L.MurpDesc):
+        return murp_score_forward(desc, h, r, t)
     if isinstance(desc, L.ConvKBDesc):
         return convkb_score_forward(desc, h, r, t)
     n = h.numel()
@@ -251,6 +253,8 @@ def score_forward(desc, h, r, t):
 
 
 def score_backward(desc, h, r, t, dscore):
+    if isinstance(desc, L.MurpDesc):
+        return murp_score_backward(desc, h, r, t, dscore)
     if isinstance(desc, L.ConvKBDesc):
         return convkb_score_backward(desc, h, r, t, dscore)
     n = h.numel()
@@ -716,6 +720,8 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
     """triples int64 [n,3]; CSR filter lists (int64 offsets [n+1], int32 ids) or None.  Returns int32 [4,n]:
     rank_head, rank_tail, filtered_rank_head, filtered_rank_tail (0-based).  ties: optional int32 [2, n] that receives, per head /
     tail sweep, the number of other candidates whose energy equals the true one's (kge_eval_ranks_ties)."""
+    if isinstance(desc, L.MurpDesc):
+        return murp_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=ties)
     if isinstance(desc, L.ConvKBDesc):
         if ties is not None:
             ties.fill_(-1)   # not counted
@@ -775,6 +781,9 @@ def eval_ranks_grouped(desc, triples, group_of_triple, group_rel, qblocks, tail_
 
 def eval_sweep_scores(desc, triples, workspace=None):
     """float32 [2n, E]: row 2i = energies of (h_i, r_i, e) for all e, row 2i+1 = energies of (e, r_i, t_i)."""
+    if isinstance(desc, L.MurpDesc):     # (float64 preds; one-sided entry point only: the two sides interleaved)
+        both = torch.stack([murp_sweep_scores_side(desc, triples, 0), murp_sweep_scores_side(desc, triples, 1)], 1)
+        return both.view(2 * triples.shape[0], desc.tot_entity)
     if isinstance(desc, L.ConvKBDesc):   # one-sided entry point only: the two sides interleaved
         both = torch.stack([convkb_sweep_scores_side(desc, triples, 0), convkb_sweep_scores_side(desc, triples, 1)], 1)
         return both.view(2 * triples.shape[0], desc.tot_entity)
@@ -791,6 +800,8 @@ def eval_sweep_scores(desc, triples, workspace=None):
 def eval_sweep_scores_side(desc, triples, side, workspace=None):
     """float32 [n, E]: side 0 = energies of (h_i, r_i, e) for all e, side 1 = energies of (e, r_i, t_i); the other side's query
     is never swept (kge_eval_sweep_scores_side).  TransR / NTN / SLM compute both sides per call: the full sweep, sliced."""
+    if isinstance(desc, L.MurpDesc):
+        return murp_sweep_scores_side(desc, triples, side)
     if isinstance(desc, L.ConvKBDesc):
         return convkb_sweep_scores_side(desc, triples, side)
     if desc.model in (MODEL_IDS["transr"], MODEL_IDS["ntn"], MODEL_IDS["slm"]):
@@ -1646,6 +1657,88 @@ def convkb_sweep_scores_side(desc, triples, side):
     wp, wb = _desc_ws(desc, "kge_convkb_sweep_scores_side_workspace_bytes", n)
     L.check(L.load().kge_convkb_sweep_scores_side(ctypes.byref(desc), _ids(triples, "triples"), n, int(side), wp, wb,
                                                   _dev(out, torch.float32, "scores"), _stream()), "kge_convkb_sweep_scores_side")
+    return out
+
+
+# ---------------------------------------------------------------- MuRP (csrc/kge_murp.hip): its own descriptor and entry points, float64
+def murp_desc(tables, grads=None, *, tot_entity, tot_relation, dim, rank_order=0):
+    """kge_murp_desc.  `tables` / `grads`: wu, bs, bo, ent_embeddings.weight, rel_embeddings.weight (the model's state-dict order), all
+    float64.  Shapes are checked here (the kernels index rows by id without a bounds test); dim and rank_order are checked by the
+    library, which refuses bad ones loudly.  rank_order: 0 = ascending score (the reference's lists), 1 = most plausible first."""
+    E, R, k = int(tot_entity), int(tot_relation), int(dim)
+    if len(tables) != 5:
+        raise L.KgeHipError("murp: 5 tensors expected (wu, bs, bo, ent, rel), got %d" % len(tables))
+    wu, bs, bo, ent, rel = tables
+    _check_embeddings("murp", ("ent_embeddings", ent, E, k), ("rel_embeddings", rel, R, k))
+    for name, t, shape in (("wu", wu, (R, k)), ("bs", bs, (E,)), ("bo", bo, (E,))):
+        if tuple(t.shape) != shape:
+            raise L.KgeHipError("murp: %s must be %s (got %s)" % (name, shape, tuple(t.shape)))
+    d = L.MurpDesc()
+    d.tot_entity, d.tot_relation, d.dim, d.rank_order = E, R, k, int(rank_order)
+    names = ("wu", "bs", "bo", "ent_embeddings", "rel_embeddings")
+    for i, (name, t) in enumerate(zip(names, tables)):
+        d.tables[i] = _dev(t, torch.float64, name).value
+    if grads is not None:
+        if len(grads) != 5:
+            raise L.KgeHipError("murp: 5 gradient tensors expected, got %d" % len(grads))
+        for i, (name, g, t) in enumerate(zip(names, grads, tables)):
+            if g.shape != t.shape:
+                raise ValueError("grad shape %s != tensor shape %s" % (tuple(g.shape), tuple(t.shape)))
+            d.grads[i] = _dev(g, torch.float64, "grad of " + name).value
+    d._keepalive = (tables, grads)
+    d._ws = None
+    return d
+
+
+def murp_new_loss(device):
+    """MuRP's loss accumulator: one float64 (new_loss_buffer / read_loss are the fp32 models')."""
+    return torch.zeros(1, dtype=torch.float64, device=device)
+
+
+def murp_score_forward(desc, h, r, t):
+    n = h.numel()
+    if r.numel() != n or t.numel() != n:
+        raise ValueError("h, r, t must have equal lengths")
+    out = torch.empty(n, dtype=torch.float64, device=h.device)
+    L.check(L.load().kge_murp_score_forward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
+                                            _dev(out, torch.float64, "preds"), _stream()), "kge_murp_score_forward")
+    return out
+
+
+def murp_score_backward(desc, h, r, t, dscore):
+    n = h.numel()
+    if r.numel() != n or t.numel() != n or dscore.numel() != n:
+        raise ValueError("h, r, t, dscore must have equal lengths")
+    L.check(L.load().kge_murp_score_backward(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), n,
+                                             _dev(dscore, torch.float64, "dscore"), _stream()), "kge_murp_score_backward")
+
+
+def murp_train_bce(desc, h, r, t, y, loss):
+    """Forward + mean BCE-with-logits on clamp(y, 0, 1) + the five gradients; loss: murp_new_loss's accumulator."""
+    n = h.numel()
+    if r.numel() != n or t.numel() != n or y.numel() != n:
+        raise ValueError("h, r, t, y must have equal lengths")
+    L.check(L.load().kge_murp_train_bce(ctypes.byref(desc), _ids(h, "h"), _ids(r, "r"), _ids(t, "t"), _ids(y, "y"), n,
+                                        _dev(loss, torch.float64, "loss"), _stream()), "kge_murp_train_bce")
+
+
+def murp_rsgd_step(desc, lr, riemannian=True):
+    """One optimiser launch over all five tensors; clears the gradients it consumed."""
+    L.check(L.load().kge_murp_rsgd_step(ctypes.byref(desc), float(lr), 1 if riemannian else 0, _stream()), "kge_murp_rsgd_step")
+
+
+def murp_eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, ties=None):
+    """int32 [4, n] as eval_ranks (+ ties int32 [2, n]), by the descriptor's rank_order."""
+    return _projection_eval_ranks("kge_murp_eval_ranks", desc, triples, tail_off, tail_ids, head_off, head_ids, ties)
+
+
+def murp_sweep_scores_side(desc, triples, side):
+    """float64 [n, E]: side 0 = preds of (h_i, r_i, e) for all e, side 1 = preds of (e, r_i, t_i)."""
+    n = triples.shape[0]
+    out = torch.empty((n, desc.tot_entity), dtype=torch.float64, device=triples.device)
+    wp, wb = _desc_ws(desc, "kge_murp_sweep_scores_side_workspace_bytes", n)
+    L.check(L.load().kge_murp_sweep_scores_side(ctypes.byref(desc), _ids(triples, "triples"), n, int(side), wp, wb,
+                                                _dev(out, torch.float64, "scores"), _stream()), "kge_murp_sweep_scores_side")
     return out
 
 

@@ -5,6 +5,8 @@ PyTorch-ROCm custom op that keeps each model's forward()/embed() signature").
   torch.ops.kge.score_backward(key, h, r, t, dscore, weights) -> dense gradients of `weights` (nn.Embedding(sparse=False) semantics)
   torch.ops.kge.convkb_score(key, h, r, t, weights) -> float32 [N]   ConvKB.forward (models/pointwise.py:302-318); weights = ent, rel, fc1.weight, fc1.bias
   torch.ops.kge.convkb_score_backward(key, h, r, t, dscore, weights) -> their dense gradients (the filters are fixed inputs)
+  torch.ops.kge.murp_score(key, h, r, t, weights) -> float64 [N]     MuRP.forward (models/pointwise.py:1081-1102); weights = wu, bs, bo, ent, rel (float64)
+  torch.ops.kge.murp_score_backward(key, h, r, t, dscore, weights) -> their dense gradients (rows 0 of ent and rel get none: padding_idx = 0)
   torch.ops.kge.tucker_body(key, e, r, seed, offset, weights) -> (x float32 [N, d1], saved)   the body of TuckER.forward (models/projection.py:321-334); weights = ent, rel, W
   torch.ops.kge.tucker_body_backward(key, e, r, seed, offset, dx, saved, weights) -> their dense gradients
   torch.ops.kge.proje_body(key, e, r, side, seed, offset, weights) -> x float32 [N, k]   tanh(ent[e] o De_s + rel[r] o Dr_s + bc_s) with dropout: f1 / f2 of ProjE_pointwise (models/projection.py:212-228); weights = its parameter_list
@@ -138,6 +140,44 @@ def _convkb_backward(ctx, dscore):
 
 
 convkb_score.register_autograd(_convkb_backward, setup_context=_score_setup)
+
+
+# MuRP has its own descriptor and entry points too (include/kge_hip.h: kge_murp_*), in float64
+@torch.library.custom_op("kge::murp_score", mutates_args=(), device_types="cuda")
+def murp_score(key: int, h: Tensor, r: Tensor, t: Tensor, weights: List[Tensor]) -> Tensor:
+    m = _model(key)
+    return K.murp_score_forward(m.make_desc(list(weights)), h.contiguous(), r.contiguous(), t.contiguous())
+
+
+@murp_score.register_fake
+def _(key, h, r, t, weights):
+    return h.new_empty((h.numel(),), dtype=torch.float64)
+
+
+@murp_score.register_kernel("cpu")
+def _(key, h, r, t, weights):
+    raise L.KgeHipError("kge::murp_score: ids and tables must live on the HIP device (got %s); the HIP path has no CPU fallback" % h.device)
+
+
+@torch.library.custom_op("kge::murp_score_backward", mutates_args=(), device_types="cuda")
+def murp_score_backward(key: int, h: Tensor, r: Tensor, t: Tensor, dscore: Tensor, weights: List[Tensor]) -> List[Tensor]:
+    m = _model(key)
+    grads = [torch.zeros_like(w) for w in weights]
+    K.murp_score_backward(m.make_desc(list(weights), grads), h.contiguous(), r.contiguous(), t.contiguous(), dscore.contiguous())
+    return grads
+
+
+@murp_score_backward.register_fake
+def _(key, h, r, t, dscore, weights):
+    return [torch.empty_like(w) for w in weights]
+
+
+def _murp_backward(ctx, dscore):
+    h, r, t, *weights = ctx.saved_tensors
+    return None, None, None, None, murp_score_backward(ctx.key, h, r, t, dscore, weights)
+
+
+murp_score.register_autograd(_murp_backward, setup_context=_score_setup)
 
 
 # TuckER's body (include/kge_hip.h: kge_tucker_body_*).  seed / offset key the dropout masks the two ops recompute; the model's

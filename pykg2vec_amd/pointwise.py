@@ -1,7 +1,8 @@
 """Drop-in pointwise (semantic-matching) models mirroring pykg2vec/models/pointwise.py (DistMult, Complex,
-ComplexN3, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, OctonionE, ConvKB), scored by HIP kernels.  `get_reg` keeps the reference's
+ComplexN3, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, OctonionE, ConvKB, MuRP), scored by HIP kernels.  `get_reg` keeps the reference's
 tensor-level form for use under the unmodified reference Trainer; the fused training kernel applies the same
 regulariser from registers."""
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -378,6 +379,81 @@ class ConvKB(PointwiseModel):
 
     def forward(self, h, r, t):
         return torch.ops.kge.convkb_score(self._kge_op_key, h, r, t, self.trainable_tensors())
+
+    def kernel_lmbda(self):
+        return 0.0
+
+    def kernel_reg_type(self, reg_type=None):
+        return L.REG_NONE
+
+
+class MuRP(PointwiseModel):
+    """pointwise.py:1004-1133, float64 throughout.  preds = -(d(u_m, v_m)^2 - bs[h] - bo[t]) with u_m the head mapped to the tangent
+    space, scaled by wu[r] and mapped back, v_m = p_sum(t, r), all through the reference's own maps (csrc/kge_murp.hip):
+    arsech(x) = log((1 + sqrt(1 - x^2)) / x) where the Poincare ball has artanh, 1 / cosh where it has tanh.  They are what the
+    reference's checkpoints were trained with and are kept.  preds is a logit (higher = more plausible); the loss is BCE-with-logits.
+
+    Tables, names, dtypes, padding_idx and the order of the random draws are the reference's, so the initial state under given torch
+    and numpy seeds is bit-identical to it.  state_dict order: wu, bs, bo, ent_embeddings.weight, rel_embeddings.weight;
+    parameter_list holds the two embeddings only; all five are trained (trainable_tensors).  `lmbda` is required and unused.
+
+    rank_order (class attribute, default 0; set it on an instance): the order predict_*_rank lists and the Evaluator's ranks use.
+    0 = ascending score, as the reference's predict_*_rank return them (the least plausible candidate first): a rank is the true
+    entity's position in that list.  1 = most plausible first.  The reference's MetricCalculator walks a list from its END, so the
+    metrics the reference reports for MuRP are the rank_order = 1 ranks.  topk is ignored, as in the reference: the lists are full."""
+    kernel_name = "murp"
+    rank_order = 0
+
+    def __init__(self, **kwargs):
+        super().__init__(self.__class__.__name__.lower())
+        self.__dict__.update(self.load_params(["tot_entity", "tot_relation", "hidden_size", "lmbda"], kwargs))
+        k = self.hidden_size
+        self.device = kwargs["device"]
+        # (the draws in the reference's order: each nn.Embedding draws its own fp32 init before its data is replaced)
+        self.ent_embeddings = NamedEmbedding("ent_embedding", self.tot_entity, k, padding_idx=0)
+        self.ent_embeddings.weight.data = 1e-3 * torch.randn((self.tot_entity, k), dtype=torch.double, device=self.device)
+        self.rel_embeddings = NamedEmbedding("rel_embedding", self.tot_relation, k, padding_idx=0)
+        self.rel_embeddings.weight.data = 1e-3 * torch.randn((self.tot_relation, k), dtype=torch.double, device=self.device)
+        self.wu = nn.Parameter(torch.tensor(np.random.uniform(-1, 1, (self.tot_relation, k)), dtype=torch.double, requires_grad=True,
+                                            device=self.device))
+        self.bs = nn.Parameter(torch.zeros(self.tot_entity, dtype=torch.double, requires_grad=True, device=self.device))
+        self.bo = nn.Parameter(torch.zeros(self.tot_entity, dtype=torch.double, requires_grad=True, device=self.device))
+        self.parameter_list = [self.ent_embeddings, self.rel_embeddings]
+        self.loss = Criterion.pointwise_bce
+
+    def trainable_tensors(self):
+        return [self.wu, self.bs, self.bo, self.ent_embeddings.weight, self.rel_embeddings.weight]
+
+    def make_desc(self, weights=None, grads=None):
+        if weights is None:
+            weights = self.trainable_tensors()
+        return K.murp_desc(list(weights), None if grads is None else list(grads), tot_entity=self.tot_entity,
+                           tot_relation=self.tot_relation, dim=self.hidden_size, rank_order=self.rank_order)
+
+    def embed(self, h, r, t):
+        return self.ent_embeddings(h), self.rel_embeddings(r), self.ent_embeddings(t)
+
+    def forward(self, h, r, t):
+        return torch.ops.kge.murp_score(self._kge_op_key, h, r, t, self.trainable_tensors())
+
+    def _ranked(self, scores):
+        # (stable: candidates that tie -- rows saturated at the last clamp -- keep their id order, in either direction)
+        return torch.sort(scores, descending=bool(self.rank_order), stable=True)[1]
+
+    def predict_tail_rank(self, h, r, topk=-1):
+        del topk
+        return self._ranked(self._sweep(h, r, torch.zeros_like(h), 0))
+
+    def predict_head_rank(self, t, r, topk=-1):
+        del topk
+        return self._ranked(self._sweep(torch.zeros_like(t), r, t, 1))
+
+    def predict_rel_rank(self, h, t, topk=-1):
+        del topk
+        rel = torch.arange(self.tot_relation, dtype=torch.int64, device=h.device)
+        with torch.no_grad():
+            return self._ranked(K.murp_score_forward(self.make_desc(), h.view(-1)[:1].expand(rel.numel()).contiguous(), rel,
+                                                     t.view(-1)[:1].expand(rel.numel()).contiguous()))
 
     def kernel_lmbda(self):
         return 0.0

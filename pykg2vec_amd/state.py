@@ -49,9 +49,12 @@ class FlatState:
     reduce-scatter(grad) -> optimiser on 1/N of the tables -> all-gather(param).  Same bytes on the wire as an
     all-reduce, 1/N of the optimiser sweep (the B-independent part of the step) and of its state memory."""
 
-    def __init__(self, model, optimizer, backend=K, world_size=1, rank=0, distributed=None, replicate_optimizer=False):
+    def __init__(self, model, optimizer, backend=K, world_size=1, rank=0, distributed=None, replicate_optimizer=False,
+                 dtype=torch.float32):
         """replicate_optimizer (data parallel with the sparse gradient exchange, Trainer._sparse_dp): every rank keeps the optimiser
-        state of ALL rows and steps all of them, so no parameter all-gather exists -- the shard is the whole buffer."""
+        state of ALL rows and steps all of them, so no parameter all-gather exists -- the shard is the whole buffer.
+        dtype: the element type of the flat buffers (MuRP: torch.float64; offsets are counted in elements, so segments stay 16-byte
+        aligned)."""
         self.K = backend
         # distributed (default: world_size > 1): the step goes through the collectives and needs a reduce-scatter target that
         # is distinct from the local gradient buffer -- also at world size 1 when a process group was given explicitly
@@ -71,8 +74,8 @@ class FlatState:
         self.replicate_optimizer = bool(replicate_optimizer)
         self.shard_numel = tot if replicate_optimizer else tot // world_size
         self.shard_lo = 0 if replicate_optimizer else rank * self.shard_numel
-        self.param = torch.zeros(tot, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.param = torch.zeros(tot, dtype=dtype, device=dev)
+        self.grad = torch.zeros(tot, dtype=dtype, device=dev)
         self.views, self.grad_views = [], []
         for p, o in zip(params, offs):
             v = self.param[o:o + p.numel()].view_as(p)
@@ -83,7 +86,7 @@ class FlatState:
         self.optimizer = optimizer
         self.param_shard = self.param[self.shard_lo:self.shard_lo + self.shard_numel]
         # reduced gradient of this rank's shard: the full buffer itself when there is nothing to reduce
-        self.grad_shard = self.grad if (not distributed or replicate_optimizer) else torch.zeros(self.shard_numel, dtype=torch.float32, device=dev)
+        self.grad_shard = self.grad if (not distributed or replicate_optimizer) else torch.zeros(self.shard_numel, dtype=dtype, device=dev)
         self.state1 = torch.zeros_like(self.param_shard) if optimizer in ("adam", "adagrad", "rms") else None
         self.state2 = torch.zeros_like(self.param_shard) if optimizer == "adam" else None
         self.step = 0

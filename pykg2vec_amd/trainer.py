@@ -116,20 +116,26 @@ class Trainer:
     def build_model(self, monitor=Monitor.FILTERED_MEAN_RANK):
         if self._projection():
             self._refuse_projection()
-        if self.config.optimizer not in K.OPTIMIZER_IDS:  # sgd / adam / adagrad / rms (utils/trainer.py:112-131)
+        murp = self._murp()
+        if murp:   # float64 tables stepped by kge_murp_rsgd_step: the Poincare update, or plain SGD (utils/trainer.py:132-138)
+            if self.config.optimizer not in ("riemannian", "sgd"):
+                raise NotImplementedError("MuRP: the %s optimizer is not supported (riemannian and sgd only)" % self.config.optimizer)
+        elif self.config.optimizer not in K.OPTIMIZER_IDS:  # sgd / adam / adagrad / rms (utils/trainer.py:112-131)
             raise NotImplementedError("No support for %s optimizer" % self.config.optimizer)
         self.model.to(self.config.device)
         if self.distributed:
             self._refuse_convkb("data-parallel training")
+        if murp and self.use_graph:
+            self._refuse_convkb("hipGraph capture of the step")
         for switch, what in (("pw_pull", "the owner-computes step (KGE_PW_PULL=1)"), ("staged", "the staged step (KGE_STAGED=1)")):
             if self.switches.get(switch):
                 self._refuse_convkb(what)
         self._sparse_dp = self._sparse_dp_wanted()
         self._dp_allreduce = (not self._sparse_dp) and self._dp_allreduce_wanted()
         self.flat = FlatState(self.model, self.config.optimizer, self.K, self.world_size, self.rank, self.distributed,
-                              replicate_optimizer=self._sparse_dp or self._dp_allreduce)
+                              replicate_optimizer=self._sparse_dp or self._dp_allreduce, **({"dtype": torch.float64} if murp else {}))
         self.evaluator = Evaluator(self.model, self.config, backend=self.K)
-        self.loss_buf = self.K.new_loss_buffer(self.flat.param.device)
+        self.loss_buf = self.K.murp_new_loss(self.flat.param.device) if murp else self.K.new_loss_buffer(self.flat.param.device)
         self.monitor = monitor
         if self.early_stopper is None:   # utils/trainer.py:143 (config.patience is hard-wired to 3 there, config.py:55)
             self.early_stopper = PatienceStopper(getattr(self.config, "patience", -1), monitor)
@@ -142,9 +148,19 @@ class Trainer:
 
     def _refuse_convkb(self, what):
         """ConvKB trains through the fused atomic-scatter step on one GPU (csrc/kge_convkb.hip): its flat buffer carries fc1 next to the
-        tables and its descriptor is not a kge_model_desc, which the other step forms and the gradient exchange assume."""
+        tables and its descriptor is not a kge_model_desc, which the other step forms and the gradient exchange assume.  MuRP
+        (csrc/kge_murp.hip) likewise: float64 buffers, wu / bs / bo next to the tables, a descriptor and an optimiser of its own."""
         if getattr(self.model, "kernel_name", None) == "convkb":
             raise NotImplementedError("ConvKB: %s is not supported (single-GPU fused step only)" % what)
+        if self._murp():
+            raise NotImplementedError("MuRP: %s is not supported (single-GPU fused step only)" % what)
+
+    def _murp(self):
+        return getattr(self.model, "kernel_name", None) == "murp"
+
+    def _read_loss(self):
+        """The accumulated loss as a device scalar (no sync): the fp32 striped buffer, or MuRP's float64 accumulator."""
+        return self.loss_buf.sum() if self._murp() else self.K.read_loss(self.loss_buf)
 
     def _mark(self, name):
         """Per-phase timing of the multi-GPU step (bench.py --gpus N): an event on the current stream at a phase boundary.  The
@@ -207,6 +223,8 @@ class Trainer:
         """Sampler + scoring + logistic loss + backward in one kernel for the pointwise models (a bundle's negatives
         must fit one lane group)."""
         if not (self.K is K and self.model.training_strategy == TrainingStrategy.POINTWISE_BASED):
+            return False
+        if self._murp():    # ids come from the device sampler: the yaml's neg_rate 50 exceeds a lane group (csrc/kge_murp.hip)
             return False
         group = 32 if self.model.hidden_size <= 256 else 64
         if self.model.kernel_name in ("octonione", "convkb"):   # the bundle's positive holds a lane of the group too (csrc/kge_octonion.hip)
@@ -278,6 +296,9 @@ class Trainer:
 
     def _accumulate_pointwise(self, h, r, t, y):
         # rows arrive as bundles [positive, its neg_rate negatives] (generator / data/generator.py:125-156)
+        if isinstance(self._desc, K.L.MurpDesc):   # BCE-with-logits on clamp(y, 0, 1), float64 (kge_murp_train_bce)
+            self.K.murp_train_bce(self._desc, h, r, t, y, self.loss_buf)
+            return
         self.K.train_pointwise_logistic(self._desc, h, r, t, y, self.model.kernel_lmbda(), self.model.kernel_reg_type(),
                                         self.loss_buf, bundle=1 + int(self.config.neg_rate))
 
@@ -690,6 +711,8 @@ class Trainer:
         """Name of the path that serves the next n batches (STEP_PATHS)."""
         if self._projection():
             return "generic"
+        if self._murp():     # sampler launch + kge_murp_train_bce + kge_murp_rsgd_step, eager
+            return "murp"
         full = n > 0 and self.generator is not None and \
             self.generator._batch_idx + n <= self.generator.n_train // int(self.config.batch_size)
         for name, pred, needs_full in self.STEP_PATHS:
@@ -882,6 +905,10 @@ class Trainer:
         flat = self.flat
 
         def optimise():
+            if self._murp():   # one launch over all five tensors; it clears the gradients it consumed
+                flat.step += 1
+                self.K.murp_rsgd_step(self._desc, self.config.learning_rate, riemannian=self.config.optimizer == "riemannian")
+                return
             if self._rescal_fused():
                 # RESCAL, single GPU: the optimiser stores the entity rows already renormalised for the next step's forward
                 # (kge_optimizer_step_rows) and the relation matrices are renormalised right behind it, so the next step skips its
@@ -976,7 +1003,7 @@ class Trainer:
     def train_step_pointwise(self, h, r, t, target):
         self.loss_buf.zero_()
         self._accumulate_pointwise(h, r, t, target)
-        return self.K.read_loss(self.loss_buf)
+        return self._read_loss()
 
     def train_step_projection(self, h, r, t, hr_t_csr, tr_h_csr, neg=None):
         """utils/trainer.py:159-174 with the label rows as CSR pairs (off int64 [B + 1], ids int32) and, for ProjE_pointwise, the batch's
@@ -992,6 +1019,10 @@ class Trainer:
         if num_batch is not None and num_batch * int(self.config.batch_size) > self.generator.n_train:
             return False
         if self.K is not K or self._projection():
+            return False
+        if self._murp():
+            if self.use_graph:
+                self._refuse_convkb("hipGraph capture of the step")
             return False
         if self.switches["staged"] and self._staged_ok():   # the staged step is an eager two-launch step
             return False
@@ -1121,7 +1152,7 @@ class Trainer:
                 self._pull_state()[0].sync_in()   # the tables may have been changed from outside since the last epoch
             self.step_next_batches(num_batch)
             self.sync_model()
-        acc = self.K.read_loss(self.loss_buf)
+        acc = self._read_loss()
         if self.distributed:
             torch.distributed.all_reduce(acc, group=self.process_group)
             if self._mean_type_loss():
