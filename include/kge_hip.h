@@ -121,6 +121,24 @@ int kge_filter_csr_count(const int64_t* known, int64_t n_known, const int64_t* q
 int kge_filter_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_known, const void* workspace, const int64_t* tail_off,
                         const int64_t* head_off, int32_t* tail_ids, int32_t* head_ids, void* stream);
 
+/* ---- row select of the batched link prediction (kge_topk.hip): the k most plausible live candidates of every score row.
+ * scores: float32 (dtype 0) or float64 (dtype 1) [nq, row_stride], of which the first n_cand elements of each row are candidates
+ * (the rest is never read).  Row q's output holds the first min(k, live_q) live candidates of ONE total order: better score first
+ * (the lower one with largest == 0, the higher one with largest == 1), lower candidate id first among equal scores; -0.0 equals
+ * +0.0; NaN is worse than every number in both directions, NaNs ordered by id.  The result is an exact function of the inputs.
+ * Mask: candidate c of row q is live unless c is in skip_ids[skip_off[q] .. skip_off[q+1]) and c != keep[q]; the lists may be
+ * unsorted and hold duplicates, keep[q] or ids outside [0, n_cand) (ignored).  skip_off == NULL: nothing is masked; keep may be NULL.
+ * out_ids int32 [nq, k], out_scores [nq, k] (the bit patterns of scores[q, out_ids[q, j]]), out_count int32 [nq] = min(k, live_q);
+ * places from out_count[q] on hold id -1 and a NaN score.  workspace: kge_topk_workspace_bytes(nq, n_cand, masked) bytes, 0 without
+ * a mask.  Refused before any GPU call, kge_last_error() naming the argument: k outside 1..KGE_TOPK_MAX, n_cand < 1, a dtype other
+ * than 0 / 1, row_stride < n_cand, skip_off without skip_ids, a workspace that is too small.  The number of launches does not
+ * depend on nq. */
+#define KGE_TOPK_MAX 1024
+size_t kge_topk_workspace_bytes(int64_t nq, int64_t n_cand, int masked);
+int kge_topk_rows(const void* scores, int dtype, int64_t nq, int64_t n_cand, int64_t row_stride, int32_t k, int largest,
+                  const int64_t* skip_off, const int32_t* skip_ids, const int64_t* keep, void* workspace, size_t workspace_bytes,
+                  int32_t* out_ids, void* out_scores, int32_t* out_count, void* stream);
+
 /* An empty kernel launch of `tag` workgroups of 64 threads ("kge::k_marker"): a boundary that shows up in a rocprofv3 kernel /
  * counter trace.  bench.py's counter passes use it to cut one process's dispatch sequence into per-configuration segments. */
 int kge_debug_marker(int32_t tag, void* stream);

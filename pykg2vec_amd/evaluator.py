@@ -5,6 +5,9 @@ test_head_rank` and `metric_calculator.{reset,settle,get_curr_scores,display_sum
 and dict fields, but `test()` ranks ALL requested triples in one kge_eval_ranks call: no per-triple id tensors, no
 topk sort, no ordering copied to the host, no python rank loop.  The hr_t / tr_h dict-of-set caches are flattened
 once into per-query CSR lists on the device.
+
+Beyond the reference: `predict_tails / predict_heads / predict_rels` answer many queries per call, most plausible first, with
+the known triples optionally left out (Model.score_rows + kernels.topk_rows); Trainer.infer_* is served by them.
 """
 import os
 import timeit
@@ -13,6 +16,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .kgmeta import ProjectionModel
 
 
 def _log(msg):
@@ -190,6 +194,95 @@ class Evaluator:
         _, rank = torch.topk(preds, k=topk)
         return rank
 
+    # --- batched link prediction: many queries per call, most plausible first, known triples optionally left out
+    PREDICT_SCRATCH_BYTES = 256 << 20   # bound of the score rows held at once; a chunk is at least one row
+    PREDICT_ROW_ITEM_BYTES = 8          # budgeted per score: float64 rows (MuRP), or the two float32 sides TransR / NTN / SLM sweep
+
+    def _ids_arg(self, x, what):
+        dev = self.config.device
+        t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise TypeError("%s must be integer ids" % what)
+        return t.reshape(-1).to(device=dev, dtype=torch.int64)
+
+    def _topk_arg(self, topk):
+        topk = int(topk)
+        if not 1 <= topk <= K.TOPK_MAX:
+            raise ValueError("topk = %d outside 1..%d (KGE_TOPK_MAX)" % (topk, K.TOPK_MAX))
+        return topk
+
+    def _select_chunks(self, n, n_cand, topk, rows_of, skip=None, keep=None):
+        """rows_of(a, b) -> [b - a, n_cand] score rows of queries a..b; each chunk goes through topk_rows into ONE pair of output
+        tensors.  Nothing in the loop reads the device."""
+        dev = self.config.device
+        ids = torch.empty((n, topk), dtype=torch.int64, device=dev)
+        vals = None
+        per = int(max(1, self.PREDICT_SCRATCH_BYTES // (self.PREDICT_ROW_ITEM_BYTES * n_cand)))
+        for a in range(0, n, per):
+            b = min(n, a + per)
+            rows = rows_of(a, b)
+            kw = {}
+            if skip is not None:   # the chunk's offsets stay absolute: they index the whole id array
+                kw = dict(skip_off=skip[0][a:b + 1], skip_ids=skip[1], keep=None if keep is None else keep[a:b])
+            i, v, _ = self.K.topk_rows(rows, topk, largest=bool(self.model.higher_is_better), **kw)
+            if vals is None:
+                vals = torch.empty((n, topk), dtype=v.dtype, device=dev)
+            ids[a:b] = i
+            vals[a:b] = v
+        if vals is None:
+            vals = torch.empty((0, topk), dtype=torch.float32, device=dev)
+        return ids, vals
+
+    def _predict_entities(self, e, r, side, topk, filtered, keep):
+        topk = self._topk_arg(topk)
+        e, r = self._ids_arg(e, "tails" if side else "heads"), self._ids_arg(r, "relations")
+        if e.numel() != r.numel():
+            raise ValueError("%d entities for %d relations: one pair per query" % (e.numel(), r.numel()))
+        n = int(e.numel())
+        zero = torch.zeros_like(e)   # the swept column: a placeholder id
+        queries = torch.stack([zero, r, e] if side else [e, r, zero], 1).contiguous()
+        skip = None
+        if keep is not None:
+            keep = self._ids_arg(keep, "keep")
+            if keep.numel() != n:
+                raise ValueError("keep holds %d ids for %d queries" % (keep.numel(), n))
+        if filtered and n:
+            _, csr = self._filter_csr(queries.cpu().numpy(), queries)
+            skip = (csr[2], csr[3]) if side else (csr[0], csr[1])
+        return self._select_chunks(n, int(self.config.tot_entity), topk, lambda a, b: self.model.score_rows(queries[a:b], side), skip,
+                                   keep if skip is not None else None)
+
+    def predict_tails(self, h, r, topk=10, filtered=False, keep=None):
+        """(ids int64 [n, topk], scores [n, topk]): the topk most plausible tails of every (h_i, r_i), most plausible first, equal
+        scores by ascending id (kge_topk_rows).  h, r: ints, sequences or tensors of equal length.  filtered: the tails known for
+        (h_i, r_i) in train + valid + test are left out, except keep[i] (an entity id per query: the true answer of a test triple).
+        Rows with fewer than topk live candidates are padded with id -1 and a NaN score."""
+        return self._predict_entities(h, r, 0, topk, filtered, keep)
+
+    def predict_heads(self, r, t, topk=10, filtered=False, keep=None):
+        """predict_tails for the heads of every (·, r_i, t_i)."""
+        return self._predict_entities(t, r, 1, topk, filtered, keep)
+
+    def predict_rels(self, h, t, topk=10):
+        """(ids int64 [n, topk], scores [n, topk]): the topk most plausible relations of every (h_i, ·, t_i), all relations scored
+        through the batch scorer.  The 1-N models' forward scores entities: they are refused, as the reference has no relation
+        inference for them either."""
+        if isinstance(self.model, ProjectionModel):
+            raise ValueError("predict_rels: %s is a projection model, whose forward scores entities, not relations"
+                             % type(self.model).__name__)
+        topk = self._topk_arg(topk)
+        h, t = self._ids_arg(h, "heads"), self._ids_arg(t, "tails")
+        if h.numel() != t.numel():
+            raise ValueError("%d heads for %d tails: one pair per query" % (h.numel(), t.numel()))
+        R = int(self.config.tot_relation)
+        rel = torch.arange(R, dtype=torch.int64, device=h.device)
+
+        def rows_of(a, b):
+            with torch.no_grad():
+                return self.model.forward(h[a:b].repeat_interleave(R), rel.repeat(b - a), t[a:b].repeat_interleave(R)).view(b - a, R)
+
+        return self._select_chunks(int(h.numel()), R, topk, rows_of)
+
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))
         if self.config.debug:
@@ -300,6 +393,28 @@ class Evaluator:
             return "triples"
         return "dicts"
 
+    def _filter_csr(self, trip, trip_dev):
+        """(source, (tail_off, tail_ids, head_off, head_ids)) of the triples `trip` (host array) = `trip_dev` (device tensor): the
+        known tails of every (h, r) and the known heads of every (t, r) over train + valid + test, from _filter_source()."""
+        mc = self.metric_calculator
+        dev = trip_dev.device
+        source = self._filter_source()
+        if source == "triples":   # sort + binary search on the device (csrc/kge_index.hip)
+            known = self._known_triples()
+            if known is None:
+                raise K.L.KgeHipError("Evaluator: the knowledge-graph cache carries neither hr_t / tr_h nor the three splits")
+            csr = self.K.filter_csr_build(known, trip_dev, self.config.tot_entity, self.config.tot_relation)
+            if trip_dev.is_cuda:
+                torch.cuda.synchronize(dev)
+        elif source == "dicts":
+            csr = tuple(torch.from_numpy(a).to(dev) for a in build_filter_csr(trip, mc.hr_t, mc.tr_h))
+        else:  # host arrays without a device backend (CPU tests of the plumbing)
+            kg = self.config.knowledge_graph
+            known = np.concatenate([_as_array(kg.read_cache_data(k), None) for k in
+                                    ('triplets_train', 'triplets_valid', 'triplets_test')])
+            csr = tuple(torch.from_numpy(a).to(dev) for a in build_filter_csr_from_triples(trip, known, self.config.tot_relation))
+        return source, tuple(csr)
+
     def _device_inputs(self, data, n):
         import time
         key = self._fingerprint(data, n)
@@ -313,25 +428,10 @@ class Evaluator:
                 nd = int(dense.sum())
                 cuts = np.concatenate([[0], np.flatnonzero(np.diff(trip[:nd, 1])) + 1, [nd]]).astype(np.int64)
                 self._groups[key] = (order, self._group_chunks(trip, cuts), nd)
-            mc = self.metric_calculator
             dev = next(self.model.parameters()).device
-            source = self._filter_source()
             trip_dev = torch.from_numpy(trip).to(dev)
             t1 = time.perf_counter()
-            if source == "triples":   # sort + binary search on the device (csrc/kge_index.hip)
-                known = self._known_triples()
-                if known is None:
-                    raise K.L.KgeHipError("Evaluator: the knowledge-graph cache carries neither hr_t / tr_h nor the three splits")
-                csr = self.K.filter_csr_build(known, trip_dev, self.config.tot_entity, self.config.tot_relation)
-                if trip_dev.is_cuda:
-                    torch.cuda.synchronize(dev)
-            elif source == "dicts":
-                csr = tuple(torch.from_numpy(a).to(dev) for a in build_filter_csr(trip, mc.hr_t, mc.tr_h))
-            else:  # host arrays without a device backend (CPU tests of the plumbing)
-                kg = self.config.knowledge_graph
-                known = np.concatenate([_as_array(kg.read_cache_data(k), None) for k in
-                                        ('triplets_train', 'triplets_valid', 'triplets_test')])
-                csr = tuple(torch.from_numpy(a).to(dev) for a in build_filter_csr_from_triples(trip, known, self.config.tot_relation))
+            source, csr = self._filter_csr(trip, trip_dev)
             t2 = time.perf_counter()
             self.setup_stats = {"csr_ms": (t2 - t1) * 1e3, "csr_source": source, "queries": int(trip.shape[0]),
                                 "host_prepare_ms": (t1 - t0) * 1e3, "filter_ids": int(csr[1].numel() + csr[3].numel())}

@@ -883,6 +883,59 @@ def filter_csr_build(known, queries, tot_entity, tot_relation):
     return t_off, t_ids, h_off, h_ids
 
 
+TOPK_MAX = L.TOPK_MAX
+
+
+def topk_rows(scores, k, largest=False, skip_off=None, skip_ids=None, keep=None):
+    """The k most plausible live candidates of every row of `scores` (float32 or float64 [nq, n_cand], unit inner stride, any row
+    stride >= n_cand): (ids int32 [nq, k], values [nq, k], count int32 [nq]) in kge_topk_rows's total order -- better score first
+    (lower unless `largest`), lower id first among equal scores, NaN last.  Candidate c of row q is masked when it is in
+    skip_ids[skip_off[q] : skip_off[q + 1]] (int32 ids, int64 offsets [nq + 1]) and differs from keep[q] (int64 [nq], optional);
+    rows with fewer than k live candidates are padded with id -1 and NaN."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise TypeError("scores must be a 2-D tensor")
+    if scores.dtype not in (torch.float32, torch.float64):
+        raise TypeError("scores must be float32 or float64 (got %s)" % scores.dtype)
+    if not scores.is_cuda:
+        raise L.KgeHipError("scores must live on the HIP device (got %s); the HIP path has no CPU fallback" % scores.device)
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError("k = %d outside 1..%d (KGE_TOPK_MAX)" % (k, TOPK_MAX))
+    nq, n_cand = (int(x) for x in scores.shape)
+    if n_cand > 1 and scores.stride(1) != 1:
+        raise ValueError("scores must have unit inner stride (got %d)" % scores.stride(1))
+    row_stride = int(scores.stride(0)) if nq > 1 else n_cand
+    dev = scores.device
+    ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    vals = torch.empty((nq, k), dtype=scores.dtype, device=dev)
+    count = torch.empty(nq, dtype=torch.int32, device=dev)
+    if nq == 0:
+        return ids, vals, count
+    if (skip_off is None) != (skip_ids is None):
+        raise ValueError("skip_off and skip_ids come together")
+    lib = L.load()
+    po = pi = pk = pw = None
+    nbytes = 0
+    if skip_off is not None:
+        if skip_off.numel() != nq + 1:
+            raise ValueError("skip_off must hold nq + 1 = %d offsets (got %d)" % (nq + 1, skip_off.numel()))
+        po = _dev(skip_off, torch.int64, "skip_off")
+        if skip_ids.numel() == 0:   # every list is empty: a pointer the library accepts, never read
+            skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+        pi = _dev(skip_ids, torch.int32, "skip_ids")
+        if keep is not None:
+            if keep.numel() != nq:
+                raise ValueError("keep must hold one id per row (%d, got %d)" % (nq, keep.numel()))
+            pk = _dev(keep, torch.int64, "keep")
+        nbytes = lib.kge_topk_workspace_bytes(nq, n_cand, 1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        pw = ctypes.c_void_p(ws.data_ptr())
+    L.check(lib.kge_topk_rows(ctypes.c_void_p(scores.data_ptr()), 1 if scores.dtype == torch.float64 else 0, nq, n_cand, row_stride, k,
+                              1 if largest else 0, po, pi, pk, pw, nbytes, _dev(ids, torch.int32, "out_ids"),
+                              ctypes.c_void_p(vals.data_ptr()), _dev(count, torch.int32, "out_count"), _stream()), "kge_topk_rows")
+    return ids, vals, count
+
+
 def triple_set_build(triples):
     """Open-addressing hash set of the train triples (uint64 slots, power of two >= 2n)."""
     n = triples.shape[0]

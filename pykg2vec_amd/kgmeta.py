@@ -74,6 +74,28 @@ class Model:
         trip = torch.stack([h0, r0, t0]).view(1, 3).contiguous()
         return K.eval_sweep_scores_side(self.make_desc(), trip, side)[0]
 
+    higher_is_better = False   # what forward() / score_rows return: an energy (lower = more plausible) or a logit / probability
+
+    def score_rows(self, queries, side):
+        """[n, E] scores of int64 `queries` [n, 3] against every entity e, no gradient, the model's evaluation form: side 0 scores
+        (h_i, r_i, e), side 1 scores (e, r_i, t_i); the id in the swept column is a placeholder.  Rows may be a strided view.
+        The one place the batched link prediction (Evaluator.predict_*) gets its rows from."""
+        assert side in (0, 1), "side 0 = tails, 1 = heads"
+        queries = queries.contiguous()
+        with torch.no_grad():
+            if self.kernel_name == "rescal":   # the reference's forward renormalises both tables during eval too, as rank_all does
+                K.rescal_normalize(self.ent_embeddings.weight.data, self.rel_matrices.weight.data, self.hidden_size)
+            desc = self.make_desc()
+            if self.kernel_name != "transr":
+                return K.eval_sweep_scores_side(desc, queries, side)
+            # TransR's sweep projects the candidates by ONE relation matrix per call: a call per relation (one host read of the
+            # distinct relations), rows scattered back
+            out = torch.empty((queries.shape[0], int(self.tot_entity)), dtype=torch.float32, device=queries.device)
+            for rel in torch.unique(queries[:, 1]).tolist():
+                idx = torch.nonzero(queries[:, 1] == rel).view(-1)
+                out[idx] = K.eval_sweep_scores_side(desc, queries[idx].contiguous(), side)
+            return out
+
     def predict_tail_rank(self, h, r, topk=-1):
         _, rank = torch.topk(self._sweep(h, r, torch.zeros_like(h), 0), k=topk)
         return rank.view(1, -1)
@@ -112,6 +134,22 @@ class ProjectionModel(nn.Module, Model):
     __setstate__ = Model._restore
     dropout_in_eval = False   # True: the model draws its dropout masks whatever the module's mode
     label_negatives = False   # True: the loss reads sampled negatives as -1 labels (the generator draws them); else neg_rate > 0 is refused
+    higher_is_better = True   # forward() / score_rows return sigmoid probabilities
+
+    def _eval_body(self, e, r, side):
+        """x [n, k]: the model's body in evaluation form (no dropout, running statistics) whatever self.training says; nothing is
+        drawn and dropout_offset does not move."""
+        raise NotImplementedError("%s has no evaluation body" % type(self).__name__)
+
+    def _head_bias(self):
+        return None
+
+    def score_rows(self, queries, side):
+        """Model.score_rows for the 1-N models: the evaluation-form body of (h_i, r_i) (side 0) or (t_i, r_i) (side 1) + the head."""
+        assert side in (0, 1), "side 0 = tails, 1 = heads"
+        e, r = queries[:, 2 if side else 0].contiguous(), queries[:, 1].contiguous()
+        with torch.no_grad():
+            return torch.ops.kge.one_to_n_scores(self._eval_body(e, r, side), self.ent_embeddings.weight, self._head_bias(), False)
 
     def fused_projection_step(self, K, desc, h, r, t, hr_t_csr, tr_h_csr, neg, config, loss_buf):
         """One training step in ONE library call: adds to loss_buf and to the descriptor's gradients.  hr_t_csr / tr_h_csr: the

@@ -403,6 +403,7 @@ class MuRP(PointwiseModel):
     metrics the reference reports for MuRP are the rank_order = 1 ranks.  topk is ignored, as in the reference: the lists are full."""
     kernel_name = "murp"
     rank_order = 0
+    higher_is_better = True   # preds is a logit; rank_order does not enter the batched link prediction
 
     def __init__(self, **kwargs):
         super().__init__(self.__class__.__name__.lower())

@@ -62,6 +62,9 @@ class TuckER(ProjectionModel):
         x, _saved = torch.ops.kge.tucker_body(self._kge_op_key, e1, r, self.dropout_seed, offset, self.trainable_tensors())
         return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, None, False)
 
+    def _eval_body(self, e, r, side):
+        return torch.ops.kge.tucker_body(self._kge_op_key, e, r, self.dropout_seed, -1, self.trainable_tensors())[0]
+
     def predict_tail_rank(self, e, r, topk=-1):
         _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
         return rank
@@ -129,6 +132,10 @@ class Conv1NModel(ProjectionModel):
         if self.training:
             self._count_batches(1)
         return torch.ops.kge.one_to_n_scores(x, self.ent_embeddings.weight, self._head_bias(), False)
+
+    def _eval_body(self, e, r, side):
+        body = getattr(torch.ops.kge, self.kernel_name + "_body")
+        return body(self._kge_op_key, e, r, self._direction("head" if side else "tail", e), self.dropout_seed, -1, self.trainable_tensors())[0]
 
     def predict_tail_rank(self, e, r, topk=-1):
         _, rank = torch.topk(-self.forward(e, r, direction="tail"), k=topk)
@@ -460,6 +467,9 @@ class ProjE_pointwise(ProjectionModel):
 
     def _body(self, e, r, side, offset):
         return torch.ops.kge.proje_body(self._kge_op_key, e, r, side, self.dropout_seed, offset, self.trainable_tensors())
+
+    def _eval_body(self, e, r, side):
+        return self._body(e, r, side, -1)
 
     def forward(self, e, r, er_e2, direction="tail"):
         assert direction in ("head", "tail"), "Unknown forward direction"

@@ -1168,6 +1168,45 @@ class Trainer:
             gen.pull_segment = min(32, 256 // max(1, self.K.pull_groups_per_block(self.model.hidden_size)))
         return gen
 
+    # ------------------------------------------------------------------ inference (utils/trainer.py:330-386)
+    def _infer(self, ids, names, header, lines, what):
+        """The reference's log block and its insertion-ordered {id: name} dict for one query's predictions (padding ids dropped)."""
+        ids = [int(i) for i in ids.view(-1).tolist() if int(i) >= 0]
+        logs = ["", "%s :: Inferred %ss->(%s)" % (header, what, ",".join(str(i) for i in ids)), ""] + lines
+        logs += ["%dth predicted %s: %s" % (k, what, names[i]) for k, i in enumerate(ids)]
+        _log("\n".join(logs))
+        return {i: names[i] for i in ids}
+
+    def infer_tails(self, h, r, topk=5, filtered=False):
+        """{tail id: name} of the topk most plausible tails of (h, r), most plausible first (the reference lists them from the other
+        end: INTEGRATION.md).  filtered: tails known for (h, r) in train + valid + test are left out."""
+        self.sync_model()
+        kg = self.config.knowledge_graph
+        idx2ent, idx2rel = kg.read_cache_data('idx2entity'), kg.read_cache_data('idx2relation')
+        tails, _ = self.evaluator.predict_tails(h, r, topk=topk, filtered=filtered)
+        return self._infer(tails, idx2ent, "(head, relation)->({},{})".format(h, r), ["head: %s" % idx2ent[h], "relation: %s" % idx2rel[r]],
+                           "tail")
+
+    def infer_heads(self, r, t, topk=5, filtered=False):
+        """infer_tails for the heads of (·, r, t)."""
+        self.sync_model()
+        kg = self.config.knowledge_graph
+        idx2ent, idx2rel = kg.read_cache_data('idx2entity'), kg.read_cache_data('idx2relation')
+        heads, _ = self.evaluator.predict_heads(r, t, topk=topk, filtered=filtered)
+        return self._infer(heads, idx2ent, "(relation,tail)->({},{})".format(t, r), ["tail: %s" % idx2ent[t], "relation: %s" % idx2rel[r]],
+                           "head")
+
+    def infer_rels(self, h, t, topk=5):
+        """{relation id: name} of the topk most plausible relations of (h, ·, t), most plausible first; {} for the projection models."""
+        if self._projection():
+            _log("%s model doesn't support relation inference in nature." % self.model.model_name)
+            return {}
+        self.sync_model()
+        kg = self.config.knowledge_graph
+        idx2ent, idx2rel = kg.read_cache_data('idx2entity'), kg.read_cache_data('idx2relation')
+        rels, _ = self.evaluator.predict_rels(h, t, topk=topk)
+        return self._infer(rels, idx2rel, "(head,tail)->({},{})".format(h, t), ["head: %s" % idx2ent[h], "tail: %s" % idx2ent[t]], "rel")
+
     # ------------------------------------------------------------------ checkpoints (reference format, utils/trainer.py:388-419)
     def _checkpoint_dir(self, path=None):
         if path is not None:
