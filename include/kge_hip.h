@@ -139,6 +139,39 @@ int kge_topk_rows(const void* scores, int dtype, int64_t nq, int64_t n_cand, int
                   const int64_t* skip_off, const int32_t* skip_ids, const int64_t* keep, void* workspace, size_t workspace_bytes,
                   int32_t* out_ids, void* out_scores, int32_t* out_count, void* stream);
 
+/* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
+ * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).
+ * triples int64 [n, 3].  side 0 ranks tails (the candidates replace column 2), side 1 ranks heads (column 0); the true entity
+ * triples[i][2] / triples[i][0] is always a candidate, implicitly.  Lists are a CSR: list l = cand_ids[cand_off[l] .. cand_off[l+1])
+ * (int32 ids, int64 offsets [n_lists + 1]); query i uses list list_of_query[i], or list i when list_of_query is NULL (then
+ * n_lists >= n).  A list entry equal to the true entity is ignored; an entry outside [0, tot_entity) is ignored and its row is never
+ * read (a rectangular [n, C] tensor can be padded with -1); a duplicate id counts as often as it occurs.
+ * counts int32 [4, n], with s_c the score of the triple with candidate c in place and "live" = not ignored:
+ *   counts[0][i] = #{live c in L(i): s_c < s_true}      counts[1][i] = the same over the c not in query i's skip list
+ *   counts[2][i] = #{live c in L(i): s_c == s_true}     counts[3][i] = the same, filtered
+ * 0-based optimistic-end counts, ties bit for bit, a NaN compares false both ways: the convention of kge_eval_ranks_ties.  Without
+ * skip lists (both NULL) rows 1 and 3 equal rows 0 and 2.  The compared scores are the values kge_score_forward returns for the same
+ * (h, r, t), bit for bit; counts are integer sums, so the result does not depend on the execution order.
+ * Skip lists: query i's known entities skip_ids[skip_off[i] .. skip_off[i+1]) (int64 offsets [n + 1]).  PRECONDITION: every segment is
+ * ascending (it is binary-searched; the lists of kge_filter_csr_* are); the debug id mode (kge_set_debug) checks it, and the ids of
+ * `triples` and `list_of_query`.
+ * Models: the row-kernel models (TransE/H/D/M, RotatE, DistMult, ComplEx, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, KG2E); any other
+ * is refused with a message naming the via-forward path (kge_rank_lists_from_scores below).  Refused before any GPU call,
+ * kge_last_error() naming the argument: a null descriptor, side outside {0, 1}, n < 0, only one of skip_off / skip_ids, a workspace
+ * below kge_rank_candidates_workspace_bytes, list_of_query with n_lists <= 0 (or no list_of_query and n_lists < n).  n == 0 returns 0.
+ * KGE_CAND_CHUNK: list entries per work item (one lane group per item); list lengths around its multiples are the edge cases. */
+#define KGE_CAND_CHUNK 64
+size_t kge_rank_candidates_workspace_bytes(int64_t n, int64_t n_lists, int64_t n_cand_ids);
+int kge_rank_candidates(const kge_model_desc* m, const int64_t* triples, int64_t n, int32_t side, const int64_t* list_of_query,
+                        const int64_t* cand_off, const int32_t* cand_ids, int64_t n_lists, const int64_t* skip_off,
+                        const int32_t* skip_ids, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+/* The counting half alone, for scores that come from a model's own batch scorer: segment i = scores[seg_off[i] .. seg_off[i+1])
+ * (float32 with dtype 0, float64 with dtype 1; int64 offsets [n + 1]) holds query i's candidate scores, truth_scores[i] its true
+ * triple's.  flags (one byte per score, or NULL = every score live and kept): bit 0 live, bit 1 live under the filter.  "Better"
+ * is lower with largest == 0 and higher with largest == 1.  counts int32 [4, n] as above (every element is written). */
+int kge_rank_lists_from_scores(const void* scores, int dtype, const void* truth_scores, const int64_t* seg_off, int64_t n,
+                               const uint8_t* flags, int largest, int32_t* counts, void* stream);
+
 /* An empty kernel launch of `tag` workgroups of 64 threads ("kge::k_marker"): a boundary that shows up in a rocprofv3 kernel /
  * counter trace.  bench.py's counter passes use it to cut one process's dispatch sequence into per-configuration segments. */
 int kge_debug_marker(int32_t tag, void* stream);

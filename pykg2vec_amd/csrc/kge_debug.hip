@@ -72,6 +72,20 @@ __global__ void k_check_ids32(const int32_t* __restrict__ ids, int64_t n, int st
     }
 }
 
+// first position j inside a segment [off[i], off[i+1]) with ids[j] < ids[j-1] (the segments must be ascending; equal ids pass)
+__global__ void k_check_ascending(const int64_t* __restrict__ off, const int32_t* __restrict__ ids, int64_t n,
+                                  unsigned long long* __restrict__ first, long long* __restrict__ value) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        for (int64_t j = off[i] + 1; j < off[i + 1]; ++j) {
+            if (ids[j] < ids[j - 1]) {
+                const unsigned long long old = atomicMin(first, (unsigned long long)j);
+                if ((unsigned long long)j < old) *value = ids[j];
+                break;
+            }
+        }
+    }
+}
+
 static BadId* g_flag = nullptr;   // 16 bytes of device memory, allocated on first use in debug mode only
 
 static bool capturing(hipStream_t s) {
@@ -90,6 +104,10 @@ static int run_check(const char* who, const char* what, int64_t bound, hipStream
     if (hipMemcpyAsync(&out, g_flag, sizeof(out), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         set_error("%s: debug id check failed to run: %s", who, hipGetErrorString(hipGetLastError()));
         return -2;
+    }
+    if (out.pos != ~0ull && bound < 0) {
+        set_error("%s: %s segments must be ascending: id %lld at position %llu is below its predecessor", who, what, out.value, out.pos);
+        return -3;
     }
     if (out.pos != ~0ull) {
         set_error("%s: %s id out of range at position %llu: %lld not in [0, %lld) (an nn.Embedding lookup would raise IndexError, "
@@ -120,6 +138,17 @@ int debug_check_ids32(const char* who, const char* what, const int32_t* ids, int
     return run_check(who, what, bound, s, [](void* p, BadId* f, hipStream_t st) {
         const Ctx32& c = *(const Ctx32*)p;
         hipLaunchKernelGGL(k_check_ids32, dim3(grid_for(c.n)), dim3(256), 0, st, c.ids, c.n, c.stride, c.col, c.bound, &f->pos, &f->value);
+    }, &c);
+}
+
+struct CtxAsc { const int64_t* off; const int32_t* ids; int64_t n; };
+
+int debug_check_ascending(const char* who, const char* what, const int64_t* off, const int32_t* ids, int64_t n, hipStream_t s) {
+    if (!debug_ids() || !off || !ids || n <= 0) return 0;
+    CtxAsc c{off, ids, n};
+    return run_check(who, what, -1 /* no bound: the ascending-order message */, s, [](void* p, BadId* f, hipStream_t st) {
+        const CtxAsc& c = *(const CtxAsc*)p;
+        hipLaunchKernelGGL(k_check_ascending, dim3(grid_for(c.n)), dim3(256), 0, st, c.off, c.ids, c.n, &f->pos, &f->value);
     }, &c);
 }
 

@@ -72,6 +72,8 @@ bool debug_ids();
 int debug_check_ids(const char* who, const char* what, const int64_t* ids, int64_t n, int stride, int col, int64_t bound, hipStream_t s,
                     const int64_t* perm = nullptr, int64_t start = 0);
 int debug_check_ids32(const char* who, const char* what, const int32_t* ids, int64_t n, int stride, int col, int64_t bound, hipStream_t s);
+// every segment ids[off[i] .. off[i+1]) ascending (the binary-searched skip lists of kge_rank_candidates)
+int debug_check_ascending(const char* who, const char* what, const int64_t* off, const int32_t* ids, int64_t n, hipStream_t s);
 int debug_check_hrt(const char* who, const kge_model_desc* m, const int64_t* h, const int64_t* r, const int64_t* t, int64_t n, hipStream_t s);
 int debug_check_triples(const char* who, int64_t tot_entity, int64_t tot_relation, const int64_t* triples, int64_t n, hipStream_t s,
                         const int64_t* perm = nullptr, int64_t start = 0);

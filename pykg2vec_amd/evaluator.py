@@ -8,6 +8,8 @@ once into per-query CSR lists on the device.
 
 Beyond the reference: `predict_tails / predict_heads / predict_rels` answer many queries per call, most plausible first, with
 the known triples optionally left out (Model.score_rows + kernels.topk_rows); Trainer.infer_* is served by them.
+`rank_candidates / test_candidates / test_type_constrained / test_sampled` rank every triple against a GIVEN list of candidates
+(fixed negatives, type constraints, sampled ids) instead of all entities (kernels.rank_candidates; CandidateLists below).
 """
 import os
 import timeit
@@ -474,9 +476,13 @@ class Evaluator:
         return (out, ties) if return_ties else out
 
     def test(self, data, num_of_test, epoch=None):
-        mc = self.metric_calculator
-        mc.reset()
+        self.metric_calculator.reset()
         ranks, ties = self.rank_all(data, num_of_test, return_ties=True)
+        return self._settle(ranks, ties, epoch)
+
+    def _settle(self, ranks, ties, epoch):
+        """Ranks [4, n] (+ tie counts [2, n] or None) -> the MetricCalculator's summary dict, with the tie warning."""
+        mc = self.metric_calculator
         ranks = ranks.cpu().numpy()  # the D2H copy: 4*n int32 (+ 2*n tie counts)
         self.tie_counts = ties.cpu().numpy() if ties is not None else None
         if self.tie_counts is not None and (self.tie_counts > 0).any():
@@ -493,3 +499,191 @@ class Evaluator:
         if mc.epoch is not None and mc.epoch >= self.config.epochs - 1:
             mc.save_test_summary(self.model.model_name)
         return mc.get_curr_scores()
+
+    # --- ranking against given candidates: the cost scales with the lists, not with tot_entity
+    ROW_KERNEL_MODELS = frozenset(["transe", "transh", "transd", "transm", "rotate", "distmult", "complex", "analogy", "cp", "simple",
+                                   "simple_ignr", "quate", "kg2e"])                       # the fused kernel (kge_rank_candidates)
+    VIA_FORWARD_MODELS = frozenset(["rescal", "ntn", "transr", "slm", "sme", "sme_bl", "hole", "octonione", "convkb", "murp"])
+    CANDIDATE_ENTRY_BYTES = 48   # budgeted per expanded list entry of the via-forward path: three int64 ids, a score, flags, indices
+
+    def _candidate_lists(self, x, n, what):
+        dev = self.config.device
+        if isinstance(x, CandidateLists):
+            lists = x.to(dev)
+            if lists.list_of_query is None and lists.n_lists < n:
+                raise ValueError("%s: %d lists for %d queries and no list_of_query" % (what, lists.n_lists, n))
+            if lists.list_of_query is not None and lists.list_of_query.numel() < n:
+                raise ValueError("%s: list_of_query holds %d entries for %d queries" % (what, lists.list_of_query.numel(), n))
+            return lists
+        t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.dim() != 2:
+            raise TypeError("%s must be a CandidateLists or an integer [n, C] table (-1 = no entry)" % what)
+        if t.shape[0] < n:
+            raise ValueError("%s holds %d rows for %d queries" % (what, t.shape[0], n))
+        C = int(t.shape[1])
+        return CandidateLists(torch.arange(n + 1, dtype=torch.int64) * C, t[:n].reshape(-1)).to(dev)
+
+    def _rank_side_via_forward(self, trip, side, lists, skip_off, skip_ids):
+        """int32 [4, n] counts of one side through the model's own forward: per chunk of queries the live list entries become
+        explicit triples, ONE forward call scores the chunk's true triples and those, rank_lists_from_scores counts."""
+        n = int(trip.shape[0])
+        dev = trip.device
+        E = int(self.config.tot_entity)
+        col = 0 if side else 2
+        out = torch.zeros((4, n), dtype=torch.int32, device=dev)
+        loq = lists.list_of_query[:n] if lists.list_of_query is not None else torch.arange(n, dtype=torch.int64, device=dev)
+        start = lists.off[loq]
+        lens = (lists.off[loq + 1] - start).clamp_(min=0)
+        lens_host = lens.cpu().numpy()   # the one host read: the chunk boundaries
+        budget = max(1, self.PREDICT_SCRATCH_BYTES // self.CANDIDATE_ENTRY_BYTES)
+        largest = bool(self.model.higher_is_better)
+        a = 0
+        while a < n:
+            b, tot = a + 1, int(lens_host[a])
+            while b < n and tot + int(lens_host[b]) <= budget:
+                tot += int(lens_host[b])
+                b += 1
+            m = b - a
+            seg = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+            seg[1:] = torch.cumsum(lens[a:b], 0)
+            pos = torch.arange(tot, dtype=torch.int64, device=dev)
+            qi = torch.searchsorted(seg, pos, right=True) - 1             # the chunk-local query of every entry
+            e = lists.ids[start[a:b][qi] + pos - seg[qi]].to(torch.int64)
+            tq = trip[a:b]
+            live = (e >= 0) & (e < E) & (e != tq[qi, col])
+            qi, e = qi[live], e[live]
+            kept = torch.ones_like(e, dtype=torch.bool)
+            if skip_off is not None and skip_ids.numel():
+                lo, hi = skip_off[a], skip_off[b]
+                spos = torch.arange(int(skip_ids.numel()), dtype=torch.int64, device=dev)
+                sseg = torch.searchsorted(skip_off[a:b + 1].contiguous(), spos, right=True) - 1
+                inside = (spos >= lo) & (spos < hi)
+                keys = torch.sort((sseg * E + skip_ids.to(torch.int64))[inside]).values
+                if keys.numel():
+                    want = qi * E + e
+                    at = torch.searchsorted(keys, want).clamp_(max=keys.numel() - 1)
+                    kept = keys[at] != want
+            live_seg = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+            live_seg[1:] = torch.cumsum(torch.bincount(qi, minlength=m), 0)
+            h = torch.cat([tq[:, 0], e if side else tq[qi, 0]]).contiguous()
+            r = torch.cat([tq[:, 1], tq[qi, 1]]).contiguous()
+            t = torch.cat([tq[:, 2], tq[qi, 2] if side else e]).contiguous()
+            with torch.no_grad():
+                s = self.model.forward(h, r, t).reshape(-1)
+            flags = (kept.to(torch.uint8) << 1) | 1
+            out[:, a:b] = self.K.rank_lists_from_scores(s[m:].contiguous(), s[:m].contiguous(), live_seg, flags, largest=largest)
+            a = b
+        return out
+
+    def rank_candidates(self, data, n, tail_candidates, head_candidates, return_ties=False):
+        """int32 [4, n] in rank_all's row order (rank_head, rank_tail, filtered head, filtered tail; 0-based) of the first n triples
+        of `data`, each ranked against ITS candidates only: tail_candidates / head_candidates are CandidateLists, or integer [n, C]
+        tables with -1 for "no entry".  The true entity is always a candidate; list entries equal to it or outside [0, tot_entity) are
+        ignored, duplicates count as often as they occur.  The filtered ranks leave out the entities known for the pair in train +
+        valid + test (the filter lists of rank_all).  return_ties: also int32 [2, n] (head, tail) with the number of candidates
+        whose score equals the true entity's bit for bit; the ranks are the optimistic end of such a group.
+        The row-kernel models take the fused kernel (kge_rank_candidates); RESCAL, NTN, TransR, SLM, SME, SME_BL, HoLE, OctonionE,
+        ConvKB and MuRP score the expanded lists through their own forward.  The 1-N models are refused: rank_all is their path."""
+        name = getattr(self.model, "kernel_name", None)
+        if isinstance(self.model, ProjectionModel):
+            raise ValueError("rank_candidates: %s is a projection model, whose scorer is 1-N over all entities; rank_all is its path"
+                             % type(self.model).__name__)
+        if name not in self.ROW_KERNEL_MODELS and name not in self.VIA_FORWARD_MODELS:
+            raise ValueError("rank_candidates: no candidate-list path for model %r" % name)
+        trip_host = _as_array(data, n)
+        n = int(trip_host.shape[0])
+        dev = self.config.device
+        trip = torch.from_numpy(trip_host).to(dev)
+        sides = [self._candidate_lists(tail_candidates, n, "tail_candidates"), self._candidate_lists(head_candidates, n, "head_candidates")]
+        source, (t_off, t_ids, h_off, h_ids) = self._filter_csr(trip_host, trip) if n else (None, (None,) * 4)
+        skips = [(t_off, t_ids), (h_off, h_ids)]
+        counts = []
+        if name in self.ROW_KERNEL_MODELS:
+            desc = self.K.model_desc(self.model)
+            for side in (0, 1):
+                ls = sides[side]
+                loq = ls.list_of_query[:n].contiguous() if ls.list_of_query is not None else None
+                counts.append(self.K.rank_candidates(desc, trip, side, ls.off, ls.ids, list_of_query=loq, skip_off=skips[side][0],
+                                                     skip_ids=skips[side][1], skip_sorted=source in ("triples", "triples_host")))
+        else:
+            if name == "rescal":   # the reference's forward renormalises both tables during eval too, as rank_all does
+                self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+            for side in (0, 1):
+                counts.append(self._rank_side_via_forward(trip, side, sides[side], *skips[side]) if n
+                              else torch.zeros((4, 0), dtype=torch.int32, device=dev))
+        ct, ch = counts
+        ranks = torch.stack([ch[0], ct[0], ch[1], ct[1]])
+        return (ranks, torch.stack([ch[2], ct[2]])) if return_ties else ranks
+
+    def test_candidates(self, data, n, tail_candidates, head_candidates, epoch=None):
+        """test() over given candidates: the same MetricCalculator summary (and tie warning) from rank_candidates' ranks.  The
+        metrics are over each query's list + its true entity, so they are comparable only between runs that use the same lists."""
+        self.metric_calculator.reset()
+        ranks, ties = self.rank_candidates(data, n, tail_candidates, head_candidates, return_ties=True)
+        return self._settle(ranks, ties, epoch)
+
+    def type_constraints(self):
+        """(range_lists, domain_lists) of the training split (build_type_constraints), built once per Evaluator."""
+        if getattr(self, "_type_constraints", None) is None:
+            train = _as_array(self.config.knowledge_graph.read_cache_data('triplets_train'), None)
+            self._type_constraints = build_type_constraints(train, self.config.tot_relation)
+        return self._type_constraints
+
+    def test_type_constrained(self, data=None, n=None, epoch=None):
+        """Type-constrained ranking (Krompass et al., 2015): every test triple's tail is ranked among the entities seen as tail of
+        its relation in the training split (+ itself), its head among those seen as head; filtered as usual.  data: default the
+        test split."""
+        data = self.test_data if data is None else data
+        rel = torch.from_numpy(_as_array(data, n)[:, 1].copy())
+        ranges, domains = self.type_constraints()
+        return self.test_candidates(data, n, ranges.for_queries(rel), domains.for_queries(rel), epoch=epoch)
+
+    def test_sampled(self, data, n, num_candidates, seed=0, epoch=None):
+        """Ranking against `num_candidates` uniform entity ids per query and side, drawn on the device from a torch.Generator seeded
+        with `seed` (the same seed draws the same candidates).  The metrics are over num_candidates + 1 candidates (the draws
+        and the true entity): they are NOT comparable with full ranks over all entities, only with runs of the same num_candidates."""
+        m = len(data) if n is None else int(n)
+        dev = torch.device(self.config.device)
+        g = torch.Generator(device=dev)
+        g.manual_seed(int(seed))
+        E = int(self.config.tot_entity)
+        tails = torch.randint(E, (m, int(num_candidates)), generator=g, device=dev, dtype=torch.int64)
+        heads = torch.randint(E, (m, int(num_candidates)), generator=g, device=dev, dtype=torch.int64)
+        return self.test_candidates(data, m, tails, heads, epoch=epoch)
+
+
+class CandidateLists:
+    """Candidate lists as a CSR: list l = ids[off[l] : off[l + 1]] (off int64 [n_lists + 1], ids int32); query i uses list
+    list_of_query[i], or list i when list_of_query is None.  Tensors or arrays; Evaluator moves them to its device."""
+
+    def __init__(self, off, ids, list_of_query=None):
+        as_t = lambda x, dt: (x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).reshape(-1).to(dt).contiguous()
+        self.off, self.ids = as_t(off, torch.int64), as_t(ids, torch.int32)
+        self.list_of_query = None if list_of_query is None else as_t(list_of_query, torch.int64)
+        if self.off.numel() < 1:
+            raise ValueError("off must hold n_lists + 1 offsets")
+
+    @property
+    def n_lists(self):
+        return int(self.off.numel()) - 1
+
+    def to(self, device):
+        return CandidateLists(self.off.to(device), self.ids.to(device), None if self.list_of_query is None else self.list_of_query.to(device))
+
+    def for_queries(self, list_of_query):
+        """The same lists with query i mapped to list list_of_query[i] (type constraints: the queries' relation ids)."""
+        return CandidateLists(self.off, self.ids, list_of_query)
+
+
+def build_type_constraints(train_triples, tot_relation):
+    """(range_lists, domain_lists): per relation r the unique tails / heads seen with r in `train_triples` [N, 3], ascending, as
+    CandidateLists with one list per relation (a relation absent from the split has an empty list).  Use .for_queries(relation ids)."""
+    a = np.asarray(train_triples, dtype=np.int64).reshape(-1, 3)
+    R = int(tot_relation)
+    rels = np.arange(R, dtype=np.int64)
+    if a.shape[0] == 0:
+        empty = lambda: CandidateLists(np.zeros(R + 1, np.int64), np.zeros(0, np.int32))
+        return empty(), empty()
+    t_off, t_ids = _csr_side(rels, a[:, 1], a[:, 2])
+    h_off, h_ids = _csr_side(rels, a[:, 1], a[:, 0])
+    return CandidateLists(t_off, t_ids), CandidateLists(h_off, h_ids)

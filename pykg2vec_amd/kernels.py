@@ -936,6 +936,90 @@ def topk_rows(scores, k, largest=False, skip_off=None, skip_ids=None, keep=None)
     return ids, vals, count
 
 
+CAND_CHUNK = L.CAND_CHUNK
+
+
+def sort_skip_segments(skip_off, skip_ids):
+    """skip_ids with every segment skip_ids[skip_off[i] : skip_off[i + 1]] ascending, the CSR layout kept: ONE torch.sort of
+    (segment index, id) keys on the device, no host read."""
+    total = int(skip_ids.numel())
+    if total == 0:
+        return skip_ids
+    pos = torch.arange(total, dtype=torch.int64, device=skip_ids.device)
+    seg = torch.searchsorted(skip_off.contiguous(), pos, right=True)      # entries of segment i get i + 1: monotone in the position
+    keys = (seg << 32) + (skip_ids.to(torch.int64) + (1 << 31))
+    keys = torch.sort(keys).values
+    return ((keys & 0xffffffff) - (1 << 31)).to(torch.int32)
+
+
+def rank_candidates(desc, triples, side, cand_off, cand_ids, list_of_query=None, skip_off=None, skip_ids=None, skip_sorted=False):
+    """Where the true entity of every triple stands among the ids of its candidate list (kge_rank_candidates): int32 [4, n] =
+    #better, #better under the filter, #tied, #tied under the filter (0-based, optimistic end, ties bit for bit).  triples int64
+    [n, 3]; side 0 ranks tails, 1 ranks heads; lists as a CSR (cand_off int64 [n_lists + 1], cand_ids int32), query i uses list
+    list_of_query[i] (int64 [n]) or list i.  Entries equal to the true entity or outside [0, tot_entity) are ignored (-1 pads).
+    skip_off / skip_ids: per-query CSR of known entities to leave out; the segments are sorted here (sort_skip_segments) unless
+    skip_sorted says they already are ascending."""
+    if not isinstance(desc, L.ModelDesc):
+        raise L.KgeHipError("rank_candidates: %s has no row kernels; rank it via-forward (the model's own forward over the expanded "
+                            "triples + rank_lists_from_scores, as Evaluator.rank_candidates does)" % type(desc).__name__)
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("triples must be [n, 3]")
+    if (skip_off is None) != (skip_ids is None):
+        raise ValueError("skip_off and skip_ids come together")
+    n = int(triples.shape[0])
+    dev = triples.device
+    counts = torch.empty((4, n), dtype=torch.int32, device=dev)
+    n_lists = int(cand_off.numel()) - 1
+    if list_of_query is not None and list_of_query.numel() != n:
+        raise ValueError("list_of_query must hold one list index per query (%d, got %d)" % (n, list_of_query.numel()))
+    if n == 0:
+        return counts
+    lib = L.load()
+    if cand_ids.numel() == 0:   # every list is empty: a pointer the library accepts, never read
+        cand_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+    po = pi = None
+    if skip_off is not None:
+        if skip_off.numel() != n + 1:
+            raise ValueError("skip_off must hold n + 1 = %d offsets (got %d)" % (n + 1, skip_off.numel()))
+        if not skip_sorted:
+            skip_ids = sort_skip_segments(skip_off, skip_ids)
+        if skip_ids.numel() == 0:
+            skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+        po, pi = _dev(skip_off, torch.int64, "skip_off"), _dev(skip_ids, torch.int32, "skip_ids")
+    nbytes = lib.kge_rank_candidates_workspace_bytes(n, n_lists, int(cand_ids.numel()))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.check(lib.kge_rank_candidates(ctypes.byref(desc), _ids(triples, "triples"), n, int(side),
+                                    _ids(list_of_query, "list_of_query") if list_of_query is not None else None,
+                                    _dev(cand_off, torch.int64, "cand_off"), _dev(cand_ids, torch.int32, "cand_ids"), n_lists, po, pi,
+                                    ctypes.c_void_p(ws.data_ptr()), nbytes, _dev(counts, torch.int32, "counts"), _stream()),
+            "kge_rank_candidates")
+    return counts
+
+
+def rank_lists_from_scores(scores, truth_scores, seg_off, flags=None, largest=False):
+    """The counts of rank_candidates from scores computed elsewhere (kge_rank_lists_from_scores): segment i of `scores` (float32 or
+    float64, 1-D) = scores[seg_off[i] : seg_off[i + 1]] against truth_scores[i]; flags uint8 per score (bit 0 live, bit 1 live under
+    the filter; None: all set); better = lower unless `largest`.  int32 [4, n]."""
+    if scores.dtype not in (torch.float32, torch.float64) or truth_scores.dtype != scores.dtype:
+        raise TypeError("scores and truth_scores must both be float32 or both float64 (got %s, %s)" % (scores.dtype, truth_scores.dtype))
+    n = int(truth_scores.numel())
+    if seg_off.numel() != n + 1:
+        raise ValueError("seg_off must hold n + 1 = %d offsets (got %d)" % (n + 1, seg_off.numel()))
+    dev = truth_scores.device
+    counts = torch.empty((4, n), dtype=torch.int32, device=dev)
+    if n == 0:
+        return counts
+    if scores.numel() == 0:
+        scores = torch.zeros(1, dtype=scores.dtype, device=dev)
+    if flags is not None and flags.numel() == 0:
+        flags = None
+    L.check(L.load().kge_rank_lists_from_scores(_dev(scores, scores.dtype, "scores"), 1 if scores.dtype == torch.float64 else 0,
+                                                _dev(truth_scores, scores.dtype, "truth_scores"), _dev(seg_off, torch.int64, "seg_off"), n,
+                                                _dev(flags, torch.uint8, "flags") if flags is not None else None, 1 if largest else 0,
+                                                _dev(counts, torch.int32, "counts"), _stream()), "kge_rank_lists_from_scores")
+    return counts
+
+
 def triple_set_build(triples):
     """Open-addressing hash set of the train triples (uint64 slots, power of two >= 2n)."""
     n = triples.shape[0]
