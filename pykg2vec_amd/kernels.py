@@ -742,12 +742,7 @@ def eval_ranks(desc, triples, tail_off, tail_ids, head_off, head_ids, workspace=
     if workspace is None:
         workspace = eval_workspace(desc, n, triples.device)
     ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
-    args = []
-    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
-        if off is None:
-            args += [None, None]
-        else:
-            args += [_dev(off, torch.int64, "csr offsets"), _dev(ids, torch.int32, "csr ids")]
+    args = _filter_csr_args(tail_off, tail_ids, head_off, head_ids)
     L.check(L.load().kge_eval_ranks_ties(ctypes.byref(desc), _ids(triples, "triples"), n, *args,
                                          _dev(workspace, torch.uint8, "workspace"), workspace.numel(),
                                          _dev(ranks, torch.int32, "ranks"),
@@ -764,12 +759,7 @@ def eval_ranks_grouped(desc, triples, group_of_triple, group_rel, qblocks, tail_
         L.check(-1, "kge_eval_grouped_workspace_bytes")
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=triples.device)
     ranks = torch.empty((4, n), dtype=torch.int32, device=triples.device)
-    args = []
-    for off, ids in ((tail_off, tail_ids), (head_off, head_ids)):
-        if off is None:
-            args += [None, None]
-        else:
-            args += [_dev(off, torch.int64, "csr offsets"), _dev(ids, torch.int32, "csr ids")]
+    args = _filter_csr_args(tail_off, tail_ids, head_off, head_ids)
     L.check(lib.kge_eval_ranks_grouped_ties(ctypes.byref(desc), _ids(triples, "triples"), n,
                                             _dev(group_of_triple, torch.int32, "group_of_triple"), _ids(group_rel, "group_rel"), G,
                                             _dev(qblocks, torch.int32, "qblocks"), qblocks.shape[0], *args,

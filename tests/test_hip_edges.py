@@ -100,6 +100,13 @@ def test_entity_counts_around_the_sweep_tile(hip, E):
     _, rk = ko.evaluate("transe", P, test, hr_t, tr_h, l1_flag=True)
     ref = np.stack([rk["head"], rk["tail"], rk["fhead"], rk["ftail"]])
     assert (got != ref).sum() <= 1 and np.abs(got - ref).max() <= 1, (got, ref)
+    # against the sweep's own fp32 rows the ranks are exact at every entity count: no mismatch is allowed there (the allowance above is
+    # for the float64 oracle, whose near-ties an fp32 energy may order the other way; tests/test_hip_rank_edges.py)
+    from pykg2vec_amd import kernels as K
+    rows = K.eval_sweep_scores(m.make_desc(), hip.dev(test)).cpu().numpy()
+    for i, (h, r, t) in enumerate(test):
+        assert (got[1, i], got[3, i]) == ko.rank_from_scores(rows[2 * i], int(t), hr_t[(int(h), int(r))]), ("tail", E, i)
+        assert (got[0, i], got[2, i]) == ko.rank_from_scores(rows[2 * i + 1], int(h), tr_h[(int(t), int(r))]), ("head", E, i)
 
 
 def test_duplicate_rows_accumulate(hip):
