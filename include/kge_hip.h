@@ -172,6 +172,38 @@ int kge_rank_candidates(const kge_model_desc* m, const int64_t* triples, int64_t
 int kge_rank_lists_from_scores(const void* scores, int dtype, const void* truth_scores, const int64_t* seg_off, int64_t n,
                                const uint8_t* flags, int largest, int32_t* counts, void* stream);
 
+/* ---- relation ranking (kge_relations.hip): where does the true relation of query i = (h, r, t) stand among ALL relations?
+ * triples int64 [n, 3]; R = m->tot_relation.  With s = score(h, r, t) and s' = score(h, r', t) for every r' in [0, R), r' != r --
+ * both the values kge_score_forward returns for those triples, bit for bit -- counts int32 [4, n] is
+ *   counts[0][i] = #{r': s' < s}       counts[1][i] = the same over the r' not in query i's skip segment
+ *   counts[2][i] = #{r': s' == s}      counts[3][i] = the same, filtered
+ * 0-based optimistic-end counts, ties bit for bit, a NaN compares false both ways (the convention of kge_rank_candidates; the
+ * row-kernel models are all lower-is-better).  Without skip segments (both NULL) rows 1 and 3 equal rows 0 and 2.  Counts are integer
+ * sums: the result does not depend on the execution order.
+ * Skip segments: the relations known for the pair (h, t), skip_ids[skip_off[i] .. skip_off[i+1]) (int32 ids, int64 offsets [n + 1]).
+ * PRECONDITION: every segment is ascending (it is binary-searched; the lists of kge_relation_csr_* are); the debug id mode
+ * (kge_set_debug) checks it, and the ids of `triples` against tot_entity / tot_relation.
+ * Models: the row-kernel models (TransE/H/D/M, RotatE, DistMult, ComplEx, ANALOGY, CP, SimplE, SimplE_ignr, QuatE, KG2E); any other
+ * is refused with a message naming the via-forward path (kge_rank_lists_from_scores).  Refused before any GPU call, kge_last_error()
+ * naming the argument: a null descriptor, an unknown model, a missing table, n < 0, only one of skip_off / skip_ids, a null workspace
+ * or one below kge_rank_relations_workspace_bytes, null triples / counts.  n == 0 returns 0.
+ * KGE_REL_CHUNK: relation ids per work item (one lane group per item); R around its multiples are the edge cases. */
+#define KGE_REL_CHUNK 64
+size_t kge_rank_relations_workspace_bytes(int64_t n);
+int kge_rank_relations(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* skip_off, const int32_t* skip_ids,
+                       void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+/* The skip segments of kge_rank_relations, built on the device (kge_index.hip) like kge_filter_csr_*: query i's segment is
+ * rel_ids[rel_off[i] .. rel_off[i+1]) = the distinct relations r with (h_i, r, t_i) in `known` (int64 [n_known, 3]: train + valid +
+ * test, duplicates allowed), ascending.  One packed key h:24 | t:24 | r:16 per known triple: tot_entity <= 2^24 and tot_relation <=
+ * 2^16, refused otherwise.  Two calls because the caller owns every buffer: _count sorts the keys into `workspace`
+ * (kge_relation_csr_workspace_bytes) and writes rel_off [n_queries + 1] and *total; the caller reads the total, sizes rel_ids, and
+ * _fill writes it (same workspace, untouched in between). */
+size_t kge_relation_csr_workspace_bytes(int64_t n_known, int64_t n_queries);
+int kge_relation_csr_count(const int64_t* known, int64_t n_known, const int64_t* queries, int64_t n_queries, int64_t tot_entity,
+                           int64_t tot_relation, void* workspace, size_t workspace_bytes, int64_t* rel_off, int64_t* total, void* stream);
+int kge_relation_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_known, const void* workspace, const int64_t* rel_off,
+                          int32_t* rel_ids, void* stream);
+
 /* An empty kernel launch of `tag` workgroups of 64 threads ("kge::k_marker"): a boundary that shows up in a rocprofv3 kernel /
  * counter trace.  bench.py's counter passes use it to cut one process's dispatch sequence into per-configuration segments. */
 int kge_debug_marker(int32_t tag, void* stream);

@@ -124,6 +124,7 @@ class StagedStep(ctypes.Structure):
 CONVKB_MAX_WIDTHS = 8
 TOPK_MAX = 1024   # KGE_TOPK_MAX: the most candidates kge_topk_rows returns per row
 CAND_CHUNK = 64   # KGE_CAND_CHUNK: list entries per work item of kge_rank_candidates
+REL_CHUNK = 64    # KGE_REL_CHUNK: relation ids per work item of kge_rank_relations
 
 
 class ConvKBDesc(ctypes.Structure):
@@ -354,6 +355,14 @@ _SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_rank_lists_from_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_rank_relations_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "kge_rank_relations": (ctypes.c_int, [ctypes.POINTER(ModelDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_relation_csr_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "kge_relation_csr_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_relation_csr_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
     "kge_last_error": (ctypes.c_char_p, []),
     "kge_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ModelDesc), ctypes.c_int64]),
     "kge_score_forward": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -379,11 +379,11 @@ __global__ __launch_bounds__(256) void k_csr_query(const int64_t* __restrict__ q
     if constexpr (!FILL) { if (lane == 0) count[side * n + q] = total; }
 }
 
-// exclusive scan of the two count rows into int64 offsets [n + 1] each; one 1024-thread block
+// exclusive scan of the `sides` (1 or 2) count rows into int64 offsets [n + 1] each; one 1024-thread block
 __global__ __launch_bounds__(kIxBlock) void k_csr_scan(const int* __restrict__ count, int64_t n, int64_t* __restrict__ off_t,
-                                                       int64_t* __restrict__ off_h, int64_t* __restrict__ totals) {
+                                                       int64_t* __restrict__ off_h, int64_t* __restrict__ totals, int sides) {
     __shared__ long long s_carry;
-    for (int side = 0; side < 2; ++side) {
+    for (int side = 0; side < sides; ++side) {
         int64_t* off = side ? off_h : off_t;
         if (threadIdx.x == 0) s_carry = 0;
         __syncthreads();
@@ -404,6 +404,46 @@ __global__ __launch_bounds__(kIxBlock) void k_csr_scan(const int* __restrict__ c
 }
 
 static int csr_P(int64_t M) { return pow2_at_least(M, 2048); }
+
+// ---------------------------------------------------------------- the same lists keyed by the PAIR (h, t): the relations known for it
+// (the skip segments of kge_rank_relations).  One key h:24 | t:24 | r:16 per known triple, one side; the sort, the per-query wave
+// with its binary search and duplicate drop, and the one-block scan are the ones above.
+__global__ __launch_bounds__(256) void k_relcsr_keys(const int64_t* __restrict__ known, int64_t M, int P, u64* __restrict__ keys) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= P) return;
+    u64 a = kKeyPad;
+    if (j < M) a = ((u64)known[3 * j] << 40) | ((u64)known[3 * j + 2] << 16) | (u64)known[3 * j + 1];
+    keys[j] = a;
+}
+
+// one wave per query.  FILL = false: count[q] = number of distinct relations; FILL = true: ids[off[q] ...] = them, ascending.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_relcsr_query(const int64_t* __restrict__ queries, int64_t n, const u64* __restrict__ k, int64_t M,
+                                                      int* __restrict__ count, const int64_t* __restrict__ off, int32_t* __restrict__ ids) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= n) return;
+    const u64 lo_key = ((u64)queries[3 * q] << 40) | ((u64)queries[3 * q + 2] << 16);
+    const int64_t lo = csr_lower_bound(k, M, lo_key), hi = csr_lower_bound(k, M, lo_key | 0xFFFFull);
+    // (the top id 0xFFFF is a legal relation with tot_relation = 2^16: the run's upper bound includes one key equal to lo_key | 0xFFFF;
+    // further copies of it are duplicates, which are dropped anyway)
+    const int64_t hi2 = (hi < M && k[hi] == (lo_key | 0xFFFFull)) ? hi + 1 : hi;
+    int total = 0;
+    int32_t* out = nullptr;
+    if constexpr (FILL) out = ids + off[q];
+    for (int64_t base = lo; base < hi2; base += 64) {
+        const int64_t j = base + lane;
+        const bool in = j < hi2;
+        const u64 key = in ? k[j] : 0;
+        const bool fresh = in && (j == lo || k[j - 1] != key);
+        const unsigned long long m = __ballot(fresh);
+        if constexpr (FILL) {
+            if (fresh) out[total + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)(key & 0xFFFFull);
+        }
+        total += __popcll(m);
+    }
+    if constexpr (!FILL) { if (lane == 0) count[q] = total; }
+}
 
 }  // namespace kge
 
@@ -435,7 +475,7 @@ int kge_filter_csr_count(const int64_t* known, int64_t n_known, const int64_t* q
     if ((rc = sort_batched(keys, 2, P, s))) return rc;
     hipLaunchKernelGGL((k_csr_query<false>), dim3((unsigned)((2 * n_queries + 3) / 4)), dim3(256), 0, s, queries, n_queries, keys, P, n_known,
                        count, (const int64_t*)nullptr, (const int64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(kIxBlock), 0, s, count, n_queries, tail_off, head_off, totals);
+    hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(kIxBlock), 0, s, count, n_queries, tail_off, head_off, totals, 2);
     return check_launch("k_csr_scan");
 }
 
@@ -447,6 +487,48 @@ int kge_filter_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_kno
     hipLaunchKernelGGL((k_csr_query<true>), dim3((unsigned)((2 * n_queries + 3) / 4)), dim3(256), 0, (hipStream_t)stream, queries, n_queries, keys, P,
                        n_known, (int*)nullptr, tail_off, head_off, tail_ids, head_ids);
     return check_launch("k_csr_query");
+}
+
+size_t kge_relation_csr_workspace_bytes(int64_t n_known, int64_t n_queries) {
+    if (n_known <= 0 || n_known >= (1ll << 30) || n_queries < 0) return 0;
+    return (size_t)csr_P(n_known) * sizeof(u64) + (size_t)(n_queries + 1) * sizeof(int) + 512;
+}
+
+int kge_relation_csr_count(const int64_t* known, int64_t n_known, const int64_t* queries, int64_t n_queries, int64_t tot_entity,
+                           int64_t tot_relation, void* workspace, size_t workspace_bytes, int64_t* rel_off, int64_t* total, void* stream) {
+    const char* who = "kge_relation_csr_count";
+    if (!known || !queries || !workspace || !rel_off || !total || n_known <= 0 || n_known >= (1ll << 30) || n_queries <= 0) {
+        set_error("%s: bad arguments (known / queries / workspace / rel_off / total null, n_known outside 1..2^30-1 or n_queries < 1)", who);
+        return -1;
+    }
+    if (tot_entity > (1 << 24) || tot_relation > (1 << 16)) { set_error("%s: the packed key holds 2^24 entities and 2^16 relations", who); return -1; }
+    if (workspace_bytes < kge_relation_csr_workspace_bytes(n_known, n_queries)) { set_error("%s: workspace too small", who); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = debug_check_triples(who, tot_entity, tot_relation, known, n_known, s)) return rc;
+    if (int rc = debug_check_triples(who, tot_entity, tot_relation, queries, n_queries, s)) return rc;
+    const int P = csr_P(n_known);
+    u64* keys = (u64*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int* count = (int*)(keys + (size_t)P);
+    hipLaunchKernelGGL(k_relcsr_keys, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, known, n_known, P, keys);
+    int rc = check_launch("k_relcsr_keys");
+    if (rc) return rc;
+    if ((rc = sort_batched(keys, 1, P, s))) return rc;
+    hipLaunchKernelGGL((k_relcsr_query<false>), dim3((unsigned)((n_queries + 3) / 4)), dim3(256), 0, s, queries, n_queries, keys, n_known, count,
+                       (const int64_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(kIxBlock), 0, s, count, n_queries, rel_off, (int64_t*)nullptr, total, 1);
+    return check_launch("k_csr_scan");
+}
+
+int kge_relation_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_known, const void* workspace, const int64_t* rel_off,
+                          int32_t* rel_ids, void* stream) {
+    if (!queries || !workspace || !rel_off || !rel_ids || n_queries <= 0 || n_known <= 0 || n_known >= (1ll << 30)) {
+        set_error("kge_relation_csr_fill: bad arguments (queries / workspace / rel_off / rel_ids null, or sizes outside kge_relation_csr_count's)");
+        return -1;
+    }
+    const u64* keys = (const u64*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    hipLaunchKernelGGL((k_relcsr_query<true>), dim3((unsigned)((n_queries + 3) / 4)), dim3(256), 0, (hipStream_t)stream, queries, n_queries, keys,
+                       n_known, (int*)nullptr, rel_off, rel_ids);
+    return check_launch("k_relcsr_query");
 }
 
 int kge_pull_index_geometry(int64_t n_batches, int64_t n_pairs, int64_t tot_entity, int64_t tot_relation, int32_t segment,

@@ -10,6 +10,8 @@ Beyond the reference: `predict_tails / predict_heads / predict_rels` answer many
 the known triples optionally left out (Model.score_rows + kernels.topk_rows); Trainer.infer_* is served by them.
 `rank_candidates / test_candidates / test_type_constrained / test_sampled` rank every triple against a GIVEN list of candidates
 (fixed negatives, type constraints, sampled ids) instead of all entities (kernels.rank_candidates; CandidateLists below).
+`rank_relations / test_relations` rank the true RELATION of every triple among all relations, raw and with the relations known for
+the pair (h, t) left out (kernels.rank_relations): MR / MRR / Hits@k of relation prediction.
 """
 import os
 import timeit
@@ -154,6 +156,19 @@ def build_filter_csr_from_triples(queries, known_triples, tot_relation):
     return t_off, t_ids, h_off, h_ids
 
 
+def build_relation_csr_from_triples(queries, known_triples, tot_entity):
+    """Per query (h, ., t) the distinct relations r with (h, r, t) in `known_triples` (train + valid + test), ascending, as a CSR:
+    (rel_off int64 [n + 1], rel_ids int32).  The filter of relation ranking; hr_t / tr_h are keyed by (h, r) / (t, r) and cannot
+    serve the pair key."""
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    a = np.asarray(known_triples, dtype=np.int64).reshape(-1, 3)
+    if a.shape[0] == 0:
+        return np.zeros(q.shape[0] + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    E = int(tot_entity)
+    off, ids = _csr_side(q[:, 0] * E + q[:, 2], a[:, 0] * E + a[:, 2], a[:, 1])
+    return off.astype(np.int64), ids
+
+
 class Evaluator:
     """utils/evaluator.py:225-334."""
 
@@ -170,6 +185,8 @@ class Evaluator:
         self._known_dev = None
         self.setup_stats = {}
         self.tie_counts = None     # [2, n] of the last test(): candidates tied with the true entity per head / tail sweep
+        self._rel_cache = {}
+        self.relation_tie_counts = None   # [n] of the last test_relations(): relations tied with the true relation
 
     # --- single-query hooks kept for Trainer.infer_* style callers (evaluator.py:249-273)
     def test_tail_rank(self, h, r, topk=-1):
@@ -485,20 +502,23 @@ class Evaluator:
         mc = self.metric_calculator
         ranks = ranks.cpu().numpy()  # the D2H copy: 4*n int32 (+ 2*n tie counts)
         self.tie_counts = ties.cpu().numpy() if ties is not None else None
-        if self.tie_counts is not None and (self.tie_counts > 0).any():
-            # ranks are count-based (#candidates strictly below the true one): exact unless candidates TIE it, where the reference
-            # lands somewhere inside the tie group (torch.topk's order) and this count is the optimistic end of it
-            t = self.tie_counts
-            _log("WARNING: %d of %d rank sweeps have candidates whose energy equals the true entity's exactly (up to %d of them): the "
-                 "reported ranks are the optimistic end of each tie group -- rank <= reference rank <= rank + ties; a saturated or "
-                 "collapsed scorer (clamped energies, constant outputs) makes MR / MRR / Hits look better than they are"
-                 % (int((t > 0).sum()), t.size, int(t.max())))
+        self._warn_ties(self.tie_counts, "entity")
         mc.append_ranks(ranks, epoch)
         mc.settle()
         mc.display_summary()
         if mc.epoch is not None and mc.epoch >= self.config.epochs - 1:
             mc.save_test_summary(self.model.model_name)
         return mc.get_curr_scores()
+
+    @staticmethod
+    def _warn_ties(t, what):
+        if t is not None and (t > 0).any():
+            # ranks are count-based (#candidates strictly below the true one): exact unless candidates TIE it, where the reference
+            # lands somewhere inside the tie group (torch.topk's order) and this count is the optimistic end of it
+            _log("WARNING: %d of %d rank sweeps have candidates whose energy equals the true %s's exactly (up to %d of them): the "
+                 "reported ranks are the optimistic end of each tie group -- rank <= reference rank <= rank + ties; a saturated or "
+                 "collapsed scorer (clamped energies, constant outputs) makes MR / MRR / Hits look better than they are"
+                 % (int((t > 0).sum()), t.size, what, int(t.max())))
 
     # --- ranking against given candidates: the cost scales with the lists, not with tot_entity
     ROW_KERNEL_MODELS = frozenset(["transe", "transh", "transd", "transm", "rotate", "distmult", "complex", "analogy", "cp", "simple",
@@ -650,6 +670,115 @@ class Evaluator:
         tails = torch.randint(E, (m, int(num_candidates)), generator=g, device=dev, dtype=torch.int64)
         heads = torch.randint(E, (m, int(num_candidates)), generator=g, device=dev, dtype=torch.int64)
         return self.test_candidates(data, m, tails, heads, epoch=epoch)
+
+    # --- relation ranking: the true relation of (h, r, t) among all relations, raw and with the relations known for (h, t) left out
+    def _relation_csr(self, trip, trip_dev):
+        """(rel_off, rel_ids) device tensors: per query the relations known for its pair (h, t) over train + valid + test, ascending.
+        Built on the device (kge_relation_csr_*) with the real backend when the splits are there and the ids fit the packed key;
+        otherwise with numpy from the splits."""
+        E, R = int(self.config.tot_entity), int(self.config.tot_relation)
+        if self.K is K and E <= self.DEVICE_CSR_MAX_ENTITY and R <= self.DEVICE_CSR_MAX_RELATION:
+            known = self._known_triples()
+            if known is not None:
+                return self.K.relation_csr_build(known, trip_dev, E, R)
+        kg = self.config.knowledge_graph
+        try:
+            parts = [_as_array(kg.read_cache_data(k), None) for k in ('triplets_train', 'triplets_valid', 'triplets_test')]
+        except (KeyError, FileNotFoundError, AttributeError):
+            raise K.L.KgeHipError("Evaluator: relation ranking filters by the pair (h, t), which needs the three splits in the "
+                                  "knowledge-graph cache (hr_t / tr_h are keyed by (h, r) / (t, r))")
+        return tuple(torch.from_numpy(a).to(trip_dev.device) for a in build_relation_csr_from_triples(trip, np.concatenate(parts), E))
+
+    def _relation_inputs(self, data, n):
+        key = self._fingerprint(data, n)
+        if key not in self._rel_cache:
+            trip = _as_array(data, n)
+            trip_dev = torch.from_numpy(trip).to(self.config.device)
+            self._rel_cache[key] = (trip_dev,) + tuple(self._relation_csr(trip, trip_dev))
+        return self._rel_cache[key]
+
+    def _rank_relations_via_forward(self, trip, rel_off, rel_ids):
+        """int32 [4, n] counts through the model's own forward: per chunk of queries the R - 1 other relations of each query become
+        explicit triples, ONE forward call scores the chunk's true triples and those, rank_lists_from_scores counts."""
+        n = int(trip.shape[0])
+        dev = trip.device
+        R = int(self.config.tot_relation)
+        out = torch.zeros((4, n), dtype=torch.int32, device=dev)
+        per = int(max(1, (self.PREDICT_SCRATCH_BYTES // self.CANDIDATE_ENTRY_BYTES) // max(1, R - 1)))
+        largest = bool(self.model.higher_is_better)
+        others = torch.arange(R - 1, dtype=torch.int64, device=dev)
+        off_host = rel_off.cpu().numpy()   # the one host read: which skip entries belong to a chunk
+        for a in range(0, n, per):
+            b = min(n, a + per)
+            m = b - a
+            tq = trip[a:b]
+            rel = others.unsqueeze(0) + (others.unsqueeze(0) >= tq[:, 1:2]).to(torch.int64)     # [m, R - 1]: every relation but the true one
+            known = torch.zeros((m, R), dtype=torch.bool, device=dev)
+            lo, hi = int(off_host[a]), int(off_host[b])
+            if hi > lo:
+                ids = rel_ids[lo:hi].to(torch.int64)
+                row = torch.searchsorted(rel_off[a:b + 1].contiguous(), torch.arange(lo, hi, dtype=torch.int64, device=dev), right=True) - 1
+                ok = (ids >= 0) & (ids < R)
+                known[row[ok], ids[ok]] = True
+            kept = ~known.gather(1, rel) if R > 1 else known[:, :0]
+            flags = ((kept.reshape(-1).to(torch.uint8) << 1) | 1).contiguous()          # bit 0 live (every other relation is), bit 1 kept
+            h = torch.cat([tq[:, 0], tq[:, 0].repeat_interleave(R - 1)]).contiguous()
+            r = torch.cat([tq[:, 1], rel.reshape(-1)]).contiguous()
+            t = torch.cat([tq[:, 2], tq[:, 2].repeat_interleave(R - 1)]).contiguous()
+            with torch.no_grad():
+                s = self.model.forward(h, r, t).reshape(-1)
+            seg = torch.arange(m + 1, dtype=torch.int64, device=dev) * (R - 1)
+            out[:, a:b] = self.K.rank_lists_from_scores(s[m:].contiguous(), s[:m].contiguous(), seg, flags, largest=largest)
+        return out
+
+    def rank_relations(self, data, n, return_ties=False):
+        """int32 [2, n] device tensor: the 0-based rank of the true relation of the first n triples of `data` among all relations
+        (row 0), and with the OTHER relations known for the pair (h, t) in train + valid + test left out (row 1).  return_ties: also
+        int32 [n], the number of other relations whose score equals the true one's bit for bit; the ranks are the optimistic end of
+        such a group.  The row-kernel models take the fused kernel (kge_rank_relations); RESCAL, NTN, TransR, SLM, SME, SME_BL, HoLE,
+        OctonionE, ConvKB and MuRP score the expanded triples through their own forward.  The 1-N models are refused."""
+        name = getattr(self.model, "kernel_name", None)
+        if isinstance(self.model, ProjectionModel):
+            raise ValueError("rank_relations: %s is a projection model, whose forward scores entities, not relations"
+                             % type(self.model).__name__)
+        if name not in self.ROW_KERNEL_MODELS and name not in self.VIA_FORWARD_MODELS:
+            raise ValueError("rank_relations: no relation-ranking path for model %r" % name)
+        trip, rel_off, rel_ids = self._relation_inputs(data, n)
+        if name in self.ROW_KERNEL_MODELS:
+            counts = self.K.rank_relations(self.K.model_desc(self.model), trip, skip_off=rel_off, skip_ids=rel_ids, skip_sorted=True)
+        else:
+            if name == "rescal":   # the reference's forward renormalises both tables during eval too, as rank_all does
+                self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+            counts = self._rank_relations_via_forward(trip, rel_off, rel_ids)
+        ranks = torch.stack([counts[0], counts[1]])
+        return (ranks, counts[2].clone()) if return_ties else ranks
+
+    def test_relations(self, data=None, n=None, epoch=None):
+        """Relation prediction metrics over the first n triples of `data` (default: the test split): {'mr', 'fmr', 'mrr', 'fmrr',
+        'hits': {k: .}, 'fhits': {k: .}} over config.hits, in float32 as MetricCalculator.settle computes the entity metrics, over the
+        one relation side.  Logs a summary and the tie warning; the tie counts stay in `relation_tie_counts`."""
+        data = self.test_data if data is None else data
+        t0 = timeit.default_timer()
+        ranks, ties = self.rank_relations(data, n, return_ties=True)
+        ranks = ranks.cpu().numpy()
+        self.relation_tie_counts = ties.cpu().numpy()
+        self._warn_ties(self.relation_tie_counts, "relation")
+        r = ranks[0].astype(np.float32) + 1
+        f = ranks[1].astype(np.float32) + 1
+        out = {'mr': np.mean(r), 'fmr': np.mean(f), 'mrr': np.mean(np.reciprocal(r)), 'fmrr': np.mean(np.reciprocal(f)),
+               'hits': {k: np.mean(r <= k, dtype=np.float32) for k in self.config.hits},
+               'fhits': {k: np.mean(f <= k, dtype=np.float32) for k in self.config.hits}}
+        lines = ["", "------Relation Prediction Results for %s: Epoch: %s --- time: %.2f------------" % (
+            getattr(self.config, "dataset_name", "?"), epoch, timeit.default_timer() - t0),
+            "--# of triples, # of relations : %d, %d" % (ranks.shape[1], self.config.tot_relation),
+            "--mr,  filtered mr             : %.4f, %.4f" % (out['mr'], out['fmr']),
+            "--mrr, filtered mrr            : %.4f, %.4f" % (out['mrr'], out['fmrr'])]
+        for k in self.config.hits:
+            lines.append("--hits%d                        : %.4f " % (k, out['hits'][k]))
+            lines.append("--filtered hits%d               : %.4f " % (k, out['fhits'][k]))
+        lines.append("---------------------------------------------------------")
+        _log("\n".join(lines))
+        return out
 
 
 class CandidateLists:

@@ -1010,6 +1010,65 @@ def rank_lists_from_scores(scores, truth_scores, seg_off, flags=None, largest=Fa
     return counts
 
 
+REL_CHUNK = L.REL_CHUNK
+
+
+def relation_csr_build(known, queries, tot_entity, tot_relation):
+    """Per query (h, ., t) of `queries` [n, 3] the distinct relations r with (h, r, t) in `known` [M, 3] (train + valid + test),
+    ascending: (rel_off int64 [n + 1], rel_ids int32), built on the device with kge_relation_csr_count / _fill.  One host read (the
+    list total) between the calls."""
+    n, M = int(queries.shape[0]), int(known.shape[0])
+    dev = queries.device
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n == 0 or M == 0:
+        return off, torch.empty(0, dtype=torch.int32, device=dev)
+    lib = L.load()
+    ws = torch.empty(lib.kge_relation_csr_workspace_bytes(M, n), dtype=torch.uint8, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.kge_relation_csr_count(_ids(known, "known triples"), M, _ids(queries, "queries"), n, int(tot_entity), int(tot_relation),
+                                       _dev(ws, torch.uint8, "workspace"), ws.numel(), _dev(off, torch.int64, "rel_off"),
+                                       _dev(total, torch.int64, "total"), _stream()), "kge_relation_csr_count")
+    nr = int(total.item())       # the one host read
+    ids = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)[:nr]
+    L.check(lib.kge_relation_csr_fill(_ids(queries, "queries"), n, M, _dev(ws, torch.uint8, "workspace"), _dev(off, torch.int64, "rel_off"),
+                                      ctypes.c_void_p(ids.data_ptr()), _stream()), "kge_relation_csr_fill")
+    return off, ids
+
+
+def rank_relations(desc, triples, skip_off=None, skip_ids=None, skip_sorted=False):
+    """Where the true relation of every triple stands among all relations (kge_rank_relations): int32 [4, n] = #better, #better under
+    the filter, #tied, #tied under the filter (0-based, optimistic end, ties bit for bit).  triples int64 [n, 3]; the number of
+    relations is the descriptor's.  skip_off / skip_ids: per-query CSR of the relations known for the pair (h, t), left out of rows
+    1 and 3; the segments are sorted here (sort_skip_segments) unless skip_sorted says they already are ascending."""
+    if not isinstance(desc, L.ModelDesc):
+        raise L.KgeHipError("rank_relations: %s has no row kernels; rank it via-forward (the model's own forward over the triples of "
+                            "every other relation + rank_lists_from_scores, as Evaluator.rank_relations does)" % type(desc).__name__)
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("triples must be [n, 3]")
+    if (skip_off is None) != (skip_ids is None):
+        raise ValueError("skip_off and skip_ids come together")
+    n = int(triples.shape[0])
+    dev = triples.device
+    counts = torch.empty((4, n), dtype=torch.int32, device=dev)
+    if n == 0:
+        return counts
+    lib = L.load()
+    po = pi = None
+    if skip_off is not None:
+        if skip_off.numel() != n + 1:
+            raise ValueError("skip_off must hold n + 1 = %d offsets (got %d)" % (n + 1, skip_off.numel()))
+        if not skip_sorted:
+            skip_ids = sort_skip_segments(skip_off, skip_ids)
+        if skip_ids.numel() == 0:   # every segment is empty: a pointer the library accepts, never read
+            skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+        po, pi = _dev(skip_off, torch.int64, "skip_off"), _dev(skip_ids, torch.int32, "skip_ids")
+    nbytes = lib.kge_rank_relations_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.check(lib.kge_rank_relations(ctypes.byref(desc), _ids(triples, "triples"), n, po, pi, ctypes.c_void_p(ws.data_ptr()), nbytes,
+                                   _dev(counts, torch.int32, "counts"), _stream()), "kge_rank_relations")
+    return counts
+
+
 def triple_set_build(triples):
     """Open-addressing hash set of the train triples (uint64 slots, power of two >= 2n)."""
     n = triples.shape[0]
