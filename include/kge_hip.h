@@ -204,6 +204,53 @@ int kge_relation_csr_count(const int64_t* known, int64_t n_known, const int64_t*
 int kge_relation_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_known, const void* workspace, const int64_t* rel_off,
                           int32_t* rel_ids, void* stream);
 
+/* ---- triple classification (kge_classify.hip; Socher et al. 2013): is a triple true, given its score and a per-relation threshold
+ * fitted on labelled validation triples?
+ * Key space (csrc/kge_classify_device.h): every float32 score maps to a 32-bit unsigned key, a SMALLER key being MORE plausible: the
+ * sign-flip image of its bits, complemented when higher_is_better != 0, with -0.0 folded onto +0.0 (key equality is float equality)
+ * and every NaN at 0xFFFFFFFF, above every number.  A threshold is an int64 in that space: -1 = nothing is positive, otherwise triple
+ * i is positive iff key(score_i) <= thr and score_i is not a NaN.  A threshold is always an observed score's key, never a midpoint.
+ *
+ * kge_classification_fit: scores float32 [n], rel int64 [n] (ids in [0, R); a triple with an id outside is ignored), label uint8 [n]
+ * (non-zero = a true triple).  Per relation r, over its triples sorted by (key, positives first):
+ *   thr[r]   the cut with the most correctly classified triples; a cut lies before everything (thr = -1) or after the LAST triple of a
+ *            group of equal keys whose score is a number; among cuts of equal value the earliest (the strictest threshold) wins
+ *   fit[r]   int64 [6] = {positives, negatives, correct at the chosen cut, AUC wins, AUC ties, 0}: wins = sum over the negatives of
+ *            the positives with a strictly smaller key, ties = the same with an equal key (AUC = (wins + ties / 2) / (pos * neg))
+ * A relation without triples gets thr = -1 and a zero row; n == 0 gives that for every relation.  Integer work throughout (one
+ * bitonic sort of 64-bit keys, a segmented scan over sorted positions in three launches, integer atomicMax / atomicAdd): the outputs
+ * are exact functions of the score bits and bit-identical from run to run.  Refused before any GPU call, kge_last_error() naming the
+ * entry point and the argument: n < 0 or n > 2^30 (the sort's array length is an int), R outside 1..2^20-1, a null scores / rel /
+ * label (with n > 0), thr, fit or workspace, a workspace below kge_classification_fit_workspace_bytes (0 = the sizes are refused).
+ * kge_classification_sort_length: the padded length of the sorted array (a power of two >= 256; 0 = n is refused).
+ *
+ * kge_classification_apply: pred uint8 [n] = 1 where triple i is positive under thr[rel_i], or under thr_global when seen[rel_i] == 0
+ * (a relation without validation triples; thr_global is the fit of all validation triples as ONE relation); an id outside [0, R) is
+ * predicted 0 and not counted.  With label != NULL also conf int64 [R, 4] = {tp, fp, tn, fn} per relation (zeroed here; integer
+ * atomics, the lanes of a wave that share a cell combined first).  Refused before any GPU call: n < 0, R outside 1..2^20-1, a null
+ * scores / rel / pred (with n > 0), thr or seen, labels without conf, thr_global outside -1..2^32-1. */
+int64_t kge_classification_sort_length(int64_t n);
+size_t kge_classification_fit_workspace_bytes(int64_t n, int64_t R);
+int kge_classification_fit(const float* scores, const int64_t* rel, const uint8_t* label, int64_t n, int64_t R, int32_t higher_is_better,
+                           void* workspace, size_t workspace_bytes, int64_t* thr, int64_t* fit, void* stream);
+int kge_classification_apply(const float* scores, const int64_t* rel, const uint8_t* label, int64_t n, int64_t R, int32_t higher_is_better,
+                             const int64_t* thr, const uint8_t* seen, int64_t thr_global, uint8_t* pred, int64_t* conf, void* stream);
+/* The classification negatives (kge_sampler.hip): ONE negative per positive (ph, pr, pt)[i], neg int64 [n, 3].  Philox counter
+ * offset + i, key = seed and the side decision exactly as kge_corrupt (word 0 of block 0: u > bern[r], or 0.5 without bern, corrupts
+ * the tail).  Draw a = 0, 1, ... uses word 1 of Philox block a: for a < KGE_TYPED_ATTEMPTS the replacement is
+ * ids[off[r] + ((word * len) >> 32)] from the relation's list of that side -- type_off int64 [2, R + 1], row 0 = heads, row 1 = tails,
+ * both indexing type_ids int32 (Evaluator.type_constraints) -- and for the KGE_TYPED_UNIFORM_ATTEMPTS draws after that (word * E) >> 32.
+ * An empty list has no typed draws: its uniform draws are blocks 0, 1, ....  A draw is rejected when it equals the replaced entity
+ * or the corrupted triple is in the packed set `slots` (kge_triple_set_build over train + valid + test; NULL = no set).  The loop is
+ * bounded: when every draw is rejected the corrupted column of the row is -1 and *n_failed (int64, zeroed here) counts it; so does a
+ * relation id outside [0, R).  Refused before any GPU call: n < 0, tot_entity outside 1..2^24-1, tot_relation outside 1..2^16-1 (the
+ * packed key's fields), a null ph / pr / pt / neg (with n > 0), type_off, type_ids or n_failed, n_slots no power of two >= 16. */
+#define KGE_TYPED_ATTEMPTS 16
+#define KGE_TYPED_UNIFORM_ATTEMPTS 64
+int kge_corrupt_typed(const int64_t* ph, const int64_t* pr, const int64_t* pt, int64_t n, int64_t tot_entity, int64_t tot_relation,
+                      const float* bern, const int64_t* type_off, const int32_t* type_ids, const uint64_t* slots, int64_t n_slots,
+                      uint64_t seed, uint64_t offset, int64_t* neg, int64_t* n_failed, void* stream);
+
 /* An empty kernel launch of `tag` workgroups of 64 threads ("kge::k_marker"): a boundary that shows up in a rocprofv3 kernel /
  * counter trace.  bench.py's counter passes use it to cut one process's dispatch sequence into per-configuration segments. */
 int kge_debug_marker(int32_t tag, void* stream);

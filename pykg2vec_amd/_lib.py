@@ -125,6 +125,8 @@ CONVKB_MAX_WIDTHS = 8
 TOPK_MAX = 1024   # KGE_TOPK_MAX: the most candidates kge_topk_rows returns per row
 CAND_CHUNK = 64   # KGE_CAND_CHUNK: list entries per work item of kge_rank_candidates
 REL_CHUNK = 64    # KGE_REL_CHUNK: relation ids per work item of kge_rank_relations
+TYPED_ATTEMPTS = 16           # KGE_TYPED_ATTEMPTS: typed draws of kge_corrupt_typed before it falls back
+TYPED_UNIFORM_ATTEMPTS = 64   # KGE_TYPED_UNIFORM_ATTEMPTS: uniform draws after those, then the row fails
 
 
 class ConvKBDesc(ctypes.Structure):
@@ -363,6 +365,14 @@ _SIGNATURES = {
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_relation_csr_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    "kge_classification_sort_length": (ctypes.c_int64, [ctypes.c_int64]),
+    "kge_classification_fit_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "kge_classification_fit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_classification_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_corrupt_typed": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p] * 4
+                          + [ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_last_error": (ctypes.c_char_p, []),
     "kge_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ModelDesc), ctypes.c_int64]),
     "kge_score_forward": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

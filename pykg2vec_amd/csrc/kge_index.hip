@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_bitonic_step(u64* __restrict__ keys, in
     if ((x > y) == asc) { a[lo] = y; a[hi] = x; }
 }
 
-static int sort_batched(u64* keys, long n_arrays, int P, hipStream_t s) {
+int sort_batched(u64* keys, long n_arrays, int P, hipStream_t s) {
     const int tile = P < 2048 ? P : 2048;
     const unsigned tiles = (unsigned)(n_arrays * (P / tile));
     hipLaunchKernelGGL(k_bitonic_tile, dim3(tiles), dim3(256), tile * sizeof(u64), s, keys, P, tile, 0);

@@ -337,6 +337,10 @@ int launch_sample_batch(const int64_t* triples, const int64_t* perm, int64_t sta
 int launch_step_advance(int64_t* cursor, float* hyper, int64_t batch_stride, int64_t n_batches, int64_t draws_per_batch,
                         float lr, hipStream_t s);
 
+// kge_index.hip: ascending batched bitonic sort of [n_arrays][P] 64-bit keys in place, P a power of two (LDS tiles of 2048 keys,
+// global steps above that); shared with the classification fit (kge_classify.hip)
+int sort_batched(unsigned long long* keys, long n_arrays, int P, hipStream_t s);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -104,6 +104,28 @@ int launch_sample_batch(const int64_t* triples, const int64_t* perm, int64_t sta
     return launch_sample(a, s);
 }
 
+// ---- classification negatives (kge_corrupt_typed): ONE negative per positive, the replacement drawn from the relation's own list for
+// the corrupted side and filtered against the set of ALL known triples; corrupt_typed_one bounds the redraws.  neg [n, 3]; a row
+// whose draws were all rejected carries -1 in the corrupted column and counts into *n_failed.
+__global__ __launch_bounds__(256) void k_corrupt_typed(const int64_t* __restrict__ ph, const int64_t* __restrict__ pr,
+                                                       const int64_t* __restrict__ pt, int64_t n, int64_t E, int64_t R,
+                                                       const float* __restrict__ bern, const int64_t* __restrict__ type_off,
+                                                       const int32_t* __restrict__ type_ids, const unsigned long long* __restrict__ slots,
+                                                       unsigned long long mask, unsigned long long seed, unsigned long long offset,
+                                                       int64_t* __restrict__ neg, unsigned long long* __restrict__ n_failed) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t h = ph[i], r = pr[i], t = pt[i];
+    bool tail = true;
+    const int64_t e = (r < 0 || r >= R) ? -1 :   // no list to read: the row fails
+                      corrupt_typed_one<kSamplerProbeW>(h, r, t, E, R, bern, type_off, type_ids, slots, mask, seed,
+                                                        offset + (unsigned long long)i, tail);
+    neg[3 * i] = tail ? h : e;
+    neg[3 * i + 1] = r;
+    neg[3 * i + 2] = tail ? e : t;
+    if (e < 0) atomicAdd(n_failed, 1ull);
+}
+
 // ---- device-resident step state for hipGraph replays: cursor = {start, draws, opt_step, batch_idx}, hyper = {lr,
 // step_size, bc2_sqrt}.  One thread; runs first in the captured step.
 __global__ void k_step_advance(int64_t* cursor, float* hyper, int64_t batch_stride, int64_t n_batches,
@@ -128,3 +150,32 @@ int launch_step_advance(int64_t* cursor, float* hyper, int64_t batch_stride, int
 }
 
 }  // namespace kge
+
+using namespace kge;
+
+extern "C" int kge_corrupt_typed(const int64_t* ph, const int64_t* pr, const int64_t* pt, int64_t n, int64_t tot_entity,
+                                 int64_t tot_relation, const float* bern, const int64_t* type_off, const int32_t* type_ids,
+                                 const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t offset, int64_t* neg,
+                                 int64_t* n_failed, void* stream) {
+    const char* who = "kge_corrupt_typed";
+    if (n < 0) { set_error("%s: n = %lld is negative", who, (long long)n); return -1; }
+    if (tot_entity < 1 || tot_entity >= (1 << 24)) { set_error("%s: tot_entity = %lld outside 1..2^24-1, the packed key's entity field", who, (long long)tot_entity); return -1; }
+    if (tot_relation < 1 || tot_relation >= (1 << 16)) { set_error("%s: tot_relation = %lld outside 1..2^16-1, the packed key's relation field", who, (long long)tot_relation); return -1; }
+    if (n > 0 && (!ph || !pr || !pt || !neg)) { set_error("%s: null %s", who, !ph ? "ph" : !pr ? "pr" : !pt ? "pt" : "neg"); return -1; }
+    if (!type_off || !type_ids) { set_error("%s: null %s", who, !type_off ? "type_off" : "type_ids"); return -1; }
+    if (!n_failed) { set_error("%s: null n_failed", who); return -1; }
+    if (slots && (n_slots < 16 || (n_slots & (n_slots - 1)))) { set_error("%s: n_slots = %lld is no power of two >= 16", who, (long long)n_slots); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) {
+        if (int rc = debug_check_ids(who, "ph", ph, n, 1, 0, tot_entity, s)) return rc;
+        if (int rc = debug_check_ids(who, "pr", pr, n, 1, 0, tot_relation, s)) return rc;
+        if (int rc = debug_check_ids(who, "pt", pt, n, 1, 0, tot_entity, s)) return rc;
+    }
+    hipError_t e = hipMemsetAsync(n_failed, 0, sizeof(int64_t), s);
+    if (e != hipSuccess) { set_error("%s: memset: %s", who, hipGetErrorString(e)); return -2; }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_corrupt_typed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ph, pr, pt, n, tot_entity, tot_relation, bern,
+                       type_off, type_ids, (const unsigned long long*)slots, (unsigned long long)(slots ? n_slots - 1 : 0),
+                       (unsigned long long)seed, (unsigned long long)offset, neg, (unsigned long long*)n_failed);
+    return check_launch("k_corrupt_typed");
+}

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/kge_hip.h"
 
 namespace kge {
 
@@ -120,6 +121,39 @@ __device__ __forceinline__ void corrupt_one(int64_t h, int64_t r, int64_t t, int
     }
     oh = corrupt_tail ? h : e;
     ot = corrupt_tail ? e : t;
+}
+
+// The classification negative of positive (h, r, t) for slot `ctr` (kge_corrupt_typed): counter, key and side decision as
+// corrupt_one; the replacement comes from the relation's list for that side (type_off int64 [2, R + 1]: row 0 = the heads seen with
+// r, row 1 = the tails; both index type_ids) and is rejected when it equals the replaced entity or the triple is in the set.  Draw a
+// (Philox block a) is typed for a < KGE_TYPED_ATTEMPTS and uniform over [0, E) for the KGE_TYPED_UNIFORM_ATTEMPTS after that; an
+// empty list has no typed draws (its uniform draws are blocks 0, 1, ...).  The loop is BOUNDED: the entity, or -1 when every draw
+// was rejected.
+template <int W = 1>
+__host__ __device__ __forceinline__ int64_t corrupt_typed_one(int64_t h, int64_t r, int64_t t, int64_t E, int64_t R,
+                                                              const float* __restrict__ bern, const int64_t* __restrict__ type_off,
+                                                              const int32_t* __restrict__ type_ids,
+                                                              const unsigned long long* __restrict__ slots, unsigned long long mask,
+                                                              unsigned long long seed, unsigned long long ctr, bool& corrupt_tail) {
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    Philox x = philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, k0, k1);
+    const float u = (float)(x.c[0] >> 8) * (1.0f / 16777216.0f);
+    const float prob = bern ? bern[r] : 0.5f;
+    corrupt_tail = u > prob;
+    const int64_t* off = type_off + (corrupt_tail ? R + 1 : 0);
+    const int64_t lo = off[r], len = off[r + 1] - lo;
+    const int64_t replaced = corrupt_tail ? t : h;
+    const uint32_t typed = len > 0 ? (uint32_t)KGE_TYPED_ATTEMPTS : 0u, total = typed + (uint32_t)KGE_TYPED_UNIFORM_ATTEMPTS;
+    for (uint32_t a = 0;;) {
+        const int64_t e = a < typed ? (int64_t)type_ids[lo + (int64_t)(((unsigned long long)x.c[1] * (unsigned long long)len) >> 32)]
+                                    : (int64_t)(((unsigned long long)x.c[1] * (unsigned long long)E) >> 32);
+        if (e != replaced) {
+            const unsigned long long key = corrupt_tail ? pack_triple(h, r, e) : pack_triple(e, r, t);
+            if (slots == nullptr || !set_probe<W>(slots, mask, key)) return e;
+        }
+        if (++a >= total) return -1;
+        x = philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), a, 0u, k0, k1);
+    }
 }
 
 

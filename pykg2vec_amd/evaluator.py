@@ -12,6 +12,9 @@ the known triples optionally left out (Model.score_rows + kernels.topk_rows); Tr
 (fixed negatives, type constraints, sampled ids) instead of all entities (kernels.rank_candidates; CandidateLists below).
 `rank_relations / test_relations` rank the true RELATION of every triple among all relations, raw and with the relations known for
 the pair (h, t) left out (kernels.rank_relations): MR / MRR / Hits@k of relation prediction.
+`score_triples / classification_negatives / fit_thresholds / classify / test_classification` are triple classification: per-relation
+thresholds fitted on labelled validation triples, then accuracy, per-relation accuracy and AUC (kernels.classification_fit /
+classification_apply / corrupt_typed).
 """
 import os
 import timeit
@@ -187,6 +190,8 @@ class Evaluator:
         self.tie_counts = None     # [2, n] of the last test(): candidates tied with the true entity per head / tail sweep
         self._rel_cache = {}
         self.relation_tie_counts = None   # [n] of the last test_relations(): relations tied with the true relation
+        self.thresholds = None     # ClassificationThresholds of the last fit_thresholds()
+        self.n_dropped = 0         # rows the last classification_negatives() could not find a negative for
 
     # --- single-query hooks kept for Trainer.infer_* style callers (evaluator.py:249-273)
     def test_tail_rank(self, h, r, topk=-1):
@@ -779,6 +784,206 @@ class Evaluator:
         lines.append("---------------------------------------------------------")
         _log("\n".join(lines))
         return out
+
+    # --- triple classification (Socher et al. 2013): true or false, by the score against a per-relation threshold fitted on
+    # labelled validation triples; accuracy, per-relation accuracy, AUC
+    CLASSIFY_FORWARD_CHUNK = 1 << 20     # triples per forward call of score_triples
+    CLASSIFY_MAX_DROPPED = 0.01          # share of negatives the bounded redraw may fail to produce before it is an error
+
+    def _triples_arg(self, data, n=None):
+        if isinstance(data, torch.Tensor):
+            t = data.detach().reshape(-1, 3)[:n]
+            if t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise TypeError("triples must be integer ids")
+            return t.to(device=self.config.device, dtype=torch.int64).contiguous()
+        return torch.from_numpy(_as_array(data, n)).to(self.config.device)
+
+    def score_triples(self, triples):
+        """float32 [n] on the device: the model's score of every (h, r, t) of `triples` [n, 3], through its own forward in chunks (the
+        values forward returns, bit for bit; RESCAL renormalises its tables first, as every evaluation of it does).  The projection
+        models score entities, not triples: their tail-side score_rows run in chunks bounded by PREDICT_SCRATCH_BYTES and the true
+        tail's column is gathered."""
+        trip = self._triples_arg(triples)
+        n = int(trip.shape[0])
+        out = torch.empty(n, dtype=torch.float32, device=trip.device)
+        if isinstance(self.model, ProjectionModel):
+            per = int(max(1, self.PREDICT_SCRATCH_BYTES // (self.PREDICT_ROW_ITEM_BYTES * int(self.config.tot_entity))))
+            for a in range(0, n, per):
+                b = min(n, a + per)
+                out[a:b] = self.model.score_rows(trip[a:b], 0).gather(1, trip[a:b, 2:3]).reshape(-1)
+            return out
+        if getattr(self.model, "kernel_name", None) == "rescal":
+            self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+        for a in range(0, n, self.CLASSIFY_FORWARD_CHUNK):
+            b = min(n, a + self.CLASSIFY_FORWARD_CHUNK)
+            with torch.no_grad():
+                out[a:b] = self.model.forward(trip[a:b, 0].contiguous(), trip[a:b, 1].contiguous(), trip[a:b, 2].contiguous()).reshape(-1)
+        return out
+
+    def _classification_sampler(self):
+        """(packed set of train + valid + test, type_off [2, R + 1], type_ids, bern table or None), built once per Evaluator."""
+        if getattr(self, "_cls_sampler", None) is None:
+            known = self._known_triples()
+            if known is None:
+                raise K.L.KgeHipError("Evaluator: classification negatives are filtered against train + valid + test, which needs the "
+                                      "three splits in the knowledge-graph cache")
+            dev = known.device
+            ranges, domains = self.type_constraints()
+            off = torch.stack([domains.off, ranges.off + int(domains.ids.numel())]).contiguous().to(dev)   # row 0 heads, row 1 tails
+            ids = torch.cat([domains.ids, ranges.ids]).contiguous().to(dev)
+            bern = None
+            if getattr(self.config, "sampling", "uniform") == "bern":
+                from .generator import bern_table, relation_property
+                train = _as_array(self.config.knowledge_graph.read_cache_data('triplets_train'), None)
+                bern = torch.from_numpy(bern_table(relation_property(train, self.config.tot_relation))).to(dev)
+            self._cls_sampler = (self.K.triple_set_build(known), off, ids, bern)
+        return self._cls_sampler
+
+    def _draw_negatives(self, pos, seed, typed):
+        """(neg int64 [n, 3] with -1 in the corrupted column of a failed row, number of failed rows) for the positives `pos`."""
+        slots, off, ids, bern = self._classification_sampler()
+        E, R = int(self.config.tot_entity), int(self.config.tot_relation)
+        ph, pr, pt = (pos[:, i].contiguous() for i in range(3))
+        if typed:
+            neg, failed = self.K.corrupt_typed(ph, pr, pt, E, R, bern, off, ids, slots, seed, 0)
+            return neg, int(failed.item())
+        nh, nr, nt = self.K.corrupt(ph, pr, pt, 1, E, bern, slots, seed, 0)
+        return torch.stack([nh, nr, nt], 1).contiguous(), 0
+
+    def _labelled_pairs(self, data, n, negatives, seed, typed=True):
+        """(positives [m, 3], negatives [m, 3], rows dropped): the first n triples of `data` with one negative each -- the given ones,
+        or drawn.  A row whose bounded redraw failed is dropped together with its positive."""
+        pos = self._triples_arg(data, n)
+        if negatives is not None:
+            neg = self._triples_arg(negatives)
+            if neg.shape[0] != pos.shape[0]:
+                raise ValueError("%d negatives for %d positives: one negative per positive" % (neg.shape[0], pos.shape[0]))
+            return pos, neg, 0
+        neg, failed = self._draw_negatives(pos, seed, typed)
+        if failed:
+            if failed > self.CLASSIFY_MAX_DROPPED * pos.shape[0]:
+                raise K.L.KgeHipError("classification negatives: %d of %d positives found no negative within the bounded redraw (more than "
+                                      "%g %%): the known-triple set leaves too little room" % (failed, pos.shape[0], 100 * self.CLASSIFY_MAX_DROPPED))
+            keep = (neg >= 0).all(1)
+            pos, neg = pos[keep].contiguous(), neg[keep].contiguous()
+            _log("classification negatives: dropped %d of %d rows whose bounded redraw found no negative" % (failed, failed + pos.shape[0]))
+        return pos, neg, failed
+
+    def classification_negatives(self, data, n, seed=0, typed=True):
+        """int64 [m, 3] on the device: one false triple per triple of the first n of `data`, head or tail replaced as the training
+        sampler decides.  typed: the replacement comes from the entities seen on that side of the relation in the training split
+        (Socher et al.'s protocol: a negative that is hard for the right reason), falling back to a uniform draw when the list runs
+        out (kernels.corrupt_typed); else the training sampler's uniform draw (kernels.corrupt).  Either way a negative is never a
+        known triple of train + valid + test, and a pure function of (seed, row).  Rows for which the bounded redraw found nothing are
+        dropped (m < n, the count is logged and kept in `n_dropped`); more than CLASSIFY_MAX_DROPPED of the rows is an error."""
+        _, neg, self.n_dropped = self._labelled_pairs(data, n, None, seed, typed)
+        return neg
+
+    def _labelled_scores(self, pos, neg):
+        m = int(pos.shape[0])
+        trip = torch.cat([pos, neg]).contiguous()
+        label = torch.zeros(2 * m, dtype=torch.uint8, device=trip.device)
+        label[:m] = 1
+        return self.score_triples(trip), trip[:, 1].contiguous(), label
+
+    def fit_thresholds(self, data=None, n=None, negatives=None, seed=0):
+        """Fit, store in `self.thresholds` and return the per-relation thresholds (ClassificationThresholds) on the first n triples
+        of `data` (default: the validation split) and one negative each (`negatives` [n, 3], default: classification_negatives with
+        `seed`).  A relation without a triple there has seen == False and is classified by the global threshold, the fit of all the
+        triples as one relation.  Exact: a threshold is an observed score, ties cut after the whole tie group, equal cuts -> the
+        strictest (kernels.classification_fit)."""
+        pos, neg, _ = self._labelled_pairs(self.eval_data if data is None else data, n, negatives, seed)
+        scores, rel, label = self._labelled_scores(pos, neg)
+        R, hib = int(self.config.tot_relation), bool(self.model.higher_is_better)
+        thr, fit = self.K.classification_fit(scores, rel, label, R, higher_is_better=hib)
+        gthr, gfit = self.K.classification_fit(scores, torch.zeros_like(rel), label, 1, higher_is_better=hib)
+        self.thresholds = ClassificationThresholds(thr.cpu().numpy(), fit.cpu().numpy(), int(gthr.cpu()[0]), gfit.cpu().numpy()[0], hib)
+        return self.thresholds
+
+    def _apply_thresholds(self, scores, rel, label, th):
+        dev = scores.device
+        return self.K.classification_apply(scores, rel, torch.from_numpy(th.key).to(dev), torch.from_numpy(th.seen.astype(np.uint8)).to(dev),
+                                           th.global_key, label=label, higher_is_better=th.higher_is_better)
+
+    def classify(self, triples, thresholds=None):
+        """bool [n] on the device: is (h, r, t) true under the thresholds (default: the stored ones, fitted on the validation split on
+        first use)?"""
+        th = thresholds or getattr(self, "thresholds", None) or self.fit_thresholds()
+        trip = self._triples_arg(triples)
+        pred, _ = self._apply_thresholds(self.score_triples(trip), trip[:, 1].contiguous(), None, th)
+        return pred.to(torch.bool)
+
+    def test_classification(self, data=None, n=None, negatives=None, seed=1, epoch=None):
+        """Triple classification metrics over the first n triples of `data` (default: the test split) and one negative each: {'accuracy',
+        'accuracy_per_relation' [R] (NaN without a test triple), 'auc', 'auc_per_relation' [R] (NaN without both labels), 'confusion'
+        int64 [R, 4] = {tp, fp, tn, fn}, 'n_dropped'}.  Thresholds: the stored ones, fitted on the validation split on first use.  The
+        AUC is threshold-free: (wins + ties / 2) / (positives * negatives) per relation, summed over relations, on the test scores."""
+        t0 = timeit.default_timer()
+        th = getattr(self, "thresholds", None) or self.fit_thresholds()
+        pos, neg, dropped = self._labelled_pairs(self.test_data if data is None else data, n, negatives, seed)
+        scores, rel, label = self._labelled_scores(pos, neg)
+        _, conf = self._apply_thresholds(scores, rel, label, th)
+        R = int(self.config.tot_relation)
+        _, fit = self.K.classification_fit(scores, rel, label, R, higher_is_better=th.higher_is_better)
+        conf, fit = conf.cpu().numpy(), fit.cpu().numpy()
+        out = classification_metrics(conf, fit)
+        out['n_dropped'] = dropped
+        unseen = int(((conf.sum(1) > 0) & ~th.seen).sum())
+        lines = ["", "------Triple Classification Results for %s: Epoch: %s --- time: %.2f------------" % (
+            getattr(self.config, "dataset_name", "?"), epoch, timeit.default_timer() - t0),
+            "--# of positives, # of relations        : %d, %d" % (pos.shape[0], R),
+            "--relations on the global threshold     : %d" % unseen,
+            "--dropped rows (no negative found)      : %d" % dropped,
+            "--accuracy                              : %.4f" % out['accuracy'],
+            "--mean per-relation accuracy            : %.4f" % (np.nanmean(out['accuracy_per_relation']) if conf.sum() else float('nan')),
+            "--auc                                   : %.4f" % out['auc'],
+            "---------------------------------------------------------"]
+        _log("\n".join(lines))
+        return out
+
+
+def classification_key_to_score(key, higher_is_better):
+    """float32 scores of classification keys (csrc/kge_classify_device.h), NaN where the key is -1 (no threshold)."""
+    key = np.asarray(key, dtype=np.int64)
+    k = (key & 0xFFFFFFFF).astype(np.uint32)
+    asc = ~k if higher_is_better else k
+    bits = np.where(asc & np.uint32(0x80000000), asc ^ np.uint32(0x80000000), ~asc).astype(np.uint32)
+    out = bits.view(np.float32).copy()
+    out[key < 0] = np.nan
+    return out
+
+
+class ClassificationThresholds:
+    """Fitted classification thresholds as plain numpy (picklable): `key` int64 [R] in the key space of kge_classification_fit (-1 =
+    nothing is positive), `value` float32 [R] the same as scores (a triple of relation r is true iff its score is at least as plausible
+    as value[r]; NaN where key is -1), `seen` bool [R] (the relation had a validation triple; the others use `global_key` /
+    `global_value`, the fit of all validation triples as one relation), `fit` int64 [R, 6] and `global_fit` [6] = {positives, negatives,
+    correct at the cut, AUC wins, AUC ties, 0}, `higher_is_better` the orientation the keys were built with."""
+
+    def __init__(self, key, fit, global_key, global_fit, higher_is_better):
+        self.key = np.ascontiguousarray(key, dtype=np.int64)
+        self.fit = np.ascontiguousarray(fit, dtype=np.int64)
+        self.seen = (self.fit[:, 0] + self.fit[:, 1]) > 0
+        self.global_key = int(global_key)
+        self.global_fit = np.ascontiguousarray(global_fit, dtype=np.int64)
+        self.higher_is_better = bool(higher_is_better)
+        self.value = classification_key_to_score(self.key, self.higher_is_better)
+        self.global_value = float(classification_key_to_score([self.global_key], self.higher_is_better)[0])
+
+
+def classification_metrics(conf, fit):
+    """The metrics dict of test_classification from conf int64 [R, 4] = {tp, fp, tn, fn} and the test scores' fit rows [R, 6]."""
+    conf, fit = np.asarray(conf, dtype=np.int64), np.asarray(fit, dtype=np.int64)
+    tot = conf.sum(1)
+    right = conf[:, 0] + conf[:, 2]
+    pairs = fit[:, 0] * fit[:, 1]
+    twice = 2 * fit[:, 3] + fit[:, 4]       # 2 * (wins + ties / 2): integers until the one division
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return {'accuracy': float(right.sum()) / float(tot.sum()) if tot.sum() else float('nan'),
+                'accuracy_per_relation': np.where(tot > 0, right / np.maximum(tot, 1), np.nan),
+                'auc': float(twice.sum()) / float(2 * pairs.sum()) if pairs.sum() else float('nan'),
+                'auc_per_relation': np.where(pairs > 0, twice / np.maximum(2 * pairs, 1), np.nan),
+                'confusion': conf}
 
 
 class CandidateLists:

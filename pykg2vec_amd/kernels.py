@@ -1069,6 +1069,69 @@ def rank_relations(desc, triples, skip_off=None, skip_ids=None, skip_sorted=Fals
     return counts
 
 
+TYPED_ATTEMPTS, TYPED_UNIFORM_ATTEMPTS = L.TYPED_ATTEMPTS, L.TYPED_UNIFORM_ATTEMPTS
+
+
+def classification_fit(scores, rel, label, n_relations, higher_is_better=False):
+    """Per-relation classification thresholds of labelled scores (kge_classification_fit): (thr int64 [R], fit int64 [R, 6]).
+    scores float32 [n], rel int64 [n], label uint8 [n] (non-zero = true triple).  thr[r] is a KEY (include/kge_hip.h), -1 = nothing is
+    positive; fit[r] = {positives, negatives, correct at the chosen cut, AUC wins, AUC ties, 0}.  Exact and bit-identical run to run."""
+    n, R = int(scores.numel()), int(n_relations)
+    if rel.numel() != n or label.numel() != n:
+        raise ValueError("scores, rel and label hold %d, %d and %d elements: one of each per triple" % (n, rel.numel(), label.numel()))
+    dev = scores.device
+    lib = L.load()
+    thr = torch.empty(max(R, 0), dtype=torch.int64, device=dev)
+    fit = torch.empty((max(R, 0), 6), dtype=torch.int64, device=dev)
+    nbytes = lib.kge_classification_fit_workspace_bytes(n, R)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    L.check(lib.kge_classification_fit(_dev(scores, torch.float32, "scores"), _ids(rel, "rel"), _dev(label, torch.uint8, "label"), n, R,
+                                       1 if higher_is_better else 0, _dev(ws, torch.uint8, "workspace"), nbytes,
+                                       _ids(thr, "thr"), _ids(fit, "fit"), _stream()), "kge_classification_fit")
+    return thr, fit
+
+
+def classification_apply(scores, rel, thr, seen, thr_global, label=None, higher_is_better=False):
+    """Classify scores against fitted thresholds (kge_classification_apply): (pred uint8 [n], conf int64 [R, 4] = {tp, fp, tn, fn} per
+    relation, or None without labels).  thr int64 [R]; seen uint8 [R]: 0 = the relation had no validation triple and uses thr_global."""
+    n, R = int(scores.numel()), int(thr.numel())
+    if rel.numel() != n or (label is not None and label.numel() != n):
+        raise ValueError("scores, rel and label must hold one element per triple")
+    if seen.numel() != R:
+        raise ValueError("seen holds %d flags for %d thresholds" % (seen.numel(), R))
+    dev = scores.device
+    pred = torch.empty(n, dtype=torch.uint8, device=dev)
+    conf = None if label is None else torch.empty((R, 4), dtype=torch.int64, device=dev)
+    L.check(L.load().kge_classification_apply(_dev(scores, torch.float32, "scores"), _ids(rel, "rel"),
+                                              None if label is None else _dev(label, torch.uint8, "label"), n, R,
+                                              1 if higher_is_better else 0, _ids(thr, "thr"), _dev(seen, torch.uint8, "seen"),
+                                              int(thr_global), _dev(pred, torch.uint8, "pred"),
+                                              None if conf is None else _ids(conf, "conf"), _stream()), "kge_classification_apply")
+    return pred, conf
+
+
+def corrupt_typed(ph, pr, pt, tot_entity, tot_relation, bern_prob, type_off, type_ids, slots, seed, offset):
+    """One classification negative per positive (kge_corrupt_typed): (neg int64 [n, 3], n_failed int64 [1], both on the device).
+    type_off int64 [2, R + 1] (row 0 = heads, row 1 = tails) + type_ids int32: the per-relation lists the replacement is drawn from;
+    slots: the packed set of every known triple (triple_set_build), or None.  A row whose draws were all rejected carries -1 in the
+    corrupted column and counts into n_failed: the redraw loop is bounded."""
+    n = int(ph.numel())
+    dev = ph.device
+    if tuple(type_off.shape) != (2, int(tot_relation) + 1):
+        raise ValueError("type_off must be [2, tot_relation + 1] (got %s)" % (tuple(type_off.shape),))
+    if type_ids.numel() == 0:   # every list is empty: a pointer the library accepts, never read
+        type_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+    neg = torch.empty((n, 3), dtype=torch.int64, device=dev)
+    failed = torch.empty(1, dtype=torch.int64, device=dev)
+    bp = _dev(bern_prob, torch.float32, "bern_prob") if bern_prob is not None else None
+    sp = ctypes.c_void_p(slots.data_ptr()) if slots is not None else None
+    L.check(L.load().kge_corrupt_typed(_ids(ph, "ph"), _ids(pr, "pr"), _ids(pt, "pt"), n, int(tot_entity), int(tot_relation), bp,
+                                       _ids(type_off, "type_off"), _dev(type_ids, torch.int32, "type_ids"), sp,
+                                       slots.numel() if slots is not None else 0, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                       _ids(neg, "neg"), _ids(failed, "n_failed"), _stream()), "kge_corrupt_typed")
+    return neg, failed
+
+
 def triple_set_build(triples):
     """Open-addressing hash set of the train triples (uint64 slots, power of two >= 2n)."""
     n = triples.shape[0]
