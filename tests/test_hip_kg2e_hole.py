@@ -224,10 +224,14 @@ SHAPES = [(model, d, B) for model in ("kg2e", "hole") for d in (50, 100, 150) fo
 
 @pytest.mark.parametrize("model,d,B", SHAPES)
 def test_step_vs_float64_restatement(hip, model, d, B):
+    check_step_vs_float64(hip, model, 3000, 40, d, B, seed=d * 7 + B)
+
+
+def check_step_vs_float64(hip, model, E, R, d, B, seed):
+    """Forward energies and one fused step of a random model against the float64 restatement (energy64 + autograd)."""
     from pykg2vec_amd import kernels as K
     from pykg2vec_amd.trainer import Trainer
-    E, R = 3000, 40
-    m, hp = random_case(hip, model, E, R, d, seed=d * 7 + B)
+    m, hp = random_case(hip, model, E, R, d, seed=seed)
     batch = batch_of(np.random.default_rng(B + d), E, R, B)
     desc = m.make_desc()
     with torch.no_grad():

@@ -387,11 +387,15 @@ def check_rank_all(env, first, grouped_min=None, tag=""):
 @gpu
 @pytest.mark.parametrize("family,width", FAMILIES, ids=IDS)
 def test_query_and_entity_count_edges(family, width):
+    run_count_edges(family, width, SET_A)
+
+
+def run_count_edges(family, width, cases):
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     from pykg2vec_amd import _lib as L
     report, refusals = [], []
     models = {}
-    for n, E in SET_A:
+    for n, E in cases:
         rng = np.random.default_rng(1000 * E + n)
         q = ref.distinct_queries(rng, n, E, R)
         known = ref.known_triples(rng, q, E, R)
@@ -423,7 +427,8 @@ def test_query_and_entity_count_edges(family, width):
         print("REFUSED", line)
     # the refusals are recorded here so that a new one is seen: QuatE's rel_{s,x,y,z} tables carry tot_entity rows (the reference's
     # quirk) and are indexed by relation ids, so the library refuses E < R; every other family ranks at E = 1 and E = 2
-    assert [(f, E) for f, _, E, _, _ in refusals] == ([("quate", 1), ("quate", 2)] if family == "quate" else []), refusals
+    small = sorted({E for _, E in cases if E < 65})
+    assert [(f, E) for f, _, E, _, _ in refusals] == ([("quate", E) for E in small] if family == "quate" else []), refusals
     assert all("indexed by relation ids" in msg for *_, msg in refusals), refusals
     worst = {}
     for line in report:
@@ -499,3 +504,50 @@ def test_planted_copies_tie_on_the_forced_sweeps(family, width, gemm, monkeypatc
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     monkeypatch.setenv("KGE_EVAL_GEMM", gemm)
     run_planted(family, width, 40)
+
+
+# ---------------------------------------------------------------- set C: wide sweeps
+# The two widths above keep the sweep width K (csrc/kge_eval.hip:68-77 sweep_K: d, 2d or 4d by model; launch_dot_eval callers: d + 1 for
+# SME / SME_BL, 2d for HoLE, 8d for OctonionE) at or below 128, so the K splits of the candidate layout kernels (k_eval_prepare4: every
+# segment % 4 == 0, chunks of 128 over grid.y; k_eval_prepare: chunks of 64) and the padded tail beyond K (Kpad: K rounded up to 8, to 16
+# in the dot form) never ran with more than one chunk.  Four further widths per family put K on (a) a value % 4 != 0 just above 64 (the
+# dword layout kernel with a K split of two), (b) exactly 128, (c) 132 (two 128-chunks of k_eval_prepare4), (d) 260 -- or, where K is an
+# even multiple of d, on the nearest values the family can take.  The comparison is set A's at (n, E) = (17, 65) and set B's at n = 40:
+# integer ranks and tie counts equal the numpy count over the family's own rows, no mismatch allowed.
+K_TIMES_2 = ("complex", "complexn3", "rotate", "analogy", "cp", "simple", "simple_ignr", "hole")
+SEMANTIC = ("sme", "sme_bl", "slm")
+SET_C_LIMITS = {     # (family, width) -> the limit that rules the width out, as the sources state it
+    ("ntn", 260): "NTN sweep: ent_hidden_size and rel_hidden_size <= 256 (csrc/kge_ntn_eval.hip:275)",
+    ("analogy", 33): "ANALOGY needs an even hidden size (csrc/kge_api.hip:60), so its K = 2d is always a multiple of 4",
+}
+for _f in ("transr_l1", "transr_l2"):
+    for _w in (132, 260):
+        SET_C_LIMITS[(_f, _w)] = "TransR: hidden sizes <= TR_MAXD = 128 (csrc/kge_transr.hip:24, :274)"
+for _f in SEMANTIC:
+    for _w in (127, 131, 259):
+        SET_C_LIMITS[(_f, _w)] = "SLM / SME / SME_BL take hidden sizes 1..kSemMaxDim = 100 (csrc/kge_semantic.hip:43, :89)"
+
+
+def set_c_widths(family):
+    if family in K_TIMES_2:
+        return (33, 64, 66, 130)          # K = 66, 128, 132, 260
+    if family == "quate":
+        return (17, 33, 65)               # K = 68, 132, 260 (K = 128 is width 32 of the sets above)
+    if family == "octonione":
+        return (9, 16, 17, 33)            # K = 8d = 72, 128, 136, 264
+    if family in SEMANTIC:
+        return (64, 100, 127, 131, 259)   # K = d + 1 = 65, 101 (the widest row the family takes), 128, 132, 260
+    return (65, 128, 132, 260)            # K = d
+
+
+SET_C = [pytest.param(f, w, id="%s-w%d" % (f, w),
+                      marks=[pytest.mark.skip(reason=SET_C_LIMITS[(f, w)])] if (f, w) in SET_C_LIMITS else [])
+         for f in TWO_WIDTHS for w in set_c_widths(f)]
+
+
+@gpu
+@pytest.mark.parametrize("family,width", SET_C)
+def test_wide_sweeps_count_and_tie_exactly(family, width):
+    run_count_edges(family, width, [(17, 65)])
+    run_planted(family, width, 40)
+

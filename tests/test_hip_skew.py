@@ -11,20 +11,20 @@ where a_r = sum over the row's incidences of |that incidence's contribution| (fl
 it).  The a_r term is needed on short rows too: TransE's per-incidence contributions pass the normalisation backward and are ~10 for
 rows of norm ~0.1, while five of them can cancel to 1e-3 -- the fp32 numpy oracle itself misses atol 2e-6 there.  a_r comes from the
 oracle: every incidence is moved onto its own fresh copy of its row, so the dense gradient of the copies is the per-incidence
-contributions.  Hub rows (c_r > 8) must exist in every case and their largest deviations are recorded."""
+contributions.  Hub rows (c_r > 8) must exist in every case and their largest deviations are recorded.  The bar itself (the oracle
+bounds, the ambiguity allowance, the tolerance line) lives in tests/step_bar.py, shared with tests/test_hip_width_edges.py."""
 import numpy as np
 import pytest
 import torch
 
 import kge_oracle as ko
 from golden_util import skewed_triples
+from step_bar import NEAR_MARGIN, NEAR_ZERO, tolerance   # noqa: F401  (the bar's constants, as this file has always named them)
+from step_bar import ambiguity_allowance as _ambiguity_allowance, hub_bounds as _hub_bounds, one_step as _one_step, sampled as _sampled
 
 pytestmark = pytest.mark.gpu
 
 SHORT_ROW = 8          # rows with more incidences than one work item takes are the hub rows
-NEAR_MARGIN = 1e-5     # hinge pairs this close to the margin may be decided differently in fp32 and float64
-NEAR_ZERO = 1e-6       # ... and TransE L1 residual components this close to 0 may take either sign
-PAIRWISE = ("transe", "transh", "rotate", "rescal")
 
 
 @pytest.fixture(scope="module")
@@ -60,120 +60,6 @@ def _trainer(hip, model, hp, E, R, B, world, env, monkeypatch, segment=None):
     return tr, m
 
 
-def _one_step(hip, tr, m):
-    """Run one epoch of one batch; the updated tables (float32 numpy) and the flat state."""
-    loss = tr.train_model_epoch(0)
-    tr.sync_model()
-    torch.cuda.synchronize()
-    tables = {k[:-len(".weight")]: p.detach().cpu().numpy().copy() for k, p in hip.table_parameters(m)}
-    state = None if tr.flat.state1 is None else tr.flat.state1.clone()
-    return tables, tr.flat.param.clone(), state, float(loss)
-
-
-def _columns(model, batch, E):
-    """(entity id arrays, relation id arrays) of a batch in its layout: the arrays every row reference comes from."""
-    if model in PAIRWISE:
-        ph, pr, pt, nh, nr, nt = batch
-        return [ph, pt, nh, nt], [pr, nr]
-    h, r, t, _y = batch
-    return [h, t], [r]
-
-
-def _hub_bounds(model, P, batch, hp, E, R):
-    """Float64 oracle gradient, per-row incidence counts and per-element a_r of every row."""
-    _loss, G64, scores, _ = ko.train_step_grads(model, P, batch, dtype=np.float64, **hp)
-    ent_cols, rel_cols = _columns(model, batch, E)
-    cnt = {"ent": np.bincount(np.concatenate(ent_cols), minlength=E), "rel": np.bincount(np.concatenate(rel_cols), minlength=R)}
-    side_of = {k: ("ent" if v.shape[0] == E else "rel") for k, v in P.items()}
-    assert E != R and all(v.shape[0] in (E, R) for v in P.values())
-    # every incidence gets its own fresh copy of its row, appended to the table
-    touched = {s: np.flatnonzero(cnt[s] > 0) for s in cnt}
-    n_rows = {"ent": E, "rel": R}
-    copies, new_cols = {}, {}
-    for s, cols in (("ent", ent_cols), ("rel", rel_cols)):
-        nxt = n_rows[s]
-        src, out = [], []
-        for col in cols:
-            col = np.asarray(col, dtype=np.int64).copy()
-            at = np.flatnonzero(np.isin(col, touched[s]))
-            src.append(col[at])
-            col[at] = nxt + np.arange(len(at))
-            nxt += len(at)
-            out.append(col)
-        copies[s] = np.concatenate(src) if src else np.zeros(0, np.int64)
-        new_cols[s] = out
-    Pext = {k: np.concatenate([np.asarray(v, np.float64), np.asarray(v, np.float64)[copies[side_of[k]]]]) for k, v in P.items()}
-    if model in PAIRWISE:
-        ph, pt, nh, nt = new_cols["ent"]
-        pr, nr = new_cols["rel"]
-        ext_batch = (ph, pr, pt, nh, nr, nt)
-    else:
-        h, t = new_cols["ent"]
-        (r,) = new_cols["rel"]
-        ext_batch = (h, r, t, batch[3])
-    _l2, Gext, _s, _ = ko.train_step_grads(model, Pext, ext_batch, dtype=np.float64, **hp)
-    assert np.isclose(_l2, _loss, rtol=1e-12), (_l2, _loss)
-    a = {}
-    for k, v in P.items():
-        s = side_of[k]
-        acc = np.zeros((v.shape[0],) + v.shape[1:], np.float64)
-        np.add.at(acc, copies[s], np.abs(Gext[k][n_rows[s]:]))
-        a[k] = acc
-        # the copies' contributions sum to the rows' gradient: a check of the construction itself
-        summed = np.zeros_like(acc)
-        np.add.at(summed, copies[s], Gext[k][n_rows[s]:])
-        tv = touched[s]
-        assert np.allclose(summed[tv], G64[k][tv], atol=1e-12, rtol=1e-9), k
-    return G64, scores, cnt, side_of, a, (G64, side_of, new_cols, Gext, n_rows)
-
-
-def _l1_residual(P, h, r, t):
-    """TransE's L1 residual u = a^ + b^ - c^ (float64; its signs are the L1 gradient) and the saved normalisation terms."""
-    P = {k: np.asarray(v, np.float64) for k, v in P.items()}
-    a, b, c = P["ent_embeddings"][h], P["rel_embeddings"][r], P["ent_embeddings"][t]
-    return (a, b, c), ko._trans_tail(a, b, c, True)[1]
-
-
-def _ambiguity_allowance(model, P, scores, batch, hp, ctx):
-    """Per-element widening of the bar for what fp32 and float64 may legitimately decide differently, and how many pairs that is.
-    Hinge pairs within NEAR_MARGIN of the margin: the pair's whole contribution may be present or not -- its rows get 2 x |that
-    incidence's contribution| (the row copies give it).  TransE L1 residual components within NEAR_ZERO of 0 may take either sign:
-    the rows get |the gradient of flipping those signs|, through the normalisation backward.  No row is left out."""
-    G64, side_of, cols_ext, Gext, n_rows = ctx
-    allow = {k: np.zeros_like(v) for k, v in G64.items()}
-    if model not in ("transe", "transh", "rescal"):
-        return allow, 0
-    pos, neg = scores
-    v = pos + float(hp["margin"]) - neg
-    near = np.abs(v) < NEAR_MARGIN
-    ph, pr, pt, nh, nr, nt = batch
-    ents = (ph, pt, nh, nt)
-    rels = (pr, nr)
-    if near.any():
-        idx = np.flatnonzero(near)
-        for k in G64:
-            s = side_of[k]
-            for col, col_ext in zip(ents if s == "ent" else rels, cols_ext[s]):
-                np.add.at(allow[k], np.asarray(col)[idx], 2.0 * np.abs(Gext[k][np.asarray(col_ext)[idx]]))
-    n_amb = near.copy()
-    if model == "transe" and hp.get("l1_flag"):
-        _loss, dpos, dneg = ko.pairwise_hinge(pos, neg, hp["margin"])
-        eps = np.float64(ko.EPS_NORMALIZE)
-        for (h, r, t), ds in (((ph, pr, pt), dpos), ((nh, nr, nt), dneg)):
-            (a, b, c), (ah, na, bh, nb, ch, nc, u) = _l1_residual(P, h, r, t)
-            flip = (np.abs(u) < NEAR_ZERO) & (ds != 0)[:, None]
-            rows = np.flatnonzero(flip.any(1))
-            n_amb[rows] = True
-            if not len(rows):
-                continue
-            dg = 2.0 * flip[rows] * np.abs(ds[rows])[:, None]
-            for arr, (xh, nx, x) in ((h, (ah, na, a)), (r, (bh, nb, b)), (t, (ch, nc, c))):
-                d = np.abs(ko._normalize_bwd(xh[rows], nx[rows], ko._norm_rows(x[rows]) > eps, dg))
-                key = "rel_embeddings" if arr is r else "ent_embeddings"
-                np.add.at(allow[key], np.asarray(arr)[rows], d)
-    return allow, int(n_amb.sum())
-
-
 def _check(hip, key, model, P, before, after, batch, hp, E, R, n_pairs, flat_grad=None, multi=None):
     """Per-row tolerance comparison of the step's gradient (before - after, or the given one) with the float64 oracle.  `multi`: rows
     (owner-index numbering, relations after the E entities) the index sends through global partial sums -- they must be compared."""
@@ -186,9 +72,7 @@ def _check(hip, key, model, P, before, after, batch, hp, E, R, n_pairs, flat_gra
         s = side_of[k]
         got = flat_grad[k] if flat_grad is not None else before[k].astype(np.float64) - after[k].astype(np.float64)
         g = G64[k]
-        c = cnt[s].reshape((-1,) + (1,) * (g.ndim - 1)).astype(np.float64)
-        # (+ the rounding of the stored update p - g itself, which before - after cannot undo)
-        tol = 2e-6 + 2e-4 * np.abs(g) + c * 2.0 ** -23 * a[k] + (0.0 if after is None else 2.0 ** -24 * np.abs(after[k])) + allow[k]
+        tol = tolerance(g, cnt[s], a[k], None if after is None else after[k], allow[k])     # tests/step_bar.py
         bad = np.abs(got - g) > tol
         if bad.any():
             rows = np.flatnonzero(bad.reshape(len(g), -1).any(1))
@@ -210,13 +94,6 @@ def _check(hip, key, model, P, before, after, batch, hp, E, R, n_pairs, flat_gra
     if multi is not None:   # ... and at least one of the two heaviest rows is one the index sends through global partial sums
         assert {int(cnt["ent"].argmax()), E + int(cnt["rel"].argmax())} & set(np.asarray(multi).tolist()), "no top row in multi"
     return worst
-
-
-def _sampled(tr, B, neg, E, pointwise):
-    from pykg2vec_amd import kernels as K
-    gen = tr.generator
-    return tuple(x.cpu().numpy() for x in K.sample_batch(gen.triples, gen.perm, 0, B, neg, E, gen.bern, gen.slots, gen.seed, 0,
-                                                       pointwise=pointwise))
 
 
 def _run_case(hip, monkeypatch, key, model, hp, E, R, B, world, env, path, segment=None, pointwise=False, neg=1,
