@@ -20,9 +20,11 @@
 //            What overflowed at first were scalar registers, hence: rows are loaded without lane masks (load_row_nomask), the
 //            arguments are read from the workspace copy, and ONE walk loop serves the true entity and the candidates, so that
 //            model_fwd (RotatE: 2 * NCH sincosf chains) is instantiated once.
+//   shared   with kge_relations.hip, in kge_rank_common.h: load_row_nomask, the list of row-kernel models, and the entry point's
+//            opening (rank_entry_checks, rank_counts_begin); what is checked here is the lists' own.
 // kge_rank_lists_from_scores is the counting half alone, for the models whose scores come from their own batch scorer: one wave
 // per segment of scores, integer wave reductions, plain stores.
-#include "kge_row_kernels.h"
+#include "kge_rank_common.h"
 
 namespace kge {
 
@@ -44,22 +46,6 @@ __device__ __forceinline__ void cand_span(const CandArgs& a, int64_t q, int64_t&
     lo = hi = 0;
     if (l >= 0 && l < a.n_lists) { lo = a.cand_off[l]; hi = a.cand_off[l + 1]; }
     if (hi < lo) hi = lo;
-}
-
-// load_row's values with no lane mask: a padding element reads the row's last float and is zeroed with an integer AND (+0.0, as
-// load_row gives).  The e < dim tests of load_row are loop-invariant lane masks that the compiler keeps in scalar register pairs
-// for the whole kernel, 2 * NCH of them; next to this kernel's arguments they no longer fit.
-template <int G, int NCH>
-__device__ __forceinline__ void load_row_nomask(float (&x)[NCH], const float* __restrict__ row, int dim, int gl) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int e = c * G + gl;
-        int keep = (e - dim) >> 31;   // all ones where e < dim
-        asm volatile("" : "+v"(keep));   // (opaque: otherwise it is folded back into a test, i.e. a lane mask)
-        int ec = min(e, dim - 1);
-        asm volatile("" : "+v"(ec));     // (opaque: redone per row, or NCH clamped indices stay live in vector registers)
-        x[c] = __int_as_float(__float_as_int(row[ec]) & keep);
-    }
 }
 
 }  // namespace
@@ -220,24 +206,6 @@ __global__ void __launch_bounds__(kBlock) k_rank_lists_from_scores(const T* __re
     }
 }
 
-#define KGE_DISPATCH_ROW_MODELS(model_id, BODY)                 \
-    switch (model_id) {                                         \
-        KGE_FOR_MODEL(KGE_TRANSE, BODY)                         \
-        KGE_FOR_MODEL(KGE_TRANSH, BODY)                         \
-        KGE_FOR_MODEL(KGE_TRANSD, BODY)                         \
-        KGE_FOR_MODEL(KGE_TRANSM, BODY)                         \
-        KGE_FOR_MODEL(KGE_ROTATE, BODY)                         \
-        KGE_FOR_MODEL(KGE_DISTMULT, BODY)                       \
-        KGE_FOR_MODEL(KGE_COMPLEX, BODY)                        \
-        KGE_FOR_MODEL(KGE_ANALOGY, BODY)                        \
-        KGE_FOR_MODEL(KGE_CP, BODY)                             \
-        KGE_FOR_MODEL(KGE_SIMPLE, BODY)                         \
-        KGE_FOR_MODEL(KGE_SIMPLE_IGNR, BODY)                    \
-        KGE_FOR_MODEL(KGE_QUATE, BODY)                          \
-        KGE_FOR_MODEL(KGE_KG2E, BODY)                           \
-        default: break;                                         \
-    }
-
 static int launch_rank_candidates(const kge_model_desc* m, Geometry geo, const CandArgs* a, hipStream_t s) {
     const DeviceModel dm = to_device_model(m);
     KGE_DISPATCH_ROW_MODELS(m->model, (k_rank_candidates<M, G, NCH><<<dim3(kMaxBlocks), dim3(kBlock), 0, s>>>(dm, a)))
@@ -261,46 +229,22 @@ int kge_rank_candidates(const kge_model_desc* m, const int64_t* triples, int64_t
                         const int64_t* cand_off, const int32_t* cand_ids, int64_t n_lists, const int64_t* skip_off,
                         const int32_t* skip_ids, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream) {
     const char* who = "kge_rank_candidates";
-    if (!m) { set_error("%s: null model descriptor", who); return -1; }
-    const ModelOps* ops = model_ops(m->model);
-    if (!ops) { set_error("%s: unknown model id %d", who, m->model); return -1; }
-    if (!ops->row_kernels) {
-        set_error("%s: model %d has no row kernels; rank it via-forward: score the expanded live triples with the model's own "
-                  "forward and count with kge_rank_lists_from_scores (Evaluator.rank_candidates does)", who, m->model);
-        return -1;
-    }
-    if (m->dim <= 0 || m->tot_entity <= 0 || m->tot_relation <= 0) {
-        set_error("%s: bad sizes (dim %d, entities %lld, relations %lld)", who, m->dim, (long long)m->tot_entity, (long long)m->tot_relation);
-        return -1;
-    }
-    for (int i = 0; i < ops->tables; ++i)
-        if (!m->tables[i]) { set_error("%s: table %d is null", who, i); return -1; }
     if (side != 0 && side != 1) { set_error("%s: side = %d (0 ranks tails, 1 ranks heads)", who, (int)side); return -1; }
-    if (n < 0 || n > 0x7fffffffll) { set_error("%s: n = %lld outside 0..2^31-1", who, (long long)n); return -1; }
-    if ((skip_off == nullptr) != (skip_ids == nullptr)) { set_error("%s: skip_off and skip_ids come together", who); return -1; }
     if (list_of_query && n_lists <= 0) { set_error("%s: list_of_query given with n_lists = %lld", who, (long long)n_lists); return -1; }
     if (!list_of_query && n_lists < n) { set_error("%s: n_lists = %lld < n = %lld without list_of_query", who, (long long)n_lists, (long long)n); return -1; }
-    const size_t need = kge_rank_candidates_workspace_bytes(n, n_lists, 0);
-    if (n > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("%s: workspace too small (%zu bytes, kge_rank_candidates_workspace_bytes asks for %zu)", who,
-                  workspace ? workspace_bytes : (size_t)0, need);
-        return -1;
-    }
-    if (n == 0) return 0;
-    if (!triples || !cand_off || !cand_ids || !counts) { set_error("%s: null triples / cand_off / cand_ids / counts", who); return -1; }
     Geometry geo;
-    if (!pick_geometry(m->dim, &geo)) { set_error("%s: hidden size %d exceeds the register-resident row kernels (max 2048)", who, m->dim); return -1; }
+    const int go = rank_entry_checks(who, m, n, skip_off, skip_ids, workspace, workspace_bytes, kge_rank_candidates_workspace_bytes(n, n_lists, 0),
+                                     "score the expanded live triples with the model's own forward and count with "
+                                     "kge_rank_lists_from_scores (Evaluator.rank_candidates does)", &geo);
+    if (go != kRankGo) return go;
+    if (!triples || !cand_off || !cand_ids || !counts) { set_error("%s: null triples / cand_off / cand_ids / counts", who); return -1; }
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = debug_check_triples(who, m->tot_entity, m->tot_relation, triples, n, s)) return rc;
     if (list_of_query)
         if (int rc = debug_check_ids(who, "list_of_query", list_of_query, n, 1, 0, n_lists, s)) return rc;
-    if (skip_off)
-        if (int rc = debug_check_ascending(who, "skip", skip_off, skip_ids, n, s)) return rc;
+    if (int rc = rank_counts_begin(who, m, triples, n, skip_off, skip_ids, counts, s)) return rc;
     CandArgs* args = (CandArgs*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);   // the kernel's copy of `a`, written by k_cand_items
     int64_t* item_off = (int64_t*)((char*)args + align256(sizeof(CandArgs)));
     const CandArgs a{triples, n, (int)side, list_of_query, cand_off, cand_ids, n_lists, skip_off, skip_ids, item_off, m->tot_entity, counts};
-    hipError_t e = hipMemsetAsync(counts, 0, (size_t)4 * (size_t)n * sizeof(int32_t), s);
-    if (e != hipSuccess) { set_error("%s: memset: %s", who, hipGetErrorString(e)); return -2; }
     hipLaunchKernelGGL(k_cand_items, dim3(1), dim3(kItemsBlock), 0, s, a, item_off, args);
     if (int rc = check_launch("k_cand_items")) return rc;
     return launch_rank_candidates(m, geo, args, s);

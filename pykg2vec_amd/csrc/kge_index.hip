@@ -445,6 +445,29 @@ __global__ __launch_bounds__(256) void k_relcsr_query(const int64_t* __restrict_
     if constexpr (!FILL) { if (lane == 0) count[q] = total; }
 }
 
+// Pass 1 of both CSR builds, after the entry point's own null / size checks: the packed-key bounds, the workspace size, the
+// debug-mode id scans, then keys -> sort of the `sides` key arrays -> counts -> offsets.  launch_keys(grid, P, keys) and
+// launch_count(grid, keys, P, count) are the caller's two kernels; the grid of the count launch is one wave per (query, side).
+template <typename Keys, typename Count>
+static int csr_count_pass(const char* who, const int64_t* known, int64_t n_known, const int64_t* queries, int64_t n_queries, int64_t tot_entity,
+                          int64_t tot_relation, void* workspace, size_t workspace_bytes, size_t need, int sides, int64_t* off_a, int64_t* off_b,
+                          int64_t* totals, hipStream_t s, const char* keys_kernel, Keys launch_keys, Count launch_count) {
+    if (tot_entity > (1 << 24) || tot_relation > (1 << 16)) { set_error("%s: the packed key holds 2^24 entities and 2^16 relations", who); return -1; }
+    if (workspace_bytes < need) { set_error("%s: workspace too small", who); return -1; }
+    if (int rc = debug_check_triples(who, tot_entity, tot_relation, known, n_known, s)) return rc;
+    if (int rc = debug_check_triples(who, tot_entity, tot_relation, queries, n_queries, s)) return rc;
+    const int P = csr_P(n_known);
+    u64* keys = (u64*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int* count = (int*)(keys + (size_t)sides * P);
+    launch_keys(dim3((unsigned)((P + 255) / 256)), P, keys);
+    int rc = check_launch(keys_kernel);
+    if (rc) return rc;
+    if ((rc = sort_batched(keys, sides, P, s))) return rc;
+    launch_count(dim3((unsigned)((sides * n_queries + 3) / 4)), keys, P, count);
+    hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(kIxBlock), 0, s, count, n_queries, off_a, off_b, totals, sides);
+    return check_launch("k_csr_scan");
+}
+
 }  // namespace kge
 
 using namespace kge;
@@ -461,22 +484,14 @@ int kge_filter_csr_count(const int64_t* known, int64_t n_known, const int64_t* q
                          int64_t* totals, void* stream) {
     const char* who = "kge_filter_csr_count";
     if (!known || !queries || !workspace || !tail_off || !head_off || !totals || n_known <= 0 || n_queries <= 0) { set_error("%s: bad arguments", who); return -1; }
-    if (tot_entity > (1 << 24) || tot_relation > (1 << 16)) { set_error("%s: the packed key holds 2^24 entities and 2^16 relations", who); return -1; }
-    if (workspace_bytes < kge_filter_csr_workspace_bytes(n_known, n_queries)) { set_error("%s: workspace too small", who); return -1; }
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = debug_check_triples(who, tot_entity, tot_relation, known, n_known, s)) return rc;
-    if (int rc = debug_check_triples(who, tot_entity, tot_relation, queries, n_queries, s)) return rc;
-    const int P = csr_P(n_known);
-    u64* keys = (u64*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* count = (int*)(keys + (size_t)2 * P);
-    hipLaunchKernelGGL(k_csr_keys, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, known, n_known, P, keys);
-    int rc = check_launch("k_csr_keys");
-    if (rc) return rc;
-    if ((rc = sort_batched(keys, 2, P, s))) return rc;
-    hipLaunchKernelGGL((k_csr_query<false>), dim3((unsigned)((2 * n_queries + 3) / 4)), dim3(256), 0, s, queries, n_queries, keys, P, n_known,
-                       count, (const int64_t*)nullptr, (const int64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(kIxBlock), 0, s, count, n_queries, tail_off, head_off, totals, 2);
-    return check_launch("k_csr_scan");
+    return csr_count_pass(who, known, n_known, queries, n_queries, tot_entity, tot_relation, workspace, workspace_bytes,
+                          kge_filter_csr_workspace_bytes(n_known, n_queries), 2, tail_off, head_off, totals, s, "k_csr_keys",
+        [&](dim3 grid, int P, u64* keys) { hipLaunchKernelGGL(k_csr_keys, grid, dim3(256), 0, s, known, n_known, P, keys); },
+        [&](dim3 grid, const u64* keys, int P, int* count) {
+            hipLaunchKernelGGL((k_csr_query<false>), grid, dim3(256), 0, s, queries, n_queries, keys, P, n_known, count, (const int64_t*)nullptr,
+                               (const int64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+        });
 }
 
 int kge_filter_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_known, const void* workspace, const int64_t* tail_off,
@@ -501,22 +516,14 @@ int kge_relation_csr_count(const int64_t* known, int64_t n_known, const int64_t*
         set_error("%s: bad arguments (known / queries / workspace / rel_off / total null, n_known outside 1..2^30-1 or n_queries < 1)", who);
         return -1;
     }
-    if (tot_entity > (1 << 24) || tot_relation > (1 << 16)) { set_error("%s: the packed key holds 2^24 entities and 2^16 relations", who); return -1; }
-    if (workspace_bytes < kge_relation_csr_workspace_bytes(n_known, n_queries)) { set_error("%s: workspace too small", who); return -1; }
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = debug_check_triples(who, tot_entity, tot_relation, known, n_known, s)) return rc;
-    if (int rc = debug_check_triples(who, tot_entity, tot_relation, queries, n_queries, s)) return rc;
-    const int P = csr_P(n_known);
-    u64* keys = (u64*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* count = (int*)(keys + (size_t)P);
-    hipLaunchKernelGGL(k_relcsr_keys, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, known, n_known, P, keys);
-    int rc = check_launch("k_relcsr_keys");
-    if (rc) return rc;
-    if ((rc = sort_batched(keys, 1, P, s))) return rc;
-    hipLaunchKernelGGL((k_relcsr_query<false>), dim3((unsigned)((n_queries + 3) / 4)), dim3(256), 0, s, queries, n_queries, keys, n_known, count,
-                       (const int64_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(kIxBlock), 0, s, count, n_queries, rel_off, (int64_t*)nullptr, total, 1);
-    return check_launch("k_csr_scan");
+    return csr_count_pass(who, known, n_known, queries, n_queries, tot_entity, tot_relation, workspace, workspace_bytes,
+                          kge_relation_csr_workspace_bytes(n_known, n_queries), 1, rel_off, (int64_t*)nullptr, total, s, "k_relcsr_keys",
+        [&](dim3 grid, int P, u64* keys) { hipLaunchKernelGGL(k_relcsr_keys, grid, dim3(256), 0, s, known, n_known, P, keys); },
+        [&](dim3 grid, const u64* keys, int, int* count) {
+            hipLaunchKernelGGL((k_relcsr_query<false>), grid, dim3(256), 0, s, queries, n_queries, keys, n_known, count, (const int64_t*)nullptr,
+                               (int32_t*)nullptr);
+        });
 }
 
 int kge_relation_csr_fill(const int64_t* queries, int64_t n_queries, int64_t n_known, const void* workspace, const int64_t* rel_off,

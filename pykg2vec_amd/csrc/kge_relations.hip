@@ -19,7 +19,9 @@
 //   scalars  as kge_candidates.hip: rows are loaded without lane masks, the arguments are read from a workspace copy (written by
 //            k_rel_args), and ONE walk loop serves the true relation and the others, so that model_fwd is instantiated once.  The
 //            kernel is held to k_score_fwd's resources (tests/test_relations_resources.py).
-#include "kge_row_kernels.h"
+//   shared   with kge_candidates.hip, in kge_rank_common.h: load_row_nomask, the list of row-kernel models, and the entry point's
+//            opening (rank_entry_checks, rank_counts_begin).  The walk loop is not shared: DESIGN.md section 30.
+#include "kge_rank_common.h"
 
 namespace kge {
 
@@ -32,22 +34,6 @@ struct RelArgs {
     const int64_t* skip_off; const int32_t* skip_ids;
     int32_t* counts; int R; int chunks;
 };
-
-// load_row's values with no lane mask (the twin of kge_candidates.hip's helper, which is private to that file): a padding element
-// reads the row's last float and is zeroed with an integer AND (+0.0, as load_row gives), so that no loop-invariant lane mask
-// occupies a scalar register pair for the whole kernel.
-template <int G, int NCH>
-__device__ __forceinline__ void load_row_nomask(float (&x)[NCH], const float* __restrict__ row, int dim, int gl) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int e = c * G + gl;
-        int keep = (e - dim) >> 31;   // all ones where e < dim
-        asm volatile("" : "+v"(keep));   // (opaque: otherwise it is folded back into a test, i.e. a lane mask)
-        int ec = min(e, dim - 1);
-        asm volatile("" : "+v"(ec));     // (opaque: redone per row, or NCH clamped indices stay live in vector registers)
-        x[c] = __int_as_float(__float_as_int(row[ec]) & keep);
-    }
-}
 
 }  // namespace
 
@@ -136,24 +122,6 @@ __global__ __launch_bounds__(kBlock) void k_rank_relations(DeviceModel m, const 
     }
 }
 
-#define KGE_DISPATCH_ROW_MODELS(model_id, BODY)                 \
-    switch (model_id) {                                         \
-        KGE_FOR_MODEL(KGE_TRANSE, BODY)                         \
-        KGE_FOR_MODEL(KGE_TRANSH, BODY)                         \
-        KGE_FOR_MODEL(KGE_TRANSD, BODY)                         \
-        KGE_FOR_MODEL(KGE_TRANSM, BODY)                         \
-        KGE_FOR_MODEL(KGE_ROTATE, BODY)                         \
-        KGE_FOR_MODEL(KGE_DISTMULT, BODY)                       \
-        KGE_FOR_MODEL(KGE_COMPLEX, BODY)                        \
-        KGE_FOR_MODEL(KGE_ANALOGY, BODY)                        \
-        KGE_FOR_MODEL(KGE_CP, BODY)                             \
-        KGE_FOR_MODEL(KGE_SIMPLE, BODY)                         \
-        KGE_FOR_MODEL(KGE_SIMPLE_IGNR, BODY)                    \
-        KGE_FOR_MODEL(KGE_QUATE, BODY)                          \
-        KGE_FOR_MODEL(KGE_KG2E, BODY)                           \
-        default: break;                                         \
-    }
-
 static int launch_rank_relations(const kge_model_desc* m, Geometry geo, const RelArgs* a, int64_t n_items, hipStream_t s) {
     const DeviceModel dm = to_device_model(m);
     KGE_DISPATCH_ROW_MODELS(m->model, (k_rank_relations<M, G, NCH><<<dim3(Launch<M, G, NCH>::grid(n_items)), dim3(kBlock), 0, s>>>(dm, a)))
@@ -175,42 +143,22 @@ size_t kge_rank_relations_workspace_bytes(int64_t n) {
 int kge_rank_relations(const kge_model_desc* m, const int64_t* triples, int64_t n, const int64_t* skip_off, const int32_t* skip_ids,
                        void* workspace, size_t workspace_bytes, int32_t* counts, void* stream) {
     const char* who = "kge_rank_relations";
-    if (!m) { set_error("%s: null model descriptor", who); return -1; }
-    const ModelOps* ops = model_ops(m->model);
-    if (!ops) { set_error("%s: unknown model id %d", who, m->model); return -1; }
-    if (!ops->row_kernels) {
-        set_error("%s: model %d has no row kernels; rank it via-forward: score the triples of every other relation with the model's "
-                  "own forward and count with kge_rank_lists_from_scores (Evaluator.rank_relations does)", who, m->model);
-        return -1;
-    }
-    if (m->dim <= 0 || m->tot_entity <= 0 || m->tot_relation <= 0 || m->tot_relation > 0x7fffffffll) {
+    if (m && m->tot_relation > 0x7fffffffll) {   // the walked ids are ints
         set_error("%s: bad sizes (dim %d, entities %lld, relations %lld)", who, m->dim, (long long)m->tot_entity, (long long)m->tot_relation);
         return -1;
     }
-    for (int i = 0; i < ops->tables; ++i)
-        if (!m->tables[i]) { set_error("%s: table %d is null", who, i); return -1; }
-    if (n < 0 || n > 0x7fffffffll) { set_error("%s: n = %lld outside 0..2^31-1", who, (long long)n); return -1; }
-    if ((skip_off == nullptr) != (skip_ids == nullptr)) { set_error("%s: skip_off and skip_ids come together", who); return -1; }
-    const size_t need = kge_rank_relations_workspace_bytes(n);
-    if (n > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("%s: workspace too small (%zu bytes, kge_rank_relations_workspace_bytes asks for %zu)", who,
-                  workspace ? workspace_bytes : (size_t)0, need);
-        return -1;
-    }
-    if (n == 0) return 0;
-    if (!triples || !counts) { set_error("%s: null triples / counts", who); return -1; }
     Geometry geo;
-    if (!pick_geometry(m->dim, &geo)) { set_error("%s: hidden size %d exceeds the register-resident row kernels (max 2048)", who, m->dim); return -1; }
+    const int go = rank_entry_checks(who, m, n, skip_off, skip_ids, workspace, workspace_bytes, kge_rank_relations_workspace_bytes(n),
+                                     "score the triples of every other relation with the model's own forward and count with "
+                                     "kge_rank_lists_from_scores (Evaluator.rank_relations does)", &geo);
+    if (go != kRankGo) return go;
+    if (!triples || !counts) { set_error("%s: null triples / counts", who); return -1; }
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = debug_check_triples(who, m->tot_entity, m->tot_relation, triples, n, s)) return rc;
-    if (skip_off)
-        if (int rc = debug_check_ascending(who, "skip", skip_off, skip_ids, n, s)) return rc;
+    if (int rc = rank_counts_begin(who, m, triples, n, skip_off, skip_ids, counts, s)) return rc;
     RelArgs* args = (RelArgs*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     const int R = (int)m->tot_relation;
     const int chunks = (R + kRelChunk - 1) / kRelChunk;
     const RelArgs a{triples, n, skip_off, skip_ids, counts, R, chunks};
-    hipError_t e = hipMemsetAsync(counts, 0, (size_t)4 * (size_t)n * sizeof(int32_t), s);
-    if (e != hipSuccess) { set_error("%s: memset: %s", who, hipGetErrorString(e)); return -2; }
     hipLaunchKernelGGL(k_rel_args, dim3(1), dim3(64), 0, s, a, args);
     if (int rc = check_launch("k_rel_args")) return rc;
     return launch_rank_relations(m, geo, args, n * chunks, s);

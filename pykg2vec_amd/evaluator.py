@@ -30,6 +30,22 @@ def _log(msg):
     print(msg, flush=True)
 
 
+def rank_metrics(ranks, hits):
+    """(mr, mrr, {k: hits@k}) of 1-based float32 ranks, in float32 (evaluator.py:125-141)."""
+    return np.mean(ranks), np.mean(np.reciprocal(ranks)), {k: np.mean(ranks <= k, dtype=np.float32) for k in hits}
+
+
+def _summary_lines(title, second_line, mr, fmr, mrr, fmrr, hit, fhit, hits):
+    lines = ["", title, second_line,
+             "--mr,  filtered mr             : %.4f, %.4f" % (mr, fmr),
+             "--mrr, filtered mrr            : %.4f, %.4f" % (mrr, fmrr)]
+    for k in hits:
+        lines.append("--hits%d                        : %.4f " % (k, hit[k]))
+        lines.append("--filtered hits%d               : %.4f " % (k, fhit[k]))
+    lines.append("---------------------------------------------------------")
+    return lines
+
+
 class MetricCalculator:
     """utils/evaluator.py:15-222, fed with rank arrays instead of candidate orderings."""
 
@@ -62,15 +78,10 @@ class MetricCalculator:
         tail_ranks = np.asarray(self.rank_tail, dtype=np.float32) + 1
         head_franks = np.asarray(self.f_rank_head, dtype=np.float32) + 1
         tail_franks = np.asarray(self.f_rank_tail, dtype=np.float32) + 1
-        ranks = np.concatenate((head_ranks, tail_ranks))
-        franks = np.concatenate((head_franks, tail_franks))
-        self.mr[self.epoch] = np.mean(ranks)
-        self.mrr[self.epoch] = np.mean(np.reciprocal(ranks))
-        self.fmr[self.epoch] = np.mean(franks)
-        self.fmrr[self.epoch] = np.mean(np.reciprocal(franks))
-        for hit in self.config.hits:
-            self.hit[(self.epoch, hit)] = np.mean(ranks <= hit, dtype=np.float32)
-            self.fhit[(self.epoch, hit)] = np.mean(franks <= hit, dtype=np.float32)
+        self.mr[self.epoch], self.mrr[self.epoch], hit = rank_metrics(np.concatenate((head_ranks, tail_ranks)), self.config.hits)
+        self.fmr[self.epoch], self.fmrr[self.epoch], fhit = rank_metrics(np.concatenate((head_franks, tail_franks)), self.config.hits)
+        for k in self.config.hits:
+            self.hit[(self.epoch, k)], self.fhit[(self.epoch, k)] = hit[k], fhit[k]
 
     def get_curr_scores(self):
         return {'mr': self.mr[self.epoch], 'fmr': self.fmr[self.epoch],
@@ -78,16 +89,12 @@ class MetricCalculator:
 
     def display_summary(self):
         dt = timeit.default_timer() - self.start_time
-        lines = ["", "------Test Results for %s: Epoch: %s --- time: %.2f------------" % (
-            getattr(self.config, "dataset_name", "?"), self.epoch, dt),
+        e, hits = self.epoch, self.config.hits
+        _log("\n".join(_summary_lines(
+            "------Test Results for %s: Epoch: %s --- time: %.2f------------" % (getattr(self.config, "dataset_name", "?"), e, dt),
             "--# of entities, # of relations: %d, %d" % (self.config.tot_entity, self.config.tot_relation),
-            "--mr,  filtered mr             : %.4f, %.4f" % (self.mr[self.epoch], self.fmr[self.epoch]),
-            "--mrr, filtered mrr            : %.4f, %.4f" % (self.mrr[self.epoch], self.fmrr[self.epoch])]
-        for hit in self.config.hits:
-            lines.append("--hits%d                        : %.4f " % (hit, self.hit[(self.epoch, hit)]))
-            lines.append("--filtered hits%d               : %.4f " % (hit, self.fhit[(self.epoch, hit)]))
-        lines.append("---------------------------------------------------------")
-        _log("\n".join(lines))
+            self.mr[e], self.fmr[e], self.mrr[e], self.fmrr[e], {k: self.hit[(e, k)] for k in hits},
+            {k: self.fhit[(e, k)] for k in hits}, hits)))
 
     def save_test_summary(self, model_name):
         """CSV of the per-epoch metrics, same columns as evaluator.py:186-206."""
@@ -383,13 +390,17 @@ class Evaluator:
         pick = [data[i] for i in sorted({0, m - 1} | {(j * m) // 64 for j in range(64)})] if m else []
         return ("o", id(data), len(data), m, tuple((t.h, t.r, t.t) for t in pick))
 
+    def _split_arrays(self):
+        """[train, valid, test] as int64 [., 3] arrays; KeyError / FileNotFoundError / AttributeError when the cache lacks one."""
+        kg = self.config.knowledge_graph
+        return [_as_array(kg.read_cache_data(k), None) for k in ('triplets_train', 'triplets_valid', 'triplets_test')]
+
     def _known_triples(self):
         """train + valid + test as ONE int64 [M, 3] device tensor (what hr_t / tr_h are built from, data/kgcontroller.py:410-428),
         uploaded once per Evaluator; None when the cache does not carry the three splits."""
         if getattr(self, "_known_dev", None) is None:
-            kg = self.config.knowledge_graph
             try:
-                parts = [_as_array(kg.read_cache_data(k), None) for k in ('triplets_train', 'triplets_valid', 'triplets_test')]
+                parts = self._split_arrays()
             except (KeyError, FileNotFoundError, AttributeError):
                 return None
             dev = next(self.model.parameters()).device
@@ -433,9 +444,7 @@ class Evaluator:
         elif source == "dicts":
             csr = tuple(torch.from_numpy(a).to(dev) for a in build_filter_csr(trip, mc.hr_t, mc.tr_h))
         else:  # host arrays without a device backend (CPU tests of the plumbing)
-            kg = self.config.knowledge_graph
-            known = np.concatenate([_as_array(kg.read_cache_data(k), None) for k in
-                                    ('triplets_train', 'triplets_valid', 'triplets_test')])
+            known = np.concatenate(self._split_arrays())
             csr = tuple(torch.from_numpy(a).to(dev) for a in build_filter_csr_from_triples(trip, known, self.config.tot_relation))
         return source, tuple(csr)
 
@@ -462,15 +471,18 @@ class Evaluator:
             self._cache[key] = (trip_dev,) + tuple(csr)
         return self._cache[key], key
 
+    def _prepare_eval_tables(self):
+        """What an evaluation does to the tables before it scores: RESCAL renormalises both, as the reference's forward does during
+        eval too (pairwise.py:843-844)."""
+        if getattr(self.model, "kernel_name", None) == "rescal":
+            self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+
     def rank_all(self, data, n, return_ties=False):
         """int32 [4, n] device tensor of ranks for the first n triples of `data`.  return_ties: also an int32 [2, n] tensor (head
         sweeps, tail sweeps) with the number of OTHER candidates whose energy equals the true entity's bit for bit (the ranks are
         the optimistic end of such a tie group; -1 = not counted, None with a backend that does not count)."""
         (trip, t_off, t_ids, h_off, h_ids), key = self._device_inputs(data, n)
-        if getattr(self.model, "kernel_name", None) == "rescal":
-            # the reference's forward renormalises both tables during eval too (pairwise.py:843-844)
-            self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data,
-                                    self.model.hidden_size)
+        self._prepare_eval_tables()
         desc = self.K.model_desc(self.model)
         count_ties = return_ties and self.K is K
         new_ties = lambda m: torch.zeros((2, m), dtype=torch.int32, device=trip.device) if count_ties else None
@@ -548,6 +560,26 @@ class Evaluator:
         C = int(t.shape[1])
         return CandidateLists(torch.arange(n + 1, dtype=torch.int64) * C, t[:n].reshape(-1)).to(dev)
 
+    def _ranking_path(self, what, projection_note, no_path_note):
+        """"rows" (the fused kernel) or "forward" (the model's own forward) for rank_candidates / rank_relations (`what`); the 1-N
+        models and unknown ones are refused."""
+        name = getattr(self.model, "kernel_name", None)
+        if isinstance(self.model, ProjectionModel):
+            raise ValueError("%s: %s is a projection model, %s" % (what, type(self.model).__name__, projection_note))
+        if name not in self.ROW_KERNEL_MODELS and name not in self.VIA_FORWARD_MODELS:
+            raise ValueError("%s: no %s path for model %r" % (what, no_path_note, name))
+        return "rows" if name in self.ROW_KERNEL_MODELS else "forward"
+
+    def _count_expanded(self, tq, h, r, t, seg, flags):
+        """The shared tail of the via-forward paths: ONE forward call scores the m true triples `tq` and the expanded triples
+        (h, r, t), whose segment of query i is seg[i] : seg[i + 1]; int32 [4, m] counts (rank_lists_from_scores)."""
+        m = int(tq.shape[0])
+        with torch.no_grad():
+            s = self.model.forward(torch.cat([tq[:, 0], h]).contiguous(), torch.cat([tq[:, 1], r]).contiguous(),
+                                   torch.cat([tq[:, 2], t]).contiguous()).reshape(-1)
+        return self.K.rank_lists_from_scores(s[m:].contiguous(), s[:m].contiguous(), seg, flags,
+                                             largest=bool(self.model.higher_is_better))
+
     def _rank_side_via_forward(self, trip, side, lists, skip_off, skip_ids):
         """int32 [4, n] counts of one side through the model's own forward: per chunk of queries the live list entries become
         explicit triples, ONE forward call scores the chunk's true triples and those, rank_lists_from_scores counts."""
@@ -561,7 +593,6 @@ class Evaluator:
         lens = (lists.off[loq + 1] - start).clamp_(min=0)
         lens_host = lens.cpu().numpy()   # the one host read: the chunk boundaries
         budget = max(1, self.PREDICT_SCRATCH_BYTES // self.CANDIDATE_ENTRY_BYTES)
-        largest = bool(self.model.higher_is_better)
         a = 0
         while a < n:
             b, tot = a + 1, int(lens_host[a])
@@ -590,13 +621,8 @@ class Evaluator:
                     kept = keys[at] != want
             live_seg = torch.zeros(m + 1, dtype=torch.int64, device=dev)
             live_seg[1:] = torch.cumsum(torch.bincount(qi, minlength=m), 0)
-            h = torch.cat([tq[:, 0], e if side else tq[qi, 0]]).contiguous()
-            r = torch.cat([tq[:, 1], tq[qi, 1]]).contiguous()
-            t = torch.cat([tq[:, 2], tq[qi, 2] if side else e]).contiguous()
-            with torch.no_grad():
-                s = self.model.forward(h, r, t).reshape(-1)
-            flags = (kept.to(torch.uint8) << 1) | 1
-            out[:, a:b] = self.K.rank_lists_from_scores(s[m:].contiguous(), s[:m].contiguous(), live_seg, flags, largest=largest)
+            out[:, a:b] = self._count_expanded(tq, e if side else tq[qi, 0], tq[qi, 1], tq[qi, 2] if side else e, live_seg,
+                                               (kept.to(torch.uint8) << 1) | 1)
             a = b
         return out
 
@@ -609,12 +635,7 @@ class Evaluator:
         whose score equals the true entity's bit for bit; the ranks are the optimistic end of such a group.
         The row-kernel models take the fused kernel (kge_rank_candidates); RESCAL, NTN, TransR, SLM, SME, SME_BL, HoLE, OctonionE,
         ConvKB and MuRP score the expanded lists through their own forward.  The 1-N models are refused: rank_all is their path."""
-        name = getattr(self.model, "kernel_name", None)
-        if isinstance(self.model, ProjectionModel):
-            raise ValueError("rank_candidates: %s is a projection model, whose scorer is 1-N over all entities; rank_all is its path"
-                             % type(self.model).__name__)
-        if name not in self.ROW_KERNEL_MODELS and name not in self.VIA_FORWARD_MODELS:
-            raise ValueError("rank_candidates: no candidate-list path for model %r" % name)
+        path = self._ranking_path("rank_candidates", "whose scorer is 1-N over all entities; rank_all is its path", "candidate-list")
         trip_host = _as_array(data, n)
         n = int(trip_host.shape[0])
         dev = self.config.device
@@ -623,7 +644,7 @@ class Evaluator:
         source, (t_off, t_ids, h_off, h_ids) = self._filter_csr(trip_host, trip) if n else (None, (None,) * 4)
         skips = [(t_off, t_ids), (h_off, h_ids)]
         counts = []
-        if name in self.ROW_KERNEL_MODELS:
+        if path == "rows":
             desc = self.K.model_desc(self.model)
             for side in (0, 1):
                 ls = sides[side]
@@ -631,8 +652,7 @@ class Evaluator:
                 counts.append(self.K.rank_candidates(desc, trip, side, ls.off, ls.ids, list_of_query=loq, skip_off=skips[side][0],
                                                      skip_ids=skips[side][1], skip_sorted=source in ("triples", "triples_host")))
         else:
-            if name == "rescal":   # the reference's forward renormalises both tables during eval too, as rank_all does
-                self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+            self._prepare_eval_tables()
             for side in (0, 1):
                 counts.append(self._rank_side_via_forward(trip, side, sides[side], *skips[side]) if n
                               else torch.zeros((4, 0), dtype=torch.int32, device=dev))
@@ -686,9 +706,8 @@ class Evaluator:
             known = self._known_triples()
             if known is not None:
                 return self.K.relation_csr_build(known, trip_dev, E, R)
-        kg = self.config.knowledge_graph
         try:
-            parts = [_as_array(kg.read_cache_data(k), None) for k in ('triplets_train', 'triplets_valid', 'triplets_test')]
+            parts = self._split_arrays()
         except (KeyError, FileNotFoundError, AttributeError):
             raise K.L.KgeHipError("Evaluator: relation ranking filters by the pair (h, t), which needs the three splits in the "
                                   "knowledge-graph cache (hr_t / tr_h are keyed by (h, r) / (t, r))")
@@ -710,7 +729,6 @@ class Evaluator:
         R = int(self.config.tot_relation)
         out = torch.zeros((4, n), dtype=torch.int32, device=dev)
         per = int(max(1, (self.PREDICT_SCRATCH_BYTES // self.CANDIDATE_ENTRY_BYTES) // max(1, R - 1)))
-        largest = bool(self.model.higher_is_better)
         others = torch.arange(R - 1, dtype=torch.int64, device=dev)
         off_host = rel_off.cpu().numpy()   # the one host read: which skip entries belong to a chunk
         for a in range(0, n, per):
@@ -727,13 +745,9 @@ class Evaluator:
                 known[row[ok], ids[ok]] = True
             kept = ~known.gather(1, rel) if R > 1 else known[:, :0]
             flags = ((kept.reshape(-1).to(torch.uint8) << 1) | 1).contiguous()          # bit 0 live (every other relation is), bit 1 kept
-            h = torch.cat([tq[:, 0], tq[:, 0].repeat_interleave(R - 1)]).contiguous()
-            r = torch.cat([tq[:, 1], rel.reshape(-1)]).contiguous()
-            t = torch.cat([tq[:, 2], tq[:, 2].repeat_interleave(R - 1)]).contiguous()
-            with torch.no_grad():
-                s = self.model.forward(h, r, t).reshape(-1)
             seg = torch.arange(m + 1, dtype=torch.int64, device=dev) * (R - 1)
-            out[:, a:b] = self.K.rank_lists_from_scores(s[m:].contiguous(), s[:m].contiguous(), seg, flags, largest=largest)
+            out[:, a:b] = self._count_expanded(tq, tq[:, 0].repeat_interleave(R - 1), rel.reshape(-1), tq[:, 2].repeat_interleave(R - 1),
+                                               seg, flags)
         return out
 
     def rank_relations(self, data, n, return_ties=False):
@@ -742,18 +756,12 @@ class Evaluator:
         int32 [n], the number of other relations whose score equals the true one's bit for bit; the ranks are the optimistic end of
         such a group.  The row-kernel models take the fused kernel (kge_rank_relations); RESCAL, NTN, TransR, SLM, SME, SME_BL, HoLE,
         OctonionE, ConvKB and MuRP score the expanded triples through their own forward.  The 1-N models are refused."""
-        name = getattr(self.model, "kernel_name", None)
-        if isinstance(self.model, ProjectionModel):
-            raise ValueError("rank_relations: %s is a projection model, whose forward scores entities, not relations"
-                             % type(self.model).__name__)
-        if name not in self.ROW_KERNEL_MODELS and name not in self.VIA_FORWARD_MODELS:
-            raise ValueError("rank_relations: no relation-ranking path for model %r" % name)
+        path = self._ranking_path("rank_relations", "whose forward scores entities, not relations", "relation-ranking")
         trip, rel_off, rel_ids = self._relation_inputs(data, n)
-        if name in self.ROW_KERNEL_MODELS:
+        if path == "rows":
             counts = self.K.rank_relations(self.K.model_desc(self.model), trip, skip_off=rel_off, skip_ids=rel_ids, skip_sorted=True)
         else:
-            if name == "rescal":   # the reference's forward renormalises both tables during eval too, as rank_all does
-                self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+            self._prepare_eval_tables()
             counts = self._rank_relations_via_forward(trip, rel_off, rel_ids)
         ranks = torch.stack([counts[0], counts[1]])
         return (ranks, counts[2].clone()) if return_ties else ranks
@@ -768,22 +776,14 @@ class Evaluator:
         ranks = ranks.cpu().numpy()
         self.relation_tie_counts = ties.cpu().numpy()
         self._warn_ties(self.relation_tie_counts, "relation")
-        r = ranks[0].astype(np.float32) + 1
-        f = ranks[1].astype(np.float32) + 1
-        out = {'mr': np.mean(r), 'fmr': np.mean(f), 'mrr': np.mean(np.reciprocal(r)), 'fmrr': np.mean(np.reciprocal(f)),
-               'hits': {k: np.mean(r <= k, dtype=np.float32) for k in self.config.hits},
-               'fhits': {k: np.mean(f <= k, dtype=np.float32) for k in self.config.hits}}
-        lines = ["", "------Relation Prediction Results for %s: Epoch: %s --- time: %.2f------------" % (
-            getattr(self.config, "dataset_name", "?"), epoch, timeit.default_timer() - t0),
+        mr, mrr, hit = rank_metrics(ranks[0].astype(np.float32) + 1, self.config.hits)
+        fmr, fmrr, fhit = rank_metrics(ranks[1].astype(np.float32) + 1, self.config.hits)
+        _log("\n".join(_summary_lines(
+            "------Relation Prediction Results for %s: Epoch: %s --- time: %.2f------------" % (
+                getattr(self.config, "dataset_name", "?"), epoch, timeit.default_timer() - t0),
             "--# of triples, # of relations : %d, %d" % (ranks.shape[1], self.config.tot_relation),
-            "--mr,  filtered mr             : %.4f, %.4f" % (out['mr'], out['fmr']),
-            "--mrr, filtered mrr            : %.4f, %.4f" % (out['mrr'], out['fmrr'])]
-        for k in self.config.hits:
-            lines.append("--hits%d                        : %.4f " % (k, out['hits'][k]))
-            lines.append("--filtered hits%d               : %.4f " % (k, out['fhits'][k]))
-        lines.append("---------------------------------------------------------")
-        _log("\n".join(lines))
-        return out
+            mr, fmr, mrr, fmrr, hit, fhit, self.config.hits)))
+        return {'mr': mr, 'fmr': fmr, 'mrr': mrr, 'fmrr': fmrr, 'hits': hit, 'fhits': fhit}
 
     # --- triple classification (Socher et al. 2013): true or false, by the score against a per-relation threshold fitted on
     # labelled validation triples; accuracy, per-relation accuracy, AUC
@@ -812,8 +812,7 @@ class Evaluator:
                 b = min(n, a + per)
                 out[a:b] = self.model.score_rows(trip[a:b], 0).gather(1, trip[a:b, 2:3]).reshape(-1)
             return out
-        if getattr(self.model, "kernel_name", None) == "rescal":
-            self.K.rescal_normalize(self.model.ent_embeddings.weight.data, self.model.rel_matrices.weight.data, self.model.hidden_size)
+        self._prepare_eval_tables()
         for a in range(0, n, self.CLASSIFY_FORWARD_CHUNK):
             b = min(n, a + self.CLASSIFY_FORWARD_CHUNK)
             with torch.no_grad():

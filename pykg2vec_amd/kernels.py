@@ -846,34 +846,68 @@ def eval_ranks_via_forward(desc, triples, tail_off, tail_ids, head_off, head_ids
     return out
 
 
+def _csr_two_pass(stem, sides, known, queries, tot_entity, tot_relation, names):
+    """The two-pass device build behind filter_csr_build / relation_csr_build: kge_<stem>_count writes the `sides` offset arrays
+    (int64 [n + 1], argument names `names`) and their totals, ONE host read sizes the id arrays, kge_<stem>_fill writes them.
+    Returns (offsets, ids), a list per side; ids is None when there is nothing to count (no query or no known triple)."""
+    n, M = int(queries.shape[0]), int(known.shape[0])
+    dev = queries.device
+    offs = [torch.zeros(n + 1, dtype=torch.int64, device=dev) for _ in range(sides)]
+    if n == 0 or M == 0:
+        return offs, None
+    lib = L.load()
+    count, fill = "kge_%s_count" % stem, "kge_%s_fill" % stem
+    ws = torch.empty(getattr(lib, "kge_%s_workspace_bytes" % stem)(M, n), dtype=torch.uint8, device=dev)
+    totals = torch.empty(sides, dtype=torch.int64, device=dev)
+    p_offs = [_dev(o, torch.int64, name) for o, name in zip(offs, names)]
+    L.check(getattr(lib, count)(_ids(known, "known triples"), M, _ids(queries, "queries"), n, int(tot_entity), int(tot_relation),
+                                _dev(ws, torch.uint8, "workspace"), ws.numel(), *p_offs, _dev(totals, torch.int64, "totals"), _stream()), count)
+    ids = [torch.empty(max(int(x), 1), dtype=torch.int32, device=dev)[:int(x)] for x in totals.tolist()]       # the one host read
+    L.check(getattr(lib, fill)(_ids(queries, "queries"), n, M, _dev(ws, torch.uint8, "workspace"), *p_offs,
+                               *[ctypes.c_void_p(i.data_ptr()) for i in ids], _stream()), fill)
+    return offs, ids
+
+
 def filter_csr_build(known, queries, tot_entity, tot_relation):
     """Per-query filter lists (tail_off int64 [n+1], tail_ids int32, head_off, head_ids) of `queries` [n, 3] against the set of
     `known` triples [M, 3] (train + valid + test), built on the device: kge_filter_csr_count / _fill.  One host read (the two list
     totals) between the calls."""
-    n, M = int(queries.shape[0]), int(known.shape[0])
-    dev = queries.device
-    t_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    h_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    if n == 0 or M == 0:
-        empty = torch.empty(0, dtype=torch.int32, device=dev)
+    (t_off, h_off), ids = _csr_two_pass("filter_csr", 2, known, queries, tot_entity, tot_relation, ("tail_off", "head_off"))
+    if ids is None:
+        empty = torch.empty(0, dtype=torch.int32, device=queries.device)
         return t_off, empty, h_off, empty.clone()
-    lib = L.load()
-    ws = torch.empty(lib.kge_filter_csr_workspace_bytes(M, n), dtype=torch.uint8, device=dev)
-    totals = torch.empty(2, dtype=torch.int64, device=dev)
-    L.check(lib.kge_filter_csr_count(_ids(known, "known triples"), M, _ids(queries, "queries"), n, int(tot_entity), int(tot_relation),
-                                     _dev(ws, torch.uint8, "workspace"), ws.numel(), _dev(t_off, torch.int64, "tail_off"),
-                                     _dev(h_off, torch.int64, "head_off"), _dev(totals, torch.int64, "totals"), _stream()),
-            "kge_filter_csr_count")
-    nt, nh = (int(x) for x in totals.tolist())       # the one host read
-    t_ids = torch.empty(max(nt, 1), dtype=torch.int32, device=dev)[:nt]
-    h_ids = torch.empty(max(nh, 1), dtype=torch.int32, device=dev)[:nh]
-    L.check(lib.kge_filter_csr_fill(_ids(queries, "queries"), n, M, _dev(ws, torch.uint8, "workspace"), _dev(t_off, torch.int64, "tail_off"),
-                                    _dev(h_off, torch.int64, "head_off"), ctypes.c_void_p(t_ids.data_ptr()), ctypes.c_void_p(h_ids.data_ptr()),
-                                    _stream()), "kge_filter_csr_fill")
-    return t_off, t_ids, h_off, h_ids
+    return t_off, ids[0], h_off, ids[1]
 
 
 TOPK_MAX = L.TOPK_MAX
+
+
+def _skip_csr_args(n, skip_off, skip_ids, dev, sort=False, what="n"):
+    """The per-query skip CSR as the library takes it: (skip_off pointer, skip_ids pointer, the id tensor the second pointer is
+    of -- the caller holds it until its launch is queued), or (None, None, None) without lists.  n + 1 offsets; sort: make every
+    segment ascending first (sort_skip_segments); an empty id array becomes a pointer the library accepts and never reads."""
+    if (skip_off is None) != (skip_ids is None):
+        raise ValueError("skip_off and skip_ids come together")
+    if skip_off is None or n == 0:
+        return None, None, None
+    if skip_off.numel() != n + 1:
+        raise ValueError("skip_off must hold %s + 1 = %d offsets (got %d)" % (what, n + 1, skip_off.numel()))
+    if sort:
+        skip_ids = sort_skip_segments(skip_off, skip_ids)
+    if skip_ids.numel() == 0:
+        skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _dev(skip_off, torch.int64, "skip_off"), _dev(skip_ids, torch.int32, "skip_ids"), skip_ids
+
+
+def _row_desc_triples(desc, triples, who, hint):
+    """The shared opening of rank_candidates / rank_relations: a row-kernel descriptor, triples [n, 3]; (n, empty counts [4, n])."""
+    if not isinstance(desc, L.ModelDesc):
+        raise L.KgeHipError("%s: %s has no row kernels; rank it via-forward (the model's own forward over %s + rank_lists_from_scores, "
+                            "as Evaluator.%s does)" % (who, type(desc).__name__, hint, who))
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("triples must be [n, 3]")
+    n = int(triples.shape[0])
+    return n, torch.empty((4, n), dtype=torch.int32, device=triples.device)
 
 
 def topk_rows(scores, k, largest=False, skip_off=None, skip_ids=None, keep=None):
@@ -901,18 +935,11 @@ def topk_rows(scores, k, largest=False, skip_off=None, skip_ids=None, keep=None)
     count = torch.empty(nq, dtype=torch.int32, device=dev)
     if nq == 0:
         return ids, vals, count
-    if (skip_off is None) != (skip_ids is None):
-        raise ValueError("skip_off and skip_ids come together")
     lib = L.load()
-    po = pi = pk = pw = None
+    pk = pw = None
     nbytes = 0
-    if skip_off is not None:
-        if skip_off.numel() != nq + 1:
-            raise ValueError("skip_off must hold nq + 1 = %d offsets (got %d)" % (nq + 1, skip_off.numel()))
-        po = _dev(skip_off, torch.int64, "skip_off")
-        if skip_ids.numel() == 0:   # every list is empty: a pointer the library accepts, never read
-            skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
-        pi = _dev(skip_ids, torch.int32, "skip_ids")
+    po, pi, skip_ids = _skip_csr_args(nq, skip_off, skip_ids, dev, what="nq")
+    if po is not None:
         if keep is not None:
             if keep.numel() != nq:
                 raise ValueError("keep must hold one id per row (%d, got %d)" % (nq, keep.numel()))
@@ -949,33 +976,17 @@ def rank_candidates(desc, triples, side, cand_off, cand_ids, list_of_query=None,
     list_of_query[i] (int64 [n]) or list i.  Entries equal to the true entity or outside [0, tot_entity) are ignored (-1 pads).
     skip_off / skip_ids: per-query CSR of known entities to leave out; the segments are sorted here (sort_skip_segments) unless
     skip_sorted says they already are ascending."""
-    if not isinstance(desc, L.ModelDesc):
-        raise L.KgeHipError("rank_candidates: %s has no row kernels; rank it via-forward (the model's own forward over the expanded "
-                            "triples + rank_lists_from_scores, as Evaluator.rank_candidates does)" % type(desc).__name__)
-    if triples.dim() != 2 or triples.shape[1] != 3:
-        raise ValueError("triples must be [n, 3]")
-    if (skip_off is None) != (skip_ids is None):
-        raise ValueError("skip_off and skip_ids come together")
-    n = int(triples.shape[0])
+    n, counts = _row_desc_triples(desc, triples, "rank_candidates", "the expanded triples")
     dev = triples.device
-    counts = torch.empty((4, n), dtype=torch.int32, device=dev)
     n_lists = int(cand_off.numel()) - 1
     if list_of_query is not None and list_of_query.numel() != n:
         raise ValueError("list_of_query must hold one list index per query (%d, got %d)" % (n, list_of_query.numel()))
+    po, pi, skip_ids = _skip_csr_args(n, skip_off, skip_ids, dev, sort=not skip_sorted)
     if n == 0:
         return counts
     lib = L.load()
     if cand_ids.numel() == 0:   # every list is empty: a pointer the library accepts, never read
         cand_ids = torch.zeros(1, dtype=torch.int32, device=dev)
-    po = pi = None
-    if skip_off is not None:
-        if skip_off.numel() != n + 1:
-            raise ValueError("skip_off must hold n + 1 = %d offsets (got %d)" % (n + 1, skip_off.numel()))
-        if not skip_sorted:
-            skip_ids = sort_skip_segments(skip_off, skip_ids)
-        if skip_ids.numel() == 0:
-            skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
-        po, pi = _dev(skip_off, torch.int64, "skip_off"), _dev(skip_ids, torch.int32, "skip_ids")
     nbytes = lib.kge_rank_candidates_workspace_bytes(n, n_lists, int(cand_ids.numel()))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     L.check(lib.kge_rank_candidates(ctypes.byref(desc), _ids(triples, "triples"), n, int(side),
@@ -1017,22 +1028,8 @@ def relation_csr_build(known, queries, tot_entity, tot_relation):
     """Per query (h, ., t) of `queries` [n, 3] the distinct relations r with (h, r, t) in `known` [M, 3] (train + valid + test),
     ascending: (rel_off int64 [n + 1], rel_ids int32), built on the device with kge_relation_csr_count / _fill.  One host read (the
     list total) between the calls."""
-    n, M = int(queries.shape[0]), int(known.shape[0])
-    dev = queries.device
-    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    if n == 0 or M == 0:
-        return off, torch.empty(0, dtype=torch.int32, device=dev)
-    lib = L.load()
-    ws = torch.empty(lib.kge_relation_csr_workspace_bytes(M, n), dtype=torch.uint8, device=dev)
-    total = torch.empty(1, dtype=torch.int64, device=dev)
-    L.check(lib.kge_relation_csr_count(_ids(known, "known triples"), M, _ids(queries, "queries"), n, int(tot_entity), int(tot_relation),
-                                       _dev(ws, torch.uint8, "workspace"), ws.numel(), _dev(off, torch.int64, "rel_off"),
-                                       _dev(total, torch.int64, "total"), _stream()), "kge_relation_csr_count")
-    nr = int(total.item())       # the one host read
-    ids = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)[:nr]
-    L.check(lib.kge_relation_csr_fill(_ids(queries, "queries"), n, M, _dev(ws, torch.uint8, "workspace"), _dev(off, torch.int64, "rel_off"),
-                                      ctypes.c_void_p(ids.data_ptr()), _stream()), "kge_relation_csr_fill")
-    return off, ids
+    (off,), ids = _csr_two_pass("relation_csr", 1, known, queries, tot_entity, tot_relation, ("rel_off",))
+    return off, torch.empty(0, dtype=torch.int32, device=queries.device) if ids is None else ids[0]
 
 
 def rank_relations(desc, triples, skip_off=None, skip_ids=None, skip_sorted=False):
@@ -1040,28 +1037,12 @@ def rank_relations(desc, triples, skip_off=None, skip_ids=None, skip_sorted=Fals
     the filter, #tied, #tied under the filter (0-based, optimistic end, ties bit for bit).  triples int64 [n, 3]; the number of
     relations is the descriptor's.  skip_off / skip_ids: per-query CSR of the relations known for the pair (h, t), left out of rows
     1 and 3; the segments are sorted here (sort_skip_segments) unless skip_sorted says they already are ascending."""
-    if not isinstance(desc, L.ModelDesc):
-        raise L.KgeHipError("rank_relations: %s has no row kernels; rank it via-forward (the model's own forward over the triples of "
-                            "every other relation + rank_lists_from_scores, as Evaluator.rank_relations does)" % type(desc).__name__)
-    if triples.dim() != 2 or triples.shape[1] != 3:
-        raise ValueError("triples must be [n, 3]")
-    if (skip_off is None) != (skip_ids is None):
-        raise ValueError("skip_off and skip_ids come together")
-    n = int(triples.shape[0])
+    n, counts = _row_desc_triples(desc, triples, "rank_relations", "the triples of every other relation")
     dev = triples.device
-    counts = torch.empty((4, n), dtype=torch.int32, device=dev)
+    po, pi, skip_ids = _skip_csr_args(n, skip_off, skip_ids, dev, sort=not skip_sorted)
     if n == 0:
         return counts
     lib = L.load()
-    po = pi = None
-    if skip_off is not None:
-        if skip_off.numel() != n + 1:
-            raise ValueError("skip_off must hold n + 1 = %d offsets (got %d)" % (n + 1, skip_off.numel()))
-        if not skip_sorted:
-            skip_ids = sort_skip_segments(skip_off, skip_ids)
-        if skip_ids.numel() == 0:   # every segment is empty: a pointer the library accepts, never read
-            skip_ids = torch.zeros(1, dtype=torch.int32, device=dev)
-        po, pi = _dev(skip_off, torch.int64, "skip_off"), _dev(skip_ids, torch.int32, "skip_ids")
     nbytes = lib.kge_rank_relations_workspace_bytes(n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     L.check(lib.kge_rank_relations(ctypes.byref(desc), _ids(triples, "triples"), n, po, pi, ctypes.c_void_p(ws.data_ptr()), nbytes,
