@@ -100,7 +100,7 @@ const char* kge_last_error(void);
  * kge_eval_ranks / _grouped / kge_eval_sweep_scores (and _side), kge_rank_from_scores. */
 int kge_set_debug(int32_t check_ids);
 /* A/B switches of the dispatch rules: RESCAL_UNFUSED, RESCAL_ROWS, RESCAL_G, RESCAL_G2, TRANSR_ROWS, TRANSR_G,
- * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an
+ * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT, KNN_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an
  * integer; "0" off, "1" on) or, if that is unset, to the built-in rule.  Same meaning on both sides of the boundary. */
 int kge_set_switch(const char* name, int32_t value);
 int kge_get_debug(void);
@@ -138,6 +138,29 @@ size_t kge_topk_workspace_bytes(int64_t nq, int64_t n_cand, int masked);
 int kge_topk_rows(const void* scores, int dtype, int64_t nq, int64_t n_cand, int64_t row_stride, int32_t k, int largest,
                   const int64_t* skip_off, const int32_t* skip_ids, const int64_t* keep, void* workspace, size_t workspace_bytes,
                   int32_t* out_ids, void* out_scores, int32_t* out_count, void* stream);
+
+/* ---- nearest neighbours in embedding space (kge_knn.hip): the k nearest live rows of `table` (float32 [n_rows, table_stride], the
+ * first dim elements of a row count) for every row of `queries` (float32 [nq, query_stride]), the select fused into the
+ * matrix-core sweep: no [nq, n_rows] score block exists.  The order is kge_topk_rows's: row q's output holds the first
+ * min(k, live_q) live candidates of ONE total order -- better score first, lower candidate id first among equal returned scores,
+ * -0.0 equals +0.0, a NaN score after every number, NaNs ordered by id; a row or query with a NaN entry scores NaN in every
+ * metric.  Candidate self_ids[q] is not live for row q (self_ids NULL or -1: every row is live).  Cosine of a zero-norm row is 0.
+ * L2 returns sqrt(sum (q_i - c_i)^2) recomputed directly for the winners (identical rows: exactly 0.0); which rows win is decided
+ * by |q|^2 + |c|^2 - 2 q.c clamped at 0.  out_ids int32 [nq, k], out_scores float32 [nq, k], out_count int32 [nq]; places from
+ * out_count[q] on hold id -1 and a NaN.  Results are bit-identical from run to run and do not depend on the candidate split S
+ * (chosen so that one query tile fills the device; the switch KNN_SPLIT forces it): the only atomics are integer LDS adds that
+ * hand out buffer slots.  workspace: kge_knn_workspace_bytes (0 for refused arguments), asked for under the same switches as the
+ * call.  Refused before any GPU call, kge_last_error() naming the argument: k outside 1..KGE_KNN_MAX, dim < 1, n_rows < 1, an
+ * unknown metric, a stride below dim, a null table / queries / output, a workspace that is too small.  Three launches (two for
+ * dot), whatever nq and n_rows are. */
+#define KGE_KNN_MAX 128
+#define KGE_KNN_DOT 0      /* higher is nearer */
+#define KGE_KNN_COSINE 1   /* higher is nearer; a zero-norm row has cosine 0 to everything */
+#define KGE_KNN_L2 2       /* Euclidean distance, lower is nearer */
+size_t kge_knn_workspace_bytes(int64_t nq, int64_t n_rows, int64_t dim, int32_t k, int metric);
+int kge_knn_rows(const float* table, int64_t n_rows, int64_t dim, int64_t table_stride, const float* queries, int64_t nq,
+                 int64_t query_stride, const int64_t* self_ids, int32_t k, int metric, void* workspace, size_t workspace_bytes,
+                 int32_t* out_ids, float* out_scores, int32_t* out_count, void* stream);
 
 /* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
  * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).

@@ -314,6 +314,84 @@ class Evaluator:
 
         return self._select_chunks(int(h.numel()), R, topk, rows_of)
 
+    # --- nearest neighbours in embedding space: which entities / relations lie closest to given ones (kge_knn_rows)
+    KNN_QUERY_BYTES = 8 * 2048 + 4   # most workspace kge_knn_rows takes per query: its partial lists (S * k <= 2048 pairs) and a norm
+
+    def _knn_matrix(self, kind, tables):
+        if kind not in ("entity", "relation"):
+            raise ValueError("kind = %r (\"entity\" or \"relation\")" % (kind,))
+        with torch.no_grad():
+            m = self.model.entity_matrix(tables) if kind == "entity" else self.model.relation_matrix(tables)
+        return m if m.stride(-1) == 1 else m.contiguous()
+
+    def _knn_chunks(self, table, n, topk, metric, queries_of, self_ids=None):
+        """queries_of(a, b) -> float32 [b - a, D] query rows a..b; the chunks are sized so that the search's workspace stays within
+        PREDICT_SCRATCH_BYTES, and each goes through knn_rows into ONE pair of output tensors.  Nothing in the loop reads the device."""
+        topk = int(topk)
+        if not 1 <= topk <= K.KNN_MAX:
+            raise ValueError("topk = %d outside 1..%d (KGE_KNN_MAX)" % (topk, K.KNN_MAX))
+        K.knn_metric(metric)
+        dev = table.device
+        ids = torch.empty((n, topk), dtype=torch.int64, device=dev)
+        vals = torch.empty((n, topk), dtype=torch.float32, device=dev)
+        per = int(max(1, (self.PREDICT_SCRATCH_BYTES - 4 * int(table.shape[0])) // self.KNN_QUERY_BYTES))
+        for a in range(0, n, per):
+            b = min(n, a + per)
+            i, v, _ = self.K.knn_rows(table, queries_of(a, b), topk, metric=metric, self_ids=None if self_ids is None else self_ids[a:b])
+            ids[a:b] = i
+            vals[a:b] = v
+        return ids, vals
+
+    def _nearest(self, kind, ids, topk, metric, tables, exclude_self):
+        table = self._knn_matrix(kind, tables)
+        ids = self._ids_arg(ids, "ids").to(table.device)
+        return self._knn_chunks(table, int(ids.numel()), topk, metric, lambda a, b: table[ids[a:b]], ids if exclude_self else None)
+
+    def nearest_entities(self, ids, topk=10, metric="cosine", tables=None, exclude_self=True):
+        """(ids int64 [n, topk], scores float32 [n, topk]): the topk entities nearest to every entity of `ids` in embedding space,
+        nearest first, equal scores by ascending id (kge_knn_rows).  metric: "cosine", "dot" (higher is nearer) or "l2" (the Euclidean
+        distance).  The rows compared are Model.entity_matrix(tables).  exclude_self: entity ids[i] is not its own neighbour.  Rows
+        with fewer than topk live candidates are padded with id -1 and a NaN score."""
+        return self._nearest("entity", ids, topk, metric, tables, exclude_self)
+
+    def nearest_relations(self, ids, topk=10, metric="cosine", tables=None, exclude_self=True):
+        """nearest_entities over Model.relation_matrix(tables)."""
+        return self._nearest("relation", ids, topk, metric, tables, exclude_self)
+
+    def nearest_to_vectors(self, vectors, kind="entity", topk=10, metric="cosine", tables=None):
+        """nearest_entities for query rows that are no rows of the table: `vectors` float32 [n, D] (or [D]) against the entity or
+        relation matrix of D columns, e.g. ent[h] + rel[r] of a TransE.  Every row of the table is live."""
+        table = self._knn_matrix(kind, tables)
+        v = vectors.detach() if isinstance(vectors, torch.Tensor) else torch.as_tensor(np.asarray(vectors))
+        v = v.to(device=table.device, dtype=torch.float32)
+        v = v.view(1, -1) if v.dim() == 1 else v
+        if v.dim() != 2 or v.shape[1] != table.shape[1]:
+            raise ValueError("vectors %s against a %s matrix of %d columns" % (tuple(v.shape), kind, table.shape[1]))
+        v = v if v.stride(-1) == 1 else v.contiguous()
+        return self._knn_chunks(table, int(v.shape[0]), topk, metric, lambda a, b: v[a:b])
+
+    def find_duplicates(self, kind="entity", metric="l2", threshold=None, topk=8, tables=None):
+        """(pairs int64 [m, 2], scores float32 [m]): the pairs a < b of entities (or relations) whose score passes `threshold` --
+        at most for "l2", at least for "cosine" / "dot" -- found among the topk nearest neighbours of every row; each pair once, in
+        (a, b) order.  A pair's score is the same from either side (the sums run in the same order).  The search runs for every
+        row in chunks that read nothing back; the filter runs once on the device behind them."""
+        if threshold is None:
+            raise ValueError("find_duplicates needs a threshold (a distance for \"l2\", a similarity for \"cosine\" / \"dot\")")
+        table = self._knn_matrix(kind, tables)
+        n = int(table.shape[0])
+        own = torch.arange(n, dtype=torch.int64, device=table.device)
+        ids, vals = self._knn_chunks(table, n, topk, metric, lambda a, b: table[a:b], own)
+        passes = (vals <= float(threshold)) if metric == "l2" else (vals >= float(threshold))   # (NaN padding passes neither)
+        a = own.view(-1, 1).expand_as(ids)
+        key = torch.minimum(a, ids) * n + torch.maximum(a, ids)
+        keep = passes & (ids >= 0)
+        key, order = torch.sort(key[keep])
+        score = vals[keep][order]
+        first = torch.ones_like(key, dtype=torch.bool)
+        first[1:] = key[1:] != key[:-1]
+        key, score = key[first], score[first]
+        return torch.stack([key // n, key % n], 1), score
+
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))
         if self.config.debug:

@@ -953,6 +953,71 @@ def topk_rows(scores, k, largest=False, skip_off=None, skip_ids=None, keep=None)
     return ids, vals, count
 
 
+KNN_MAX = L.KNN_MAX
+KNN_METRICS = L.KNN_METRICS
+
+
+def _knn_rows_arg(t, what):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise TypeError("%s must be a 2-D tensor" % what)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32 (got %s)" % (what, t.dtype))
+    if not t.is_cuda:
+        raise L.KgeHipError("%s must live on the HIP device (got %s); the HIP path has no CPU fallback" % (what, t.device))
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError("%s must have unit inner stride (got %d)" % (what, t.stride(1)))
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def knn_metric(metric):
+    if metric not in KNN_METRICS:
+        raise ValueError("metric = %r (one of %s)" % (metric, ", ".join(sorted(KNN_METRICS))))
+    return KNN_METRICS[metric]
+
+
+def knn_rows(table, queries, k, metric="cosine", self_ids=None):
+    """The k nearest live rows of `table` (float32 [n_rows, dim], unit inner stride, any row stride >= dim) for every row of `queries`
+    (float32 [nq, dim], likewise): (ids int32 [nq, k], scores float32 [nq, k], count int32 [nq]) in kge_knn_rows's total order --
+    nearer first ("dot" and "cosine": the higher score, "l2": the lower Euclidean distance), lower id first among equal scores, NaN
+    last.  Candidate self_ids[q] (int64 [nq], -1 = none) is not live for row q; rows with fewer than k live candidates are padded
+    with id -1 and NaN.  The select runs inside the matrix-core sweep (csrc/kge_knn.hip): no [nq, n_rows] block is written."""
+    tstride = _knn_rows_arg(table, "table")
+    qstride = _knn_rows_arg(queries, "queries")
+    if queries.device != table.device:
+        raise ValueError("table and queries live on different devices")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError("k = %d outside 1..%d (KGE_KNN_MAX)" % (k, KNN_MAX))
+    code = knn_metric(metric)
+    n_rows, dim = (int(x) for x in table.shape)
+    nq = int(queries.shape[0])
+    if int(queries.shape[1]) != dim:
+        raise ValueError("queries have %d columns, the table %d" % (queries.shape[1], dim))
+    dev = table.device
+    ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    vals = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    count = torch.empty(nq, dtype=torch.int32, device=dev)
+    if nq == 0:
+        return ids, vals, count
+    ps = None
+    if self_ids is not None:
+        if self_ids.numel() != nq:
+            raise ValueError("self_ids must hold one id per query (%d, got %d)" % (nq, self_ids.numel()))
+        ps = _dev(self_ids, torch.int64, "self_ids")
+    lib = L.load()
+    nbytes = lib.kge_knn_workspace_bytes(nq, n_rows, dim, k, code)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.check(lib.kge_knn_rows(ctypes.c_void_p(table.data_ptr()), n_rows, dim, tstride, ctypes.c_void_p(queries.data_ptr()), nq, qstride, ps,
+                             k, code, ctypes.c_void_p(ws.data_ptr()), nbytes, _dev(ids, torch.int32, "out_ids"),
+                             _dev(vals, torch.float32, "out_scores"), _dev(count, torch.int32, "out_count"), _stream()), "kge_knn_rows")
+    return ids, vals, count
+
+
+def knn_workspace_bytes(nq, n_rows, dim, k, metric="cosine"):
+    """Bytes of workspace a knn_rows call of this shape allocates (kge_knn_workspace_bytes): what the Evaluator chunks its queries by."""
+    return int(L.load().kge_knn_workspace_bytes(int(nq), int(n_rows), int(dim), int(k), knn_metric(metric)))
+
+
 CAND_CHUNK = L.CAND_CHUNK
 
 

@@ -96,6 +96,52 @@ class Model:
                 out[idx] = K.eval_sweep_scores_side(desc, queries[idx].contiguous(), side)
             return out
 
+    # ---- the rows of the nearest-neighbour search (Evaluator.nearest_*): what "the embedding of entity e" is, per model
+    # THE rule, by NamedEmbedding name: a table of parameter_list is entity-indexed when its name starts with one of the first
+    # prefixes or is one of the first names, relation-indexed likewise with the second.  Every model, by hand: TransE / TransM /
+    # HoLE / DistMult / ConvKB / MuRP / TuckER / ConvE / HypER / InteractE / AcrE / ProjE take ent_embedding(s) | rel_embedding(s)
+    # (ConvE's b [1, E], ProjE's bc / De / Dr, TuckER's W, HypER's filters are neither); TransR + rel_matrix, Rescal rel_matrices
+    # (the flattened matrices); TransH + w (the normal vectors); TransD + ent_mappings | rel_mappings; RotatE
+    # ent_embeddings_real, ent_embeddings_imag | rel_embeddings_real; KG2E ent_embeddings_mu, _sigma | rel_embeddings_mu, _sigma;
+    # Complex(N3) emb_e_real, emb_e_img | emb_rel_real, emb_rel_img; ANALOGY all three of each; CP sub_embedding, obj_embedding |
+    # rel_embedding; SimplE(_ignr) ent_head_, ent_tail_embedding | rel_, rel_inv_embedding; QuatE ent_{s,x,y,z}_embedding |
+    # rel_{s,x,y,z,w}_embedding; OctonionE ent_embedding_1..8 | rel_embedding_1..8, rel_w_embedding; NTN / SLM / SME(_BL)
+    # ent_embedding | rel_embedding (mr*, br, mu*, mv*, bu, bv are indexed by neither).
+    _MATRIX_RULE = {"entity": (("ent_", "emb_e_"), ("sub_embedding", "obj_embedding")),
+                    "relation": (("rel_", "emb_rel_"), ("w",))}
+
+    def _index_matrix(self, kind, tables):
+        prefixes, names = self._MATRIX_RULE[kind]
+        rows = int(self.tot_entity if kind == "entity" else self.tot_relation)
+        by_name = {p.name: p for p in self.parameter_list}
+        if tables is None:
+            picked = [p for p in self.parameter_list if p.name.startswith(prefixes) or p.name in names]
+        else:
+            missing = [n for n in tables if n not in by_name]
+            if missing:
+                raise KeyError("%s has no table named %s (it has %s)" % (type(self).__name__, missing, sorted(by_name)))
+            picked = [by_name[n] for n in tables]
+        if not picked:
+            raise ValueError("%s has no %s-indexed table" % (type(self).__name__, kind))
+        parts = []
+        for p in picked:
+            w = p.weight.detach()
+            if w.shape[0] < rows:
+                raise ValueError("table %s has %d rows, fewer than the %d %s ids" % (p.name, w.shape[0], rows, kind))
+            # a table with more rows than ids (the reciprocal relations of ConvE / AcrE behind the relations): the ids' own rows
+            parts.append(w[:rows].to(torch.float32))
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+
+    def entity_matrix(self, tables=None):
+        """float32 [tot_entity, D]: the model's entity-indexed tables of parameter_list (picked by name, _MATRIX_RULE), concatenated
+        along the columns in that order; a single float32 table is returned as it is, without a copy.  tables: explicit
+        NamedEmbedding names instead.  MuRP's float64 tables are converted to float32 for the search."""
+        return self._index_matrix("entity", tables)
+
+    def relation_matrix(self, tables=None):
+        """entity_matrix for the relation-indexed tables: float32 [tot_relation, D]."""
+        return self._index_matrix("relation", tables)
+
     def predict_tail_rank(self, h, r, topk=-1):
         _, rank = torch.topk(self._sweep(h, r, torch.zeros_like(h), 0), k=topk)
         return rank.view(1, -1)

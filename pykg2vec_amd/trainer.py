@@ -1207,6 +1207,21 @@ class Trainer:
         rels, _ = self.evaluator.predict_rels(h, t, topk=topk)
         return self._infer(rels, idx2rel, "(head,tail)->({},{})".format(h, t), ["head: %s" % idx2ent[h], "tail: %s" % idx2ent[t]], "rel")
 
+    def infer_similar_entities(self, e, topk=5, metric="cosine"):
+        """{entity id: name} of the topk entities nearest to entity e in embedding space (Evaluator.nearest_entities), nearest first,
+        e itself left out."""
+        self.sync_model()
+        idx2ent = self.config.knowledge_graph.read_cache_data('idx2entity')
+        ids, _ = self.evaluator.nearest_entities([int(e)], topk=topk, metric=metric)
+        return self._infer(ids, idx2ent, "(entity)->({})".format(e), ["entity: %s" % idx2ent[e]], "neighbour")
+
+    def infer_similar_relations(self, r, topk=5, metric="cosine"):
+        """infer_similar_entities for the relations nearest to relation r."""
+        self.sync_model()
+        idx2rel = self.config.knowledge_graph.read_cache_data('idx2relation')
+        ids, _ = self.evaluator.nearest_relations([int(r)], topk=topk, metric=metric)
+        return self._infer(ids, idx2rel, "(relation)->({})".format(r), ["relation: %s" % idx2rel[r]], "neighbour")
+
     # ------------------------------------------------------------------ checkpoints (reference format, utils/trainer.py:388-419)
     def _checkpoint_dir(self, path=None):
         if path is not None:
