@@ -100,7 +100,7 @@ const char* kge_last_error(void);
  * kge_eval_ranks / _grouped / kge_eval_sweep_scores (and _side), kge_rank_from_scores. */
 int kge_set_debug(int32_t check_ids);
 /* A/B switches of the dispatch rules: RESCAL_UNFUSED, RESCAL_ROWS, RESCAL_G, RESCAL_G2, TRANSR_ROWS, TRANSR_G,
- * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT, KNN_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an
+ * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT, KNN_SPLIT, TSNE_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an
  * integer; "0" off, "1" on) or, if that is unset, to the built-in rule.  Same meaning on both sides of the boundary. */
 int kge_set_switch(const char* name, int32_t value);
 int kge_get_debug(void);
@@ -161,6 +161,50 @@ size_t kge_knn_workspace_bytes(int64_t nq, int64_t n_rows, int64_t dim, int32_t 
 int kge_knn_rows(const float* table, int64_t n_rows, int64_t dim, int64_t table_stride, const float* queries, int64_t nq,
                  int64_t query_stride, const int64_t* self_ids, int32_t k, int metric, void* workspace, size_t workspace_bytes,
                  int32_t* out_ids, float* out_scores, int32_t* out_count, void* stream);
+
+/* ---- t-SNE projection of embedding rows to 2-D (kge_tsne.hip): exact t-SNE over the sparse affinities of the nearest-neighbour
+ * search; the repulsive term is an all-pairs sweep, nothing is approximated.  Every buffer is the caller's and lives on the device.
+ * Results are bit-identical from run to run: no float atomics, every sum in a fixed order.
+ *
+ * kge_tsne_affinities: dist float32 [n, k] (Euclidean, as kge_knn_rows returns them under KGE_KNN_L2) and count int32 [n] ->
+ * cond_p float32 [n, k], the conditional probabilities p_{j|i} over row i's first count[i] places (0 behind them), and beta
+ * float32 [n], the precision found.  The search is sklearn's _binary_search_perplexity (beta from 1, doubled or halved while a bound
+ * is open, bisected after, at most 100 steps, stop at |H - log perplexity| <= 1e-5) in float64, with one difference: the row's
+ * smallest squared distance is subtracted from all of them first, which leaves p unchanged and keeps rows of large distances from
+ * underflowing.  A row whose count is below the perplexity ends uniform over its live places.
+ *
+ * The joint probabilities are a CSR over n rows: row_off int64 [n + 1], col int32 [nnz] (ascending within a row, no diagonal, no
+ * duplicate), val float32 [nnz] = (p_{j|i} + p_{i|j}) / (2 n).
+ *
+ * kge_tsne_gradient: Y float32 [n, 2] -> grad float32 [n, 2], Z float64 [1] and, when KL is not NULL, KL float64 [1], with
+ *   w_ij = 1 / (1 + |y_i - y_j|^2),  Z = sum_{i != j} w_ij,
+ *   grad_i = 4 (sum_j exaggeration P_ij w_ij (y_i - y_j) - (1 / Z) sum_j w_ij^2 (y_i - y_j)),
+ *   KL = sum over stored entries of P_ij log(P_ij Z / w_ij)   (the unexaggerated P; entries with P_ij = 0 add nothing).
+ * The j range of the all-pairs sweep is cut into S slabs of whole tiles of KGE_TSNE_TILE points, S a function of n alone (the
+ * switch TSNE_SPLIT forces it); slab partials are added in slab order, Z in float64.  The same bits on every call at the same S;
+ * across S the summation order differs.
+ *
+ * kge_tsne_run: iterations [it0, it1) of sklearn's _gradient_descent without its early stopping, no host read inside:
+ *   inc = update * grad < 0;  gains = inc ? gains + 0.2 : gains * 0.8;  gains = max(gains, 0.01);
+ *   update = momentum * update - learning_rate * (gains * grad);  Y += update.
+ * State: Y, update, gains float32 [n, 2]; Y_tmp [n, 2] is scratch (the sweep reads one buffer while the step writes the other; the
+ * state is back in Y on return).  Iteration `it` is recorded when (it + 1) % record_every == 0 (record_every 0: never): KL and
+ * |grad|_2 of the Y that iteration started from go to trace[(it + 1) / record_every - 1] (float64 [n_records, 2]), so a run cut
+ * into several calls over the same trace leaves the bits of one call.
+ *
+ * workspace: kge_tsne_workspace_bytes(n) (0 for a refused n), asked for under the same switches as the call.  Refused before any GPU
+ * call, kge_last_error() naming the argument: n < 2, k outside 1..KGE_KNN_MAX, perplexity outside [1, n), an exaggeration that is
+ * not positive, a learning_rate that is not finite, momentum outside [0, 1), a null pointer, nnz outside 0..n (n - 1) (row_off[n]
+ * itself is on the device and is not read), a trace too short for it1, a workspace that is too small. */
+#define KGE_TSNE_TILE 256
+int kge_tsne_affinities(const float* dist, const int32_t* count, int64_t n, int32_t k, float perplexity, float* cond_p, float* beta,
+                        void* stream);
+size_t kge_tsne_workspace_bytes(int64_t n);
+int kge_tsne_gradient(const float* Y, int64_t n, const int64_t* row_off, const int32_t* col, const float* val, int64_t nnz,
+                      float exaggeration, void* workspace, size_t workspace_bytes, float* grad, double* Z, double* KL, void* stream);
+int kge_tsne_run(float* Y, float* Y_tmp, float* update, float* gains, int64_t n, const int64_t* row_off, const int32_t* col,
+                 const float* val, int64_t nnz, int64_t it0, int64_t it1, float exaggeration, float momentum, float learning_rate,
+                 int32_t record_every, double* trace, int64_t n_records, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
  * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).

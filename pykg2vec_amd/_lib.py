@@ -125,6 +125,7 @@ CONVKB_MAX_WIDTHS = 8
 TOPK_MAX = 1024   # KGE_TOPK_MAX: the most candidates kge_topk_rows returns per row
 KNN_MAX = 128     # KGE_KNN_MAX: the most neighbours kge_knn_rows returns per query
 KNN_METRICS = {"dot": 0, "cosine": 1, "l2": 2}   # KGE_KNN_DOT / _COSINE / _L2
+TSNE_TILE = 256   # KGE_TSNE_TILE: points per tile of the t-SNE repulsion sweep
 CAND_CHUNK = 64   # KGE_CAND_CHUNK: list entries per work item of kge_rank_candidates
 REL_CHUNK = 64    # KGE_REL_CHUNK: relation ids per work item of kge_rank_relations
 TYPED_ATTEMPTS = 16           # KGE_TYPED_ATTEMPTS: typed draws of kge_corrupt_typed before it falls back
@@ -357,6 +358,16 @@ _SIGNATURES = {
     "kge_knn_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_tsne_affinities": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_tsne_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "kge_tsne_gradient": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "kge_tsne_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
+                                    ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                    ctypes.c_size_t, ctypes.c_void_p]),
     "kge_rank_candidates_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "kge_rank_candidates": (ctypes.c_int, [ctypes.POINTER(ModelDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,

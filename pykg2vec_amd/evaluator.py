@@ -199,6 +199,7 @@ class Evaluator:
         self.relation_tie_counts = None   # [n] of the last test_relations(): relations tied with the true relation
         self.thresholds = None     # ClassificationThresholds of the last fit_thresholds()
         self.n_dropped = 0         # rows the last classification_negatives() could not find a negative for
+        self.last_projection_trace = None   # float64 [records, 2] = (KL, |grad|) of the last project_*() call
 
     # --- single-query hooks kept for Trainer.infer_* style callers (evaluator.py:249-273)
     def test_tail_rank(self, h, r, topk=-1):
@@ -391,6 +392,89 @@ class Evaluator:
         first[1:] = key[1:] != key[:-1]
         key, score = key[first], score[first]
         return torch.stack([key // n, key % n], 1), score
+
+    # --- t-SNE projection of embedding rows to 2-D (kge_tsne_*): exact t-SNE over the sparse affinities of the neighbour search
+    def _projection_init(self, X, init, seed):
+        n = int(X.shape[0])
+        if isinstance(init, torch.Tensor) or isinstance(init, np.ndarray):
+            Y = torch.as_tensor(init).detach().to(device=X.device, dtype=torch.float32)
+            if tuple(Y.shape) != (n, 2):
+                raise ValueError("init must be [%d, 2] (got %s)" % (n, list(Y.shape)))
+            return Y.clone().contiguous()
+        if init == "random":
+            gen = torch.Generator(device="cpu")
+            gen.manual_seed(int(seed))
+            return (1e-4 * torch.randn((n, 2), generator=gen, dtype=torch.float32)).to(X.device)
+        if init != "pca":
+            raise ValueError("init = %r (\"pca\", \"random\" or an [n, 2] tensor)" % (init,))
+        # the top two principal axes of the D x D covariance; an eigenvector's sign is fixed by its largest component
+        Xc = X.double() - X.double().mean(0, keepdim=True)
+        _, vec = torch.linalg.eigh(Xc.t() @ Xc / max(n - 1, 1))
+        top = vec[:, -2:].flip(1) if vec.shape[1] >= 2 else torch.cat([vec, torch.zeros_like(vec)], 1)
+        big = top.gather(0, top.abs().argmax(0, keepdim=True))
+        top = top * torch.where(big < 0, -torch.ones_like(big), torch.ones_like(big))
+        Y = Xc @ top
+        std = Y[:, 0].std(unbiased=False)
+        Y = Y / torch.where(std > 0, std, torch.ones_like(std)) * 1e-4
+        return Y.float().contiguous()
+
+    def _project(self, X, perplexity=30.0, n_iter=1000, early_exaggeration=12.0, exaggeration_iter=250, learning_rate="auto",
+                 init="pca", seed=0, record_every=50):
+        n = int(X.shape[0])
+        perplexity = float(perplexity)
+        if n < 2:
+            raise ValueError("a projection needs at least 2 rows (got %d)" % n)
+        if not 1.0 <= perplexity < n:
+            raise ValueError("perplexity = %g outside [1, n = %d)" % (perplexity, n))
+        k = min(n - 1, int(3 * perplexity))
+        if k > K.KNN_MAX:
+            raise ValueError("perplexity = %g asks for %d neighbours per row, the search returns at most %d (KGE_KNN_MAX): "
+                             "perplexity <= %d for more than %d rows" % (perplexity, k, K.KNN_MAX, K.KNN_MAX // 3, K.KNN_MAX + 1))
+        n_iter, stop = int(n_iter), min(int(exaggeration_iter), int(n_iter))
+        lr = max(n / float(early_exaggeration) / 4.0, 50.0) if isinstance(learning_rate, str) and learning_rate == "auto" else float(learning_rate)
+        own = torch.arange(n, dtype=torch.int64, device=X.device)
+        ids, dist = self._knn_chunks(X, n, k, "l2", lambda a, b: X[a:b], own)
+        count = (ids >= 0).sum(1).to(torch.int32)
+        cond_p, _ = self.K.tsne_affinities(ids, dist, count, perplexity)
+        csr = self.K.tsne_joint(ids, cond_p, count)
+        Y = self._projection_init(X, init, seed)
+        update, gains = torch.zeros_like(Y), torch.ones_like(Y)
+        Y, trace = self.K.tsne_run(csr, Y, stop, it0=0, exaggeration=float(early_exaggeration), momentum=0.5, learning_rate=lr,
+                                   record_every=record_every, update=update, gains=gains,
+                                   trace=torch.full((n_iter // record_every if record_every > 0 else 0, 2), float("nan"),
+                                                    dtype=torch.float64, device=X.device))
+        Y, trace = self.K.tsne_run(csr, Y, n_iter - stop, it0=stop, exaggeration=1.0, momentum=0.8, learning_rate=lr,
+                                   record_every=record_every, update=update, gains=gains, trace=trace)
+        self.last_projection_trace = trace
+        return Y
+
+    def _project_rows(self, kind, ids, tables, kw):
+        table = self._knn_matrix(kind, tables)
+        if ids is not None:
+            table = table[self._ids_arg(ids, "ids").to(table.device)]
+        return self._project(table if table.is_contiguous() else table.contiguous(), **kw)
+
+    def project_entities(self, ids=None, tables=None, **kw):
+        """float32 [n, 2] on the device: the t-SNE map of the entities `ids` (None: every entity), rows from
+        Model.entity_matrix(tables).  Keywords and defaults are sklearn.manifold.TSNE's: perplexity=30.0, n_iter=1000,
+        early_exaggeration=12.0, exaggeration_iter=250, learning_rate="auto" (max(n / early_exaggeration / 4, 50)), init="pca"
+        ("random", or an [n, 2] tensor), seed=0; record_every=50 iterations (KL, |grad|) go to last_projection_trace.  The
+        affinities are those of the min(n - 1, floor(3 perplexity)) nearest rows under L2 (nearest_entities' search), at most
+        KGE_KNN_MAX: up to 129 rows the graph is complete and the result is exact t-SNE.  The descent is exact too (an all-pairs
+        repulsion sweep, kge_tsne_run) and runs all n_iter iterations: there is no early stopping."""
+        return self._project_rows("entity", ids, tables, kw)
+
+    def project_relations(self, ids=None, tables=None, **kw):
+        """project_entities over Model.relation_matrix(tables)."""
+        return self._project_rows("relation", ids, tables, kw)
+
+    def project_vectors(self, X, **kw):
+        """project_entities for rows that are no table rows: X float32 [n, D], e.g. the concatenated h, r, t rows of a plot."""
+        X = X.detach() if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X))
+        X = X.to(device=self.config.device, dtype=torch.float32)
+        if X.dim() != 2:
+            raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
+        return self._project(X.contiguous(), **kw)
 
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))

@@ -3,6 +3,7 @@
 PyTorch is used here only for device memory and the current HIP stream; all arithmetic happens in
 libkge_hip.so.  Every function raises if a tensor is not a contiguous tensor on a HIP device.
 """
+import collections
 import ctypes
 import os
 import math
@@ -1016,6 +1017,135 @@ def knn_rows(table, queries, k, metric="cosine", self_ids=None):
 def knn_workspace_bytes(nq, n_rows, dim, k, metric="cosine"):
     """Bytes of workspace a knn_rows call of this shape allocates (kge_knn_workspace_bytes): what the Evaluator chunks its queries by."""
     return int(L.load().kge_knn_workspace_bytes(int(nq), int(n_rows), int(dim), int(k), knn_metric(metric)))
+
+
+# --- t-SNE projection (csrc/kge_tsne.hip): affinities from the search's neighbour lists, the joint CSR, the gradient, the descent loop
+TSNE_TILE = L.TSNE_TILE
+
+
+class TsneCSR(collections.namedtuple("TsneCSR", "row_off col val n")):
+    """The joint probabilities P of a t-SNE run: row_off int64 [n + 1], col int32 [nnz] (ascending within a row, no diagonal, no
+    duplicate), val float32 [nnz]."""
+    __slots__ = ()
+
+    @property
+    def nnz(self):
+        return int(self.col.numel())
+
+
+def _tsne_dev(t, dtype, shape, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError("%s must be a %s tensor" % (what, dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be %s (got %s)" % (what, list(shape), list(t.shape)))
+    if not t.is_cuda:
+        raise L.KgeHipError("%s must live on the HIP device (got %s); the HIP path has no CPU fallback" % (what, t.device))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def tsne_affinities(ids, dist, count, perplexity):
+    """(cond_p float32 [n, k], beta float32 [n]): the conditional probabilities p_{j|i} of every row's neighbours at the given
+    perplexity (kge_tsne_affinities).  ids [n, k], dist float32 [n, k] (Euclidean) and count int32 [n] are knn_rows's output under
+    metric="l2"; places from count[i] on get 0."""
+    if not isinstance(dist, torch.Tensor) or dist.dim() != 2:
+        raise TypeError("dist must be a 2-D tensor")
+    n, k = (int(x) for x in dist.shape)
+    if tuple(ids.shape) != (n, k):
+        raise ValueError("ids %s and dist %s differ in shape" % (list(ids.shape), [n, k]))
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError("k = %d outside 1..%d (KGE_KNN_MAX)" % (k, KNN_MAX))
+    pd = _tsne_dev(dist, torch.float32, (n, k), "dist")
+    pc = _tsne_dev(count, torch.int32, (n,), "count")
+    cond_p = torch.empty((n, k), dtype=torch.float32, device=dist.device)
+    beta = torch.empty(n, dtype=torch.float32, device=dist.device)
+    L.check(L.load().kge_tsne_affinities(pd, pc, n, k, float(perplexity), ctypes.c_void_p(cond_p.data_ptr()),
+                                         ctypes.c_void_p(beta.data_ptr()), _stream()), "kge_tsne_affinities")
+    return cond_p, beta
+
+
+def tsne_joint(ids, cond_p, count):
+    """TsneCSR of P_ij = (p_{j|i} + p_{i|j}) / (2 n) over the union of the two neighbour graphs: ONE sort of the 64-bit (i, j) keys of
+    both directions on the tensors' device.  A key occurs at most twice (a row's ids are distinct) and a sum of two floats does not
+    depend on their order, so P is symmetric bit for bit and the same on every run.  One-time set-up in torch ops; nnz is read."""
+    n, k = (int(x) for x in ids.shape)
+    dev = ids.device
+    ids64 = ids.to(torch.int64)
+    rows = torch.arange(n, dtype=torch.int64, device=dev).view(-1, 1).expand(n, k)
+    live = (torch.arange(k, dtype=torch.int64, device=dev).view(1, -1) < count.view(-1, 1).to(torch.int64)) & (ids64 >= 0) & (ids64 != rows)
+    i, j, p = rows[live], ids64[live], cond_p[live]
+    keys, order = torch.sort(torch.cat([i * n + j, j * n + i]))
+    vals = torch.cat([p, p])[order]
+    first = torch.ones_like(keys, dtype=torch.bool)
+    first[1:] = keys[1:] != keys[:-1]
+    pair = torch.zeros_like(vals)
+    pair[:-1] = torch.where(first[1:], torch.zeros_like(vals[1:]), vals[1:])     # the key's second entry, if it has one
+    keys, vals = keys[first], (vals + pair)[first] / float(2 * n)
+    row_off = torch.searchsorted(keys, torch.arange(n + 1, dtype=torch.int64, device=dev) * n)
+    return TsneCSR(row_off.contiguous(), (keys % n).to(torch.int32).contiguous(), vals.contiguous(), n)
+
+
+def _tsne_csr_args(csr, Y, what):
+    n = int(csr.n)
+    pY = _tsne_dev(Y, torch.float32, (n, 2), what)
+    nnz = csr.nnz
+    if int(csr.val.numel()) != nnz:
+        raise ValueError("csr: col holds %d entries, val %d" % (nnz, csr.val.numel()))
+    return (n, pY, _tsne_dev(csr.row_off, torch.int64, (n + 1,), "csr.row_off"), _tsne_dev(csr.col, torch.int32, (nnz,), "csr.col"),
+            _tsne_dev(csr.val, torch.float32, (nnz,), "csr.val"), nnz)
+
+
+def tsne_workspace_bytes(n):
+    return int(L.load().kge_tsne_workspace_bytes(int(n)))
+
+
+def tsne_gradient(csr, Y, exaggeration=1.0, want_kl=False):
+    """(grad float32 [n, 2], Z float64 [], KL float64 [] or None) of the t-SNE objective at the map Y float32 [n, 2] under the joint
+    probabilities `csr` (kge_tsne_gradient): the exact all-pairs gradient, every sum in a fixed order."""
+    n, pY, pr, pc, pv, nnz = _tsne_csr_args(csr, Y, "Y")
+    dev = Y.device
+    lib = L.load()
+    nbytes = lib.kge_tsne_workspace_bytes(n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    grad = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    out = torch.zeros(2, dtype=torch.float64, device=dev)
+    L.check(lib.kge_tsne_gradient(pY, n, pr, pc, pv, nnz, float(exaggeration), ctypes.c_void_p(ws.data_ptr()), nbytes,
+                                  ctypes.c_void_p(grad.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                  ctypes.c_void_p(out.data_ptr() + 8) if want_kl else None, _stream()), "kge_tsne_gradient")
+    return grad, out[0], (out[1] if want_kl else None)
+
+
+def tsne_state(Y):
+    """(update, gains) a descent starts from: zeros and ones, float32 [n, 2]."""
+    return torch.zeros_like(Y), torch.ones_like(Y)
+
+
+def tsne_run(csr, Y, n_iter, it0=0, exaggeration=1.0, momentum=0.8, learning_rate=200.0, record_every=0, update=None, gains=None,
+             trace=None):
+    """Iterations [it0, it0 + n_iter) of the t-SNE descent in one C loop (kge_tsne_run): no Python per iteration, no host read.  Y
+    float32 [n, 2] is updated IN PLACE, and so are update and gains (tsne_state(Y) when not given): all of a run's state is in
+    these three tensors, so a run cut into several calls leaves the bits of one.  Iteration `it` is recorded when
+    (it + 1) % record_every == 0: trace[(it + 1) // record_every - 1] = (KL, |grad|_2) of the Y it started from (float64
+    [records, 2], NaN where nothing was written; created for it0 + n_iter iterations when not given).  -> (Y, trace)."""
+    n, pY, pr, pc, pv, nnz = _tsne_csr_args(csr, Y, "Y")
+    dev = Y.device
+    update = torch.zeros_like(Y) if update is None else update
+    gains = torch.ones_like(Y) if gains is None else gains
+    n_iter, it0, record_every = int(n_iter), int(it0), int(record_every)
+    records = (it0 + n_iter) // record_every if record_every > 0 else 0
+    if trace is None:
+        trace = torch.full((records, 2), float("nan"), dtype=torch.float64, device=dev)
+    pt = _tsne_dev(trace, torch.float64, (int(trace.shape[0]), 2), "trace") if trace.numel() else None
+    lib = L.load()
+    nbytes = lib.kge_tsne_workspace_bytes(n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    tmp = torch.empty_like(Y)
+    L.check(lib.kge_tsne_run(pY, ctypes.c_void_p(tmp.data_ptr()), _tsne_dev(update, torch.float32, (n, 2), "update"),
+                             _tsne_dev(gains, torch.float32, (n, 2), "gains"), n, pr, pc, pv, nnz, it0, it0 + n_iter, float(exaggeration),
+                             float(momentum), float(learning_rate), record_every, pt, int(trace.shape[0]),
+                             ctypes.c_void_p(ws.data_ptr()), nbytes, _stream()), "kge_tsne_run")
+    return Y, trace
 
 
 CAND_CHUNK = L.CAND_CHUNK

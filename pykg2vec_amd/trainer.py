@@ -1222,6 +1222,29 @@ class Trainer:
         ids, _ = self.evaluator.nearest_relations([int(r)], topk=topk, metric=metric)
         return self._infer(ids, idx2rel, "(relation)->({})".format(r), ["relation: %s" % idx2rel[r]], "neighbour")
 
+    def project_entities(self, ids=None, **kw):
+        """(coords numpy float32 [n, 2], {entity id: name}): the t-SNE map of the entities `ids` (None: every entity) through
+        Evaluator.project_entities, whose keywords it takes."""
+        self.sync_model()
+        idx2ent = self.config.knowledge_graph.read_cache_data('idx2entity')
+        coords = self.evaluator.project_entities(ids, **kw).cpu().numpy()
+        which = range(len(coords)) if ids is None else [int(i) for i in self.evaluator._ids_arg(ids, "ids").tolist()]
+        return coords, {i: idx2ent[i] for i in which}
+
+    def display(self):
+        """utils/trainer.py:421-437: the embedding plots when config.plot_embedding is set (entities; relations and entities with
+        relations too unless config.plot_entity_only).  The loss-curve and result-table plots of the two other flags are not built."""
+        from .visualization import Visualization
+        cfg = self.config
+        options = {"ent_only_plot": True, "rel_only_plot": not getattr(cfg, "plot_entity_only", False),
+                   "ent_and_rel_plot": not getattr(cfg, "plot_entity_only", False)}
+        if getattr(cfg, "plot_embedding", False):
+            self.sync_model()
+            viz = Visualization(self.model, cfg, vis_opts=options, evaluator=self.evaluator)
+            viz.plot_embedding(resultpath=cfg.path_figures, algos=self.model.model_name, show_label=False)
+        if getattr(cfg, "plot_training_result", False) or getattr(cfg, "plot_testing_result", False):
+            _log("display: plot_training_result / plot_testing_result (loss curves, result tables) are not built here; nothing drawn")
+
     # ------------------------------------------------------------------ checkpoints (reference format, utils/trainer.py:388-419)
     def _checkpoint_dir(self, path=None):
         if path is not None:
