@@ -632,13 +632,11 @@ struct DzSrc {
     }
 };
 
-// four consecutive elements of a gradient row for the 128-wide products.  FUSED (the workspace of kge_head_1n_bce): rows are padded
-// to a multiple of four floats and i is a multiple of four, so this is ONE aligned 16-byte load with no control flow around it (the
-// load stays in flight across the slab it is issued in); elements past the operand -- pad columns are never written -- are masked.
-// four consecutive elements of a gradient row, the first nv of them inside the operand, in two steps: the raw fetch (dz_fetch4)
-// and, at the LDS store, the value (dz_value4).  FUSED (the workspace of kge_head_1n_bce): rows are padded to a multiple of four
-// floats and i is a multiple of four -- one aligned 16-byte load; pad columns are never written, hence the mask.  Otherwise
-// (autograd form) dpreds * p (1 - p) from two 4-byte aligned loads.
+// four consecutive elements of a gradient row for the 128-wide products, the first nv of them inside the operand, in two steps: the
+// raw fetch (dz_fetch4) and, at the LDS store, the value (dz_value4).  FUSED (the workspace of kge_head_1n_bce): rows are padded to
+// a multiple of four floats and i is a multiple of four -- ONE aligned 16-byte load with no control flow around it (the load stays in
+// flight across the slab it is issued in); pad columns are never written, hence the mask.  Otherwise (autograd form)
+// dpreds * p (1 - p) from two 4-byte aligned loads.
 struct DzRaw { float4 a, b; };
 template <bool FUSED>
 __device__ __forceinline__ DzRaw dz_fetch4(const DzSrc& g, int64_t i, int nv, int64_t total) {
