@@ -678,6 +678,11 @@ typedef struct kge_pull_direction {
 int kge_pull_direction_bytes(int32_t dim, int32_t l1, int64_t n_pairs, size_t* codes_bytes, size_t* recs_bytes);
 int kge_pull_partial_stride(int32_t dim);
 int kge_pull_hat_stride(int32_t dim);         /* floats between consecutive rows of the hat tables (kge_row_norms writes, kge_pull_step reads / writes) */
+/* 1 while the two-phase form with an optimiser runs hat-less (switch KGE_PULL_HATLESS / kge_set_switch("PULL_HATLESS")): phase 1 gathers
+ * the table rows and scales them by 1 / max(norm_in, 1e-12) itself -- bit for bit the hat rows -- and phase 2 writes no hat_out.  Such
+ * a step neither reads hat_in nor writes hat_out (both must still be passed); a caller that keeps hat tables rebuilds them with
+ * kge_row_norms before a step that reads them: the one-phase form, the gradient form, any step with the switch off. */
+int kge_pull_hatless(void);
 int kge_pull_groups_per_block(int32_t dim);   /* owner groups per 256-thread workgroup: items are laid out in workgroup slots */
 int kge_row_norms(const float* table, int64_t rows, int32_t dim, float* norms, float* normalised, void* stream);
 int kge_pull_sample(const int32_t* pairs, const int32_t* inv, int64_t n, int64_t tot_entity, const float* bern_prob,

@@ -205,6 +205,7 @@ int launch_optimizer_rows_rownorm(int kind, float* p, float* g, float* s1, float
 // kge_pull.hip (owner-computes training step: no atomics, optimiser fused, deterministic)
 int pull_partial_stride(int dim);
 int pull_hat_stride(int dim);
+int pull_hatless();
 // the staged owner-computes step of the remaining pointwise gather models (kge_ownx.hip)
 bool ownx_model(int model);
 int ownx_groups_per_block(int model, int dim);

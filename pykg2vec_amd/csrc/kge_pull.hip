@@ -65,6 +65,8 @@ struct PullArgs {
                                // low byte) and of the negative residual (high byte) -- one 16-bit load per visit
     int64_t n_pairs;
     unsigned wt;               // kWt* bits: the output streams stored write-through (store16_wt) instead of left dirty in the XCD's L2
+    unsigned hatless;          // two-phase form only (switch PULL_HATLESS): k_pull_eval_nohat scales table rows by 1 / norm_in itself, the
+                               // owners (k_pull_step_nohat, k_pull_finish<..., true>) write no hat rows; hat_in / hat_out are not touched
 };
 
 #define KGE_F4_EACH(expr_x, expr_y, expr_z, expr_w) expr_x; expr_y; expr_z; expr_w;
@@ -77,15 +79,15 @@ __device__ __forceinline__ int mad_i24(int a, int b, int c) {
 }
 
 // gradient wrt the NORMALISED own row, summed over incidences -> normalisation backward -> optimiser -> new row, its
-// normalised copy and its norm
-template <int OPT, int G, int NV, bool PRE = false>
+// normalised copy (HATLESS: not the copy -- its only reader would be the evaluation, which then derives it from row and norm) and its norm
+template <int OPT, int G, int NV, bool PRE = false, bool HATLESS = false>
 __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const float4 (&X)[NV], float nX, const float4 (&gs)[NV],
                                                 int gl, const float4* pre1 = nullptr, const float4* pre2 = nullptr) {
     const int nvec = a.d >> 2;
     const bool is_rel = g >= a.E;
     // (pointer selects, not a[tb]: a runtime index into a kernel-argument array would put the array in scratch)
     float* const t_out = is_rel ? a.tab_out[1] : a.tab_out[0];
-    float* const h_out = is_rel ? a.hat_out[1] : a.hat_out[0];
+    float* const h_out = HATLESS ? nullptr : (is_rel ? a.hat_out[1] : a.hat_out[0]);
     float* const st1 = is_rel ? a.s1[1] : a.s1[0];
     float* const st2 = is_rel ? a.s2[1] : a.s2[0];
     const int64_t off = (int64_t)(is_rel ? g - a.E : g) * a.d;
@@ -141,7 +143,7 @@ __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const 
     // (lanes beyond the row hold zeros: X = 0, gs = 0, state loaded as 0 -> every optimiser leaves p = 0, n2 unchanged)
     n2 = gsum<G>(n2);
     const float nn = sqrtf(n2);
-    const float inn = 1.0f / fmaxf(nn, kEpsNormalize);
+    const float inn = 1.0f / fmaxf(nn, kEpsNormalize);   // (HATLESS: unused)
     // Per stream: a plain store stays dirty in this XCD's L2 and is written back at the launch boundary, in front of k_pull_eval; a
     // write-through store leaves while the other owners still work (profiles/r14_experiments.md).  The flavours are
     // kernel-uniform.  All four on (what ships) and all four off are straight-line blocks; a mixed choice (A/B runs) pays a scalar
@@ -152,12 +154,15 @@ __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const 
         store_row4<G, NV>(t_out + off, P, nvec, gl, wt_tab);
         if constexpr (OPT != KGE_OPT_SGD) store_row4<G, NV>(st1 + off, M1, nvec, gl, wt_s1);
         if constexpr (OPT == KGE_OPT_ADAM) store_row4<G, NV>(st2 + off, M2, nvec, gl, wt_s2);
+        if constexpr (!HATLESS) {   // (HATLESS: no scaled copy, no fourth stream)
 #pragma unroll
-        for (int v = 0; v < NV; ++v) { P[v].x *= inn; P[v].y *= inn; P[v].z *= inn; P[v].w *= inn; }
-        store_row4<G, NV>(reinterpret_cast<float*>(hrow), P, hvec, gl, wt_hat);
+            for (int v = 0; v < NV; ++v) { P[v].x *= inn; P[v].y *= inn; P[v].z *= inn; P[v].w *= inn; }
+            store_row4<G, NV>(reinterpret_cast<float*>(hrow), P, hvec, gl, wt_hat);
+        }
     };
-    const unsigned wt = a.wt & kWtFinish;
-    if (wt == kWtFinish) store_streams(true, true, true, true);
+    constexpr unsigned kStreams = HATLESS ? kWtFinish & ~kWtHat : kWtFinish;
+    const unsigned wt = a.wt & kStreams;
+    if (wt == kStreams) store_streams(true, true, true, true);
     else if (wt == 0u) store_streams(false, false, false, false);
     else store_streams((wt & kWtTab) != 0, (wt & kWtS1) != 0, (wt & kWtS2) != 0, (wt & kWtHat) != 0);
     if (gl == 0) a.norm_out[g] = nn;
@@ -184,15 +189,26 @@ constexpr bool kHatCompactDefault = true;   // hat rows: padded to 4 * G * NV fl
 // (C1, NV = 1: 62 VGPRs -- 8 waves per SIMD, the launch's 2 048 workgroups are one residency round; tests/test_pull_occupancy.py checks it)
 // (WT: records and codes stored write-through, switch WT_EVAL -- a kernel of its own, k_pull_eval_wt, so that the shipped kernel carries
 //  none of its code: the flavour as a run-time branch cost k_pull_eval 0.18 us, profiles/r14_experiments.md section 4)
-template <bool L1, int G, int NV, bool WT>
+// (HATLESS, switch PULL_HATLESS -- again a kernel of its own, k_pull_eval_nohat: the four rows are gathered from the TABLES, 4 * d bytes
+//  apart like compact hat rows, and scaled in place by 1 / max(norm, eps) of their row before the residuals: the very expression, on the
+//  very operands, that pull_finish_row / k_row_norms store as a hat row, so the scaled row is that hat row bit for bit (-ffp-contract=off:
+//  the multiply is not fused into the residual's add) and the owners need not write the hat tables at all.  The 4 * PP inverse norms of a
+//  lane group live in ONE register: lane k < 4 * PP loads the norm of the group's k-th row (h, E + r, t, c of pair 0, then of pair 1) and
+//  takes the reciprocal; a row is scaled by the value broadcast from its lane.  Eight scalars per lane instead -- 68-70 VGPRs -- would
+//  lose the 8-waves-per-SIMD residency round: profiles/r14_experiments.md section 6, profiles/r30_experiments.md)
+#ifndef KGE_HATLESS_READLANE
+#define KGE_HATLESS_READLANE 0   /* 1 (G = 32 only): two v_readlane + a select per row instead of one ds_bpermute; registers of both forms in r30 */
+#endif
+template <bool L1, int G, int NV, bool WT, bool HATLESS = false>
 __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restrict__ loss) {
     constexpr int GPB = kBlock / G, PP = kEvalPP;
+    static_assert(4 * PP <= G, "one lane per gathered row holds its inverse norm");
     KGE_TS_BEGIN(1)
     const int gl = threadIdx.x % G;
     float acc = 0.f;
-    const char* __restrict__ hat_e = reinterpret_cast<const char*>(a.hat_in[0]);
-    const char* __restrict__ hat_r = reinterpret_cast<const char*>(a.hat_in[1]);
-    const unsigned kRowBytes = a.hat_row_bytes;
+    const char* __restrict__ hat_e = reinterpret_cast<const char*>(HATLESS ? a.tab_in[0] : a.hat_in[0]);
+    const char* __restrict__ hat_r = reinterpret_cast<const char*>(HATLESS ? a.tab_in[1] : a.hat_in[1]);
+    const unsigned kRowBytes = HATLESS ? 4u * (unsigned)a.d : a.hat_row_bytes;
     const unsigned lane_off = 16u * gl;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     int64_t idx[PP];
@@ -216,6 +232,16 @@ __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restr
         ot[q] = (unsigned)p[q].z * kRowBytes + lane_off; oc[q] = (unsigned)(w[q] & 0xFFFFFF) * kRowBytes + lane_off;
         th[q] = a.theta ? a.theta[p[q].y] : 1.0f;
     }
+    float inv = 0.f;   // HATLESS: lane 4 q + role holds 1 / max(norm, eps) of that row of pair q
+    if constexpr (HATLESS) {
+        int row = 0;
+#pragma unroll
+        for (int q = 0; q < PP; ++q) {
+            const int role = gl - 4 * q;
+            row = role == 0 ? p[q].x : (role == 1 ? a.E + p[q].y : (role == 2 ? p[q].z : (role == 3 ? (w[q] & 0xFFFFFF) : row)));
+        }
+        if (gl < 4 * PP) inv = 1.0f / fmaxf(a.norm_in[row], kEpsNormalize);   // (ids of a clamped dead pair are those of the last pair: in range)
+    }
 #pragma unroll
     for (int v = 0; v < NV; ++v) {   // ONE predicated region per chunk for all PP x 4 row gathers (padded rows: every lane is inside)
 #pragma unroll
@@ -234,6 +260,19 @@ __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restr
     for (int q = 0; q < PP; ++q) {
         const int64_t i = idx[q];
         const bool tail = ((w[q] >> 24) & 1) != 0;
+        if constexpr (HATLESS) {   // rows -> normalised rows, in place
+            auto scale = [&](float4 (&x)[NV], int k) {
+                float s;
+                if constexpr (KGE_HATLESS_READLANE && G == 32) {   // (two groups per wave: one SGPR per half-wave)
+                    const float s_lo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), k));
+                    const float s_hi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), 32 + k));
+                    s = (threadIdx.x & 32) ? s_hi : s_lo;
+                } else s = __shfl(inv, k, G);
+#pragma unroll
+                for (int v = 0; v < NV; ++v) { x[v].x *= s; x[v].y *= s; x[v].z *= s; x[v].w *= s; }
+            };
+            scale(hh[q], 4 * q); scale(rr[q], 4 * q + 1); scale(tt[q], 4 * q + 2); scale(cc[q], 4 * q + 3);
+        }
         float4 up[NV], un[NV];
         float sp = 0.f, sn = 0.f;
 #pragma unroll
@@ -290,13 +329,20 @@ template <bool L1, int G, int NV>
 __global__ __launch_bounds__(kBlock) void k_pull_eval(PullArgs a, float* __restrict__ loss) { pull_eval_body<L1, G, NV, false>(a, loss); }
 template <bool L1, int G, int NV>
 __global__ __launch_bounds__(kBlock) void k_pull_eval_wt(PullArgs a, float* __restrict__ loss) { pull_eval_body<L1, G, NV, true>(a, loss); }
+template <bool L1, int G, int NV>
+__global__ __launch_bounds__(kBlock) void k_pull_eval_nohat(PullArgs a, float* __restrict__ loss) { pull_eval_body<L1, G, NV, false, true>(a, loss); }
+template <bool L1, int G, int NV>
+__global__ __launch_bounds__(kBlock) void k_pull_eval_nohat_wt(PullArgs a, float* __restrict__ loss) { pull_eval_body<L1, G, NV, true, true>(a, loss); }
 
 // (two-phase form with NV = 1: 8 waves per SIMD, 2 048 workgroup slots instead of 1 792 for the C1 launch's 2 045 owner and 128 sampler
 //  workgroups.  The attribute is a guard: the code fits without it; an edit that needs more registers now spills, which
 //  tests/test_pull_occupancy.py reports)
-template <int OPT, bool L1, int G, int NV, bool DIR = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIR && NV == 1 ? 8 : 1))) void k_pull_step(PullArgs a, PullSampleArgs sa, float* __restrict__ loss) {
+//  (HATLESS: the owners of the two-phase form that finish their rows without the hat stream -- a kernel of its own, k_pull_step_nohat, so
+//  that the shipped kernel carries no flavour branch: those cost 0.1-0.4 us here, profiles/r14_experiments.md)
+template <int OPT, bool L1, int G, int NV, bool DIR, bool HATLESS>
+__device__ __forceinline__ void pull_step_body(const PullArgs& a, const PullSampleArgs& sa, float* __restrict__ loss) {
     static_assert(!DIR || L1, "the two-phase form exists for L1 only");
+    static_assert(!HATLESS || (DIR && OPT != KGE_OPT_GRADIENT), "only the two-phase optimiser step has a reader-less hat stream");
     constexpr int GPB = kBlock / G;
     KGE_TS_BEGIN(0)
     if ((int)blockIdx.x < a.sample_blocks) {   // leading blocks: the sampler of the NEXT batch rides along (writes the other list set)
@@ -606,7 +652,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIR && N
             if (cnt > kPullCap) a.lists.head[g] = -1;
         }
         if (kind == 0) {
-            pull_finish_row<OPT, G, NV, DIR && OPT != KGE_OPT_GRADIENT>(a, g, X, nX, gs, gl, S1, S2);
+            pull_finish_row<OPT, G, NV, DIR && OPT != KGE_OPT_GRADIENT, HATLESS>(a, g, X, nX, gs, gl, S1, S2);
         } else if (kind == 3) {
 #pragma unroll
             for (int v = 0; v < NV; ++v) s_part[threadIdx.x / G][v * G + gl] = gs[v];
@@ -626,14 +672,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIR && N
                 gs[v].x += p.x; gs[v].y += p.y; gs[v].z += p.z; gs[v].w += p.w;
             }
         }
-        pull_finish_row<OPT, G, NV, DIR && OPT != KGE_OPT_GRADIENT>(a, g, X, nX, gs, gl, S1, S2);
+        pull_finish_row<OPT, G, NV, DIR && OPT != KGE_OPT_GRADIENT, HATLESS>(a, g, X, nX, gs, gl, S1, S2);
     }
     block_accumulate_loss<G>(acc, gl, loss);
     KGE_TS_END(0, 1)
 }
+template <int OPT, bool L1, int G, int NV, bool DIR = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIR && NV == 1 ? 8 : 1))) void k_pull_step(PullArgs a, PullSampleArgs sa, float* __restrict__ loss) {
+    pull_step_body<OPT, L1, G, NV, DIR, false>(a, sa, loss);
+}
+template <int OPT, int G, int NV>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NV == 1 ? 8 : 1))) void k_pull_step_nohat(PullArgs a, PullSampleArgs sa, float* __restrict__ loss) {
+    pull_step_body<OPT, true, G, NV, true, true>(a, sa, loss);
+}
 
 // rows cut into several segments: add the segments' partial sums in segment order, then finish the row
-template <int OPT, int G, int NV>
+template <int OPT, int G, int NV, bool HATLESS = false>
 __global__ __launch_bounds__(kBlock) void k_pull_finish(PullArgs a) {
     constexpr int GPB = kBlock / G;
     const int gl = threadIdx.x % G;
@@ -654,7 +708,7 @@ __global__ __launch_bounds__(kBlock) void k_pull_finish(PullArgs a) {
             gs[v].x += p.x; gs[v].y += p.y; gs[v].z += p.z; gs[v].w += p.w;
         }
     }
-    pull_finish_row<OPT, G, NV>(a, g, X, a.norm_in[g], gs, gl);
+    pull_finish_row<OPT, G, NV, false, HATLESS>(a, g, X, a.norm_in[g], gs, gl);
 }
 
 // L2 norms and normalised copies of the rows of a table, in the lane layout / operation order pull_finish_row uses
@@ -737,9 +791,21 @@ static int launch_pull_geo(PullArgs& a, const PullSampleArgs& sa, float* loss, h
     a.sample_blocks = sa.n > 0 ? (int)((sa.n + kBlock - 1) / kBlock) : 0;
     if (a.recs) {   // two-phase form (L1 only): evaluate every pair once, then let the owners sum the records
         const unsigned eb = (unsigned)((a.n_pairs + GPB * kEvalPP - 1) / (GPB * kEvalPP));
+        const dim3 ob((unsigned)(item_blocks + a.sample_blocks));
+        if constexpr (OPT != KGE_OPT_GRADIENT) {
+            if (a.hatless) {   // (launch_pull_step: never set for the gradient form, whose caller keeps no hat_out)
+                if (a.wt & kWtEval) hipLaunchKernelGGL((k_pull_eval_nohat_wt<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
+                else hipLaunchKernelGGL((k_pull_eval_nohat<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
+                hipLaunchKernelGGL((k_pull_step_nohat<OPT, G, NV>), ob, dim3(kBlock), 0, s, a, sa, loss);
+                int rc = check_launch("k_pull_step_nohat");
+                if (rc || a.n_multi == 0) return rc;
+                hipLaunchKernelGGL((k_pull_finish<OPT, G, NV, true>), dim3((unsigned)((a.n_multi + GPB - 1) / GPB)), dim3(kBlock), 0, s, a);
+                return check_launch("k_pull_finish");
+            }
+        }
         if (a.wt & kWtEval) hipLaunchKernelGGL((k_pull_eval_wt<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
         else hipLaunchKernelGGL((k_pull_eval<true, G, NV>), dim3(eb), dim3(kBlock), 0, s, a, loss);
-        hipLaunchKernelGGL((k_pull_step<OPT, true, G, NV, true>), dim3((unsigned)(item_blocks + a.sample_blocks)), dim3(kBlock), 0, s, a, sa, loss);
+        hipLaunchKernelGGL((k_pull_step<OPT, true, G, NV, true>), ob, dim3(kBlock), 0, s, a, sa, loss);
 #ifdef KGE_TS_DEBUG
         // timeline study of the boundary BEHIND the owner launch (tools/wg_timeline.py c1gap): KGE_TS_EVAL_AFTER=1 repeats the evaluation
         // after it -- same inputs, same records and codes; the loss counts twice -- so that the last records of the two slots are
@@ -788,6 +854,13 @@ static unsigned write_through_mask() {
         if (sw >= 0 ? sw != 0 : st.on) m |= st.bit;
     }
     return m;
+}
+// Do the two-phase launches leave the hat tables alone (switch PULL_HATLESS)?  Read per launch; callers that keep hat tables ask the same
+// question (kge_pull_hatless) to know when theirs have gone stale.
+constexpr bool kHatlessDefault = true;   // (same-box A/B against the parent: 24.63-24.85 against 24.94-25.14 us per step, profiles/r30_experiments.md)
+int pull_hatless() {
+    const int sw = switch_value("PULL_HATLESS");
+    return (sw >= 0 ? sw != 0 : kHatlessDefault) ? 1 : 0;
 }
 int pull_hat_stride(int dim) { const PullGeo g = pull_geo(dim); return g.G ? (int)(hat_row_bytes(g, dim) / 4) : 0; }
 int pull_groups_per_block(int dim) { const PullGeo g = pull_geo(dim); return g.G ? kBlock / g.G : 0; }
@@ -840,6 +913,7 @@ int launch_pull_step(const kge_model_desc* m, float* const tables_out[2], const 
     a.codes = two_phase ? dir->codes : nullptr;
     a.n_pairs = two_phase ? dir->n_pairs : 0;
     a.wt = write_through_mask();
+    a.hatless = two_phase && optimizer != KGE_OPT_GRADIENT && pull_hatless() ? 1u : 0u;
     PullSampleArgs sa = make_sample_args(next_pairs, next_inv, next_pairs && next_lists ? next_n : 0, m->tot_entity, bern, slots,
                                          n_slots, seed, next_offset, nullptr, next_lists);
     sa.no_desc = two_phase && dir->lists_without_descriptors ? 1 : 0;

@@ -1402,6 +1402,11 @@ def pull_hat_stride(dim):
     return int(L.load().kge_pull_hat_stride(int(dim)))
 
 
+def pull_hatless():
+    """Do two-phase optimiser steps currently run hat-less (switch PULL_HATLESS: hat tables neither read nor written)?"""
+    return bool(L.load().kge_pull_hatless())
+
+
 def pull_groups_per_block(dim):
     return int(L.load().kge_pull_groups_per_block(int(dim)))
 

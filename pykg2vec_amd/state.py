@@ -230,12 +230,33 @@ class PullState(OwnerRunState):
         # two-phase ("staged direction") form: every pair evaluated once (k_pull_eval), the owners sum its record
         self.direction = K.PullDirection(batch_size, d, bool(getattr(model, "l1_flag", True)), dev) if two_phase else None
         self.cur = 0
+        self.plan, self.plan_two_phase = None, False   # the Trainer's kernels.PullPlan over this state and the form of its steps
+        # hat-less two-phase steps (K.pull_hatless()) neither read nor write the hat tables: after them hats[cur] no longer describes
+        # tables[cur], and whoever reads hats asks fresh_hats() first
+        self.hats_stale = False
 
     def run_steps(self, gen, index, n_steps, flat, run):
         """As OwnerRunState.run_steps; `run` also takes, after n_steps, the table half the first step reads (the halves alternate)."""
         first = gen._batch_idx
         super().run_steps(gen, index, n_steps, flat, lambda b, n, *rest: run(b, n, self.cur, *rest))
         self.cur ^= (gen._batch_idx - first) & 1
+
+    def run_plan_steps(self, gen, index, n_steps, flat):
+        """run_steps through `self.plan`, with the hat tables looked after: rebuilt first if the steps read them, marked stale if not."""
+        if n_steps <= 0:
+            return
+        hatless = self.plan_two_phase and K.pull_hatless()   # (once per run: the native loop asks nothing of Python)
+        if not hatless:
+            self.fresh_hats()
+        self.run_steps(gen, index, n_steps, flat, self.plan.run)
+        self.hats_stale = hatless
+
+    def fresh_hats(self):
+        """Before a launch that reads hats[cur]: rebuild them from the current tables if hat-less steps left them behind."""
+        if self.hats_stale:
+            for t, (lo, hi) in enumerate(((0, self.E), (self.E, self.E + self.R))):
+                K.row_norms(self.tables[self.cur][t], self.norms[self.cur][lo:hi], self.hats[self.cur][t])
+            self.hats_stale = False
 
     def sync_in(self):
         """(Re)derive the row norms from the tables the model currently holds (they may have been set from outside)."""
@@ -246,6 +267,7 @@ class PullState(OwnerRunState):
         self.sync_out()
         K.row_norms(self.tables[0][0], self.norms[0][:self.E], self.hats[0][0])
         K.row_norms(self.tables[0][1], self.norms[0][self.E:], self.hats[0][1])
+        self.hats_stale = False
 
     def refresh_norms(self):
         """Row norms / normalised copies of the current parameter tables (after the all-gather of a data-parallel step)."""
@@ -262,6 +284,7 @@ class PullState(OwnerRunState):
         if self.cur == 1 and not self.grad_only:
             self.flat.param.copy_(self.alt)
             self.norms[0].copy_(self.norms[1])
-            for t in (0, 1):
-                self.hats[0][t].copy_(self.hats[1][t])
+            if not self.hats_stale:   # (stale hats stay stale in either half: nothing to carry over)
+                for t in (0, 1):
+                    self.hats[0][t].copy_(self.hats[1][t])
             self.cur = 0

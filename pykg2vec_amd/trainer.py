@@ -423,21 +423,31 @@ class Trainer:
 
     def _pull_state(self):
         idx = self.generator.pull_index()
+        two_phase = self._pull_two_phase()
         if getattr(self, "_pull", None) is None or self._pull.batch_size != idx.batch_size:
-            ps = self._pull = PullState(self.flat, self.model, idx.batch_size, idx.max_slots, two_phase=self._pull_two_phase())
+            ps = self._pull = PullState(self.flat, self.model, idx.batch_size, idx.max_slots, two_phase=two_phase)
             ps.sync_in()
+        ps = self._pull
+        if ps.plan is None or ps.plan_two_phase != (two_phase and ps.direction is not None):
+            if ps.plan is not None:
+                # the form changed on a live state (KGE_PULL_DIR flipped): a sampler that rode in a two-phase launch filed no visit
+                # descriptors, which one-phase owners read -- the next run samples its first batch itself
+                for ls in ps.lists:
+                    ls.clear()
+                ps.ready = None
             gen, cfg = self.generator, self.config
+            ps.plan_two_phase = two_phase and ps.direction is not None
             ps.plan = K.PullPlan(self.model.kernel_name, self.model.desc_kwargs(), cfg.tot_entity, cfg.tot_relation,
                                  [t + self._pull_fixed_tables() for t in ps.tables], ps.hats,
                                  ps.norms, ps.state1, ps.state2, ps.lists, idx, ps.partials, cfg.margin, cfg.optimizer,
                                  cfg.learning_rate, self.loss_buf, gen.bern, gen.slots, gen.seed,
-                                 idx.batch_size * gen.neg_rate, direction=ps.direction)
-        return self._pull, idx
+                                 idx.batch_size * gen.neg_rate, direction=ps.direction if ps.plan_two_phase else None)
+        return ps, idx
 
     def _pull_steps(self, n_steps):
         """The next n_steps steps of the current epoch, enqueued by one native call (kge_pull_run)."""
         ps, idx = self._pull_state()
-        ps.run_steps(self.generator, idx, n_steps, self.flat, ps.plan.run)
+        ps.run_plan_steps(self.generator, idx, n_steps, self.flat)
 
     def pull_step_explicit(self, ph, pr, pt, nh, nr, nt, segment=None, compact=None):
         """The owner-computes step on an explicit batch (positives + given negatives, neg_rate 1): the incidence index
@@ -460,6 +470,7 @@ class Trainer:
                     ps.lists[0], items, inc,
                     ps.partials, multi, self.config.margin, self.config.optimizer, self.config.learning_rate,
                     self.flat.step, self.loss_buf, dense_skip=skip, direction=ps.direction)
+        ps.hats_stale = ps.direction is not None and K.pull_hatless()
         ps.cur = 1
         ps.sync_out()
 
