@@ -679,12 +679,14 @@ int kge_pull_direction_bytes(int32_t dim, int32_t l1, int64_t n_pairs, size_t* c
 int kge_pull_partial_stride(int32_t dim);
 int kge_pull_hat_stride(int32_t dim);         /* floats between consecutive rows of the hat tables (kge_row_norms writes, kge_pull_step reads / writes) */
 /* 1 while the two-phase form with an optimiser runs hat-less (switch KGE_PULL_HATLESS / kge_set_switch("PULL_HATLESS")): phase 1 gathers
- * the table rows and scales them by 1 / max(norm_in, 1e-12) itself -- bit for bit the hat rows -- and phase 2 writes no hat_out.  Such
+ * the table rows and scales them by the stored 1 / max(norm_in, 1e-12) itself -- bit for bit the hat rows -- and phase 2 writes no hat_out.  Such
  * a step neither reads hat_in nor writes hat_out (both must still be passed); a caller that keeps hat tables rebuilds them with
  * kge_row_norms before a step that reads them: the one-phase form, the gradient form, any step with the switch off. */
 int kge_pull_hatless(void);
 int kge_pull_groups_per_block(int32_t dim);   /* owner groups per 256-thread workgroup: items are laid out in workgroup slots */
 int kge_row_norms(const float* table, int64_t rows, int32_t dim, float* norms, float* normalised, void* stream);
+/* The same, and inv_norms[r] = 1 / max(norms[r], 1e-12) (NULL: not written): the scale of the hat-less two-phase step, below. */
+int kge_row_norms_inv(const float* table, int64_t rows, int32_t dim, float* norms, float* inv_norms, float* normalised, void* stream);
 int kge_pull_sample(const int32_t* pairs, const int32_t* inv, int64_t n, int64_t tot_entity, const float* bern_prob,
                     const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t offset, const int64_t* dev_cursor,
                     const kge_pull_lists* out, void* stream);
@@ -698,6 +700,18 @@ int kge_pull_step(const kge_model_desc* m, float* const tables_out[2], const flo
                   int32_t reset_lists, const int32_t* next_pairs, const int32_t* next_inv, int64_t next_n, const float* bern_prob,
                   const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t next_offset, const kge_pull_lists* next_lists,
                   float* loss, const kge_pull_direction* direction /* NULL: one-phase step */, void* stream);
+/* kge_pull_step with the inverse row norms 1 / max(norm, 1e-12) of both halves ([E + R] floats each, next to norm_in / norm_out).  Only
+ * the hat-less two-phase step touches them: its phase 1 scales the gathered table rows by inv_norm_in, its owners store inv_norm_out with
+ * the norm of every row they finish; that step is refused without them (kge_pull_step passes NULL).  Every other form neither reads nor
+ * writes them, so after such a step inv_norm_out is stale: kge_row_norms_inv rebuilds it before the next hat-less step. */
+int kge_pull_step_inv(const kge_model_desc* m, float* const tables_out[2], const float* const hat_in[2], float* const hat_out[2],
+                  const float* norm_in, float* norm_out, const float* inv_norm_in, float* inv_norm_out,
+                  float* const state1[2], float* const state2[2], const int32_t* pairs, const kge_pull_lists* lists,
+                  const int32_t* items, int64_t n_items, const uint32_t* dense_skip, const int32_t* inc, float* partials, const int32_t* multi,
+                  int64_t n_multi, float margin, int32_t optimizer, float lr, int64_t step, const float* dev_hyper,
+                  int32_t reset_lists, const int32_t* next_pairs, const int32_t* next_inv, int64_t next_n, const float* bern_prob,
+                  const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t next_offset, const kge_pull_lists* next_lists,
+                  float* loss, const kge_pull_direction* direction, void* stream);
 
 /* A whole run of consecutive owner-computes steps enqueued by ONE native call (the per-step work is ~35 us of GPU time: a
  * Python-level loop cannot keep the queue full).  The plan holds everything that does not change between steps. */
@@ -734,6 +748,7 @@ typedef struct kge_pull_plan {
     int64_t draws_per_batch;      /* Philox counters consumed per batch (= n_pairs * neg_rate) */
     float* loss;
     kge_pull_direction direction; /* codes == NULL: one-phase steps; else the two-phase form (n_pairs is taken from each batch) */
+    float* inv_norm[2];           /* [half] 1 / max(norm, 1e-12), E + R: the hat-less two-phase steps' scale (kge_pull_step_inv) */
 } kge_pull_plan;
 /* Steps on batches first_batch .. first_batch + n_steps - 1.  src_half: the table half the first step reads (halves
  * alternate); cur_list: the list set the first step consumes; lists_ready == 0: a stand-alone sampler launch fills it first

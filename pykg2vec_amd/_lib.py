@@ -69,7 +69,7 @@ class PullPlanC(ctypes.Structure):
                 ("margin", ctypes.c_float), ("optimizer", ctypes.c_int32), ("lr", ctypes.c_float),
                 ("bern_prob", ctypes.c_void_p), ("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int64),
                 ("seed", ctypes.c_uint64), ("draws_per_batch", ctypes.c_int64), ("loss", ctypes.c_void_p),
-                ("direction", PullDirection)]
+                ("direction", PullDirection), ("inv_norm", ctypes.c_void_p * 2)]
 
 class TransXPlanC(ctypes.Structure):
     """struct kge_transx_plan"""
@@ -465,10 +465,17 @@ _SIGNATURES = {
     "kge_pull_hatless": (ctypes.c_int, []),
     "kge_pull_groups_per_block": (ctypes.c_int, [ctypes.c_int32]),
     "kge_row_norms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_row_norms_inv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_pull_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(PullLists), ctypes.c_void_p]),
     "kge_pull_lists_explicit": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.POINTER(PullLists), ctypes.c_void_p]),
     "kge_pull_step": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 8 + [ctypes.POINTER(PullLists), ctypes.c_void_p,
+                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                     ctypes.c_int32, ctypes.c_float, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                     ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(PullLists), ctypes.c_void_p,
+                                     ctypes.POINTER(PullDirection), ctypes.c_void_p]),
+    "kge_pull_step_inv": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 10 + [ctypes.POINTER(PullLists), ctypes.c_void_p,
                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
                                      ctypes.c_int32, ctypes.c_float, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,

@@ -536,9 +536,12 @@ int kge_pull_hat_stride(int32_t dim) { return pull_hat_stride(dim); }
 int kge_pull_hatless(void) { return pull_hatless(); }
 int kge_pull_groups_per_block(int32_t dim) { return pull_groups_per_block(dim); }
 
-int kge_row_norms(const float* table, int64_t rows, int32_t dim, float* norms, float* normalised, void* stream) {
+int kge_row_norms_inv(const float* table, int64_t rows, int32_t dim, float* norms, float* inv_norms, float* normalised, void* stream) {
     if (!table || !norms || rows < 0 || dim <= 0) { set_error("kge_row_norms: bad arguments"); return -1; }
-    return launch_row_norms(table, rows, dim, norms, normalised, (hipStream_t)stream);
+    return launch_row_norms(table, rows, dim, norms, inv_norms, normalised, (hipStream_t)stream);
+}
+int kge_row_norms(const float* table, int64_t rows, int32_t dim, float* norms, float* normalised, void* stream) {
+    return kge_row_norms_inv(table, rows, dim, norms, nullptr, normalised, stream);
 }
 
 static int lists_ok(const kge_pull_lists* l) { return l && l->pc && l->count && l->bucket && l->head && l->next && l->sdesc && l->dbucket; }
@@ -570,8 +573,8 @@ int kge_pull_lists_explicit(const int32_t* pairs, const int32_t* inv, const int6
     return launch_pull_lists_explicit(pairs, inv, nh, nt, n, out, (hipStream_t)stream);
 }
 
-int kge_pull_step(const kge_model_desc* m, float* const tables_out[2], const float* const hat_in[2], float* const hat_out[2],
-                  const float* norm_in, float* norm_out,
+int kge_pull_step_inv(const kge_model_desc* m, float* const tables_out[2], const float* const hat_in[2], float* const hat_out[2],
+                  const float* norm_in, float* norm_out, const float* inv_norm_in, float* inv_norm_out,
                   float* const state1[2], float* const state2[2], const int32_t* pairs, const kge_pull_lists* lists,
                   const int32_t* items, int64_t n_items, const uint32_t* dense_skip, const int32_t* inc, float* partials, const int32_t* multi,
                   int64_t n_multi, float margin, int32_t optimizer, float lr, int64_t step, const float* dev_hyper,
@@ -601,9 +604,22 @@ int kge_pull_step(const kge_model_desc* m, float* const tables_out[2], const flo
     if (optimizer != KGE_OPT_SGD && !grad_only && (!state1 || !state1[0] || !state1[1])) { set_error("kge_pull_step: optimizer state missing"); return -1; }
     if (optimizer == KGE_OPT_ADAM && (!state2 || !state2[0] || !state2[1])) { set_error("kge_pull_step: adam needs two state buffers"); return -1; }
     if (next_pairs && check_next_sampler("kge_pull_step", m, lists, next_inv, next_n, slots, n_slots, next_lists)) return -1;
-    return launch_pull_step(m, tables_out, hat_in, hat_out, norm_in, norm_out, state1, state2, pairs, lists, items, n_items, dense_skip, inc, partials, multi,
+    return launch_pull_step(m, tables_out, hat_in, hat_out, norm_in, norm_out, inv_norm_in, inv_norm_out, state1, state2, pairs, lists, items, n_items,
+                            dense_skip, inc, partials, multi,
                             n_multi, margin, optimizer, lr, step, dev_hyper, reset_lists, next_pairs, next_inv, next_n, bern_prob, slots,
                             n_slots, seed, next_offset, next_lists, loss, direction, (hipStream_t)stream);
+}
+int kge_pull_step(const kge_model_desc* m, float* const tables_out[2], const float* const hat_in[2], float* const hat_out[2],
+                  const float* norm_in, float* norm_out,
+                  float* const state1[2], float* const state2[2], const int32_t* pairs, const kge_pull_lists* lists,
+                  const int32_t* items, int64_t n_items, const uint32_t* dense_skip, const int32_t* inc, float* partials, const int32_t* multi,
+                  int64_t n_multi, float margin, int32_t optimizer, float lr, int64_t step, const float* dev_hyper,
+                  int32_t reset_lists, const int32_t* next_pairs, const int32_t* next_inv, int64_t next_n, const float* bern_prob,
+                  const uint64_t* slots, int64_t n_slots, uint64_t seed, uint64_t next_offset, const kge_pull_lists* next_lists,
+                  float* loss, const kge_pull_direction* direction, void* stream) {
+    return kge_pull_step_inv(m, tables_out, hat_in, hat_out, norm_in, norm_out, nullptr, nullptr, state1, state2, pairs, lists, items, n_items,
+                             dense_skip, inc, partials, multi, n_multi, margin, optimizer, lr, step, dev_hyper, reset_lists, next_pairs, next_inv,
+                             next_n, bern_prob, slots, n_slots, seed, next_offset, next_lists, loss, direction, stream);
 }
 
 int kge_pull_direction_bytes(int32_t dim, int32_t l1, int64_t n_pairs, size_t* codes_bytes, size_t* recs_bytes) {
@@ -631,7 +647,7 @@ int kge_pull_run(const kge_pull_plan* p, int64_t first_batch, int64_t n_steps, i
         kge_pull_direction dir = p->direction;
         dir.n_pairs = b->n_pairs;
         dir.lists_without_descriptors = 1;
-        return kge_pull_step(&p->model[src], tables_out, hat_in, hat_out, p->norm[src], p->norm[1 - src], p->state1, p->state2,
+        return kge_pull_step_inv(&p->model[src], tables_out, hat_in, hat_out, p->norm[src], p->norm[1 - src], p->inv_norm[src], p->inv_norm[1 - src], p->state1, p->state2,
                              b->pairs, &p->lists[cl], b->items, b->n_items, b->dense_skip, b->inc, p->partials, b->multi, b->n_multi, p->margin,
                              p->optimizer, p->lr, first_opt_step + k, nullptr, 1, nb ? nb->pairs : nullptr, nb ? nb->inv : nullptr,
                              nb ? nb->n_pairs : 0, p->bern_prob, p->slots, p->n_slots, p->seed, next_offset,

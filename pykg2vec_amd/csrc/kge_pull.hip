@@ -42,6 +42,8 @@ struct PullArgs {
                                // lanes beyond the row skip their load; 6.5 instead of 8.3 MB of normalised rows for the L2s to hold at C1)
     const float* norm_in;      // [E + R] L2 norms of the rows of tab_in (entities first)
     float* norm_out;           // norms of the rows of tab_out
+    const float* inv_norm_in;  // [E + R] 1 / max(norm_in, eps), stored next to the norm by whoever finished the row.  Hat-less two-phase
+    float* inv_norm_out;       // form only: read by k_pull_eval_nohat, written by its owners; no other form touches either (may be NULL)
     float* s1[2];              // optimiser state, same row layout as the tables (NULL where the optimiser has none)
     float* s2[2];
     const int4* pairs;         // this batch: (h, r, t, -)
@@ -65,8 +67,9 @@ struct PullArgs {
                                // low byte) and of the negative residual (high byte) -- one 16-bit load per visit
     int64_t n_pairs;
     unsigned wt;               // kWt* bits: the output streams stored write-through (store16_wt) instead of left dirty in the XCD's L2
-    unsigned hatless;          // two-phase form only (switch PULL_HATLESS): k_pull_eval_nohat scales table rows by 1 / norm_in itself, the
-                               // owners (k_pull_step_nohat, k_pull_finish<..., true>) write no hat rows; hat_in / hat_out are not touched
+    unsigned hatless;          // two-phase form only (switch PULL_HATLESS): k_pull_eval_nohat scales table rows by inv_norm_in itself, the
+                               // owners (k_pull_step_nohat, k_pull_finish<..., true>) write inv_norm_out and no hat rows; hat_in / hat_out
+                               // are not touched
 };
 
 #define KGE_F4_EACH(expr_x, expr_y, expr_z, expr_w) expr_x; expr_y; expr_z; expr_w;
@@ -79,7 +82,7 @@ __device__ __forceinline__ int mad_i24(int a, int b, int c) {
 }
 
 // gradient wrt the NORMALISED own row, summed over incidences -> normalisation backward -> optimiser -> new row, its
-// normalised copy (HATLESS: not the copy -- its only reader would be the evaluation, which then derives it from row and norm) and its norm
+// normalised copy (HATLESS: not the copy, only its scale 1 / max(norm, eps) -- the evaluation derives the copy from row and scale) and its norm
 template <int OPT, int G, int NV, bool PRE = false, bool HATLESS = false>
 __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const float4 (&X)[NV], float nX, const float4 (&gs)[NV],
                                                 int gl, const float4* pre1 = nullptr, const float4* pre2 = nullptr) {
@@ -143,7 +146,7 @@ __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const 
     // (lanes beyond the row hold zeros: X = 0, gs = 0, state loaded as 0 -> every optimiser leaves p = 0, n2 unchanged)
     n2 = gsum<G>(n2);
     const float nn = sqrtf(n2);
-    const float inn = 1.0f / fmaxf(nn, kEpsNormalize);   // (HATLESS: unused)
+    const float inn = 1.0f / fmaxf(nn, kEpsNormalize);   // (HATLESS: stored instead of the row it would scale)
     // Per stream: a plain store stays dirty in this XCD's L2 and is written back at the launch boundary, in front of k_pull_eval; a
     // write-through store leaves while the other owners still work (profiles/r14_experiments.md).  The flavours are
     // kernel-uniform.  All four on (what ships) and all four off are straight-line blocks; a mixed choice (A/B runs) pays a scalar
@@ -154,10 +157,15 @@ __device__ __forceinline__ void pull_finish_row(const PullArgs& a, int g, const 
         store_row4<G, NV>(t_out + off, P, nvec, gl, wt_tab);
         if constexpr (OPT != KGE_OPT_SGD) store_row4<G, NV>(st1 + off, M1, nvec, gl, wt_s1);
         if constexpr (OPT == KGE_OPT_ADAM) store_row4<G, NV>(st2 + off, M2, nvec, gl, wt_s2);
-        if constexpr (!HATLESS) {   // (HATLESS: no scaled copy, no fourth stream)
+        if constexpr (!HATLESS) {
 #pragma unroll
             for (int v = 0; v < NV; ++v) { P[v].x *= inn; P[v].y *= inn; P[v].z *= inn; P[v].w *= inn; }
             store_row4<G, NV>(reinterpret_cast<float*>(hrow), P, hvec, gl, wt_hat);
+        } else if (gl == 0) {
+            // (HATLESS: no scaled copy, no fourth stream -- one float per row, a plain store like the norm's below: a 4-byte write-through
+            //  store is a fabric write of its own, 16 296 of them added 0.42 MB of WRITE_SIZE and 0.2 us to the owner launch;
+            //  profiles/r31_experiments.md section 5)
+            a.inv_norm_out[g] = inn;
         }
     };
     constexpr unsigned kStreams = HATLESS ? kWtFinish & ~kWtHat : kWtFinish;
@@ -193,12 +201,13 @@ constexpr bool kHatCompactDefault = true;   // hat rows: padded to 4 * G * NV fl
 //  apart like compact hat rows, and scaled in place by 1 / max(norm, eps) of their row before the residuals: the very expression, on the
 //  very operands, that pull_finish_row / k_row_norms store as a hat row, so the scaled row is that hat row bit for bit (-ffp-contract=off:
 //  the multiply is not fused into the residual's add) and the owners need not write the hat tables at all.  The 4 * PP inverse norms of a
-//  lane group live in ONE register: lane k < 4 * PP loads the norm of the group's k-th row (h, E + r, t, c of pair 0, then of pair 1) and
-//  takes the reciprocal; a row is scaled by the value broadcast from its lane.  Eight scalars per lane instead -- 68-70 VGPRs -- would
-//  lose the 8-waves-per-SIMD residency round: profiles/r14_experiments.md section 6, profiles/r30_experiments.md)
-#ifndef KGE_HATLESS_READLANE
-#define KGE_HATLESS_READLANE 0   /* 1 (G = 32 only): two v_readlane + a select per row instead of one ds_bpermute; registers of both forms in r30 */
-#endif
+//  lane group live in ONE register: lane k < 4 * PP loads the STORED inverse norm of the group's k-th row (h, E + r, t, c of pair 0, then
+//  of pair 1) -- inv_norm_in, written next to the norm by the row's owner or by k_row_norms: that very expression, evaluated once per row
+//  instead of once per gathered row (16 296 against 131 072 divisions per step at C1) -- and a row is scaled by the value broadcast from
+//  its lane with one ds_bpermute.  Fetching the eight scales through the scalar cache into SGPRs, or reading the register with
+//  v_readlane, both measured SLOWER than the permute (16 v_readlane + moves per wave against 8 LDS-pipe permutes in a kernel bound by
+//  VALU issue) and were removed: profiles/r31_experiments.md.  Eight scalars per lane instead -- 68-70 VGPRs -- would lose the
+//  8-waves-per-SIMD residency round: profiles/r14_experiments.md section 6, profiles/r30_experiments.md)
 template <bool L1, int G, int NV, bool WT, bool HATLESS = false>
 __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restrict__ loss) {
     constexpr int GPB = kBlock / G, PP = kEvalPP;
@@ -232,7 +241,7 @@ __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restr
         ot[q] = (unsigned)p[q].z * kRowBytes + lane_off; oc[q] = (unsigned)(w[q] & 0xFFFFFF) * kRowBytes + lane_off;
         th[q] = a.theta ? a.theta[p[q].y] : 1.0f;
     }
-    float inv = 0.f;   // HATLESS: lane 4 q + role holds 1 / max(norm, eps) of that row of pair q
+    float inv = 0.f;   // HATLESS: lane 4 q + role holds the stored 1 / max(norm, eps) of that row of pair q
     if constexpr (HATLESS) {
         int row = 0;
 #pragma unroll
@@ -240,7 +249,7 @@ __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restr
             const int role = gl - 4 * q;
             row = role == 0 ? p[q].x : (role == 1 ? a.E + p[q].y : (role == 2 ? p[q].z : (role == 3 ? (w[q] & 0xFFFFFF) : row)));
         }
-        if (gl < 4 * PP) inv = 1.0f / fmaxf(a.norm_in[row], kEpsNormalize);   // (ids of a clamped dead pair are those of the last pair: in range)
+        if (gl < 4 * PP) inv = a.inv_norm_in[row];   // (ids of a clamped dead pair are those of the last pair: in range)
     }
 #pragma unroll
     for (int v = 0; v < NV; ++v) {   // ONE predicated region per chunk for all PP x 4 row gathers (padded rows: every lane is inside)
@@ -262,12 +271,7 @@ __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restr
         const bool tail = ((w[q] >> 24) & 1) != 0;
         if constexpr (HATLESS) {   // rows -> normalised rows, in place
             auto scale = [&](float4 (&x)[NV], int k) {
-                float s;
-                if constexpr (KGE_HATLESS_READLANE && G == 32) {   // (two groups per wave: one SGPR per half-wave)
-                    const float s_lo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), k));
-                    const float s_hi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), 32 + k));
-                    s = (threadIdx.x & 32) ? s_hi : s_lo;
-                } else s = __shfl(inv, k, G);
+                const float s = __shfl(inv, k, G);
 #pragma unroll
                 for (int v = 0; v < NV; ++v) { x[v].x *= s; x[v].y *= s; x[v].z *= s; x[v].w *= s; }
             };
@@ -301,12 +305,15 @@ __device__ __forceinline__ void pull_eval_body(const PullArgs& a, float* __restr
                 unsigned short* cp = reinterpret_cast<unsigned short*>(a.codes) + i * (int64_t)(G * NV);
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
-                    // the sign k_pull_step uses: clamp(x * 2^100, -1, 1); code 0 = zero, 1 = positive, 3 = negative: the two bits ARE the
-                    // sign as a two's-complement number (the owner decodes with one v_bfe_i32 + one v_cvt_f32_i32 per element)
+                    // the sign k_pull_step uses, clamp(x * 2^100, -1, 1), as a code: 0 = zero, 1 = positive, 3 = negative: the two bits ARE
+                    // the sign as a two's-complement number (the owner decodes with one v_bfe_i32 + one v_cvt_f32_i32 per element).  Taken
+                    // from the ordering of x itself against zero: multiplying by 2^100 keeps the sign of every finite non-zero float,
+                    // subnormals included (the product of a subnormal is at least 2^-49), and maps +-0 to +-0, so clamp(...) > 0 <=> x > 0
+                    // and clamp(...) < 0 <=> x < 0 -- the multiply and the v_med3 decided nothing (two VALU instructions less per sign:
+                    // 352 -> 320 in k_pull_eval<true, 32, 1>).  NaN: both compares are false, code 0, as before
                     unsigned bp = 0, bn = 0;
 #define KGE_CODE(c, sh)                                                                                       \
-                    { const float s1 = __builtin_amdgcn_fmed3f(up[v].c * 0x1p100f, -1.f, 1.f);                 \
-                      const float s2 = __builtin_amdgcn_fmed3f(un[v].c * 0x1p100f, -1.f, 1.f);                 \
+                    { const float s1 = up[v].c, s2 = un[v].c;                                                  \
                       bp |= (s1 > 0.f ? 1u : (s1 < 0.f ? 3u : 0u)) << sh;                                      \
                       bn |= (s2 > 0.f ? 1u : (s2 < 0.f ? 3u : 0u)) << sh; }
                     KGE_CODE(x, 0) KGE_CODE(y, 2) KGE_CODE(z, 4) KGE_CODE(w, 6)
@@ -714,7 +721,7 @@ __global__ __launch_bounds__(kBlock) void k_pull_finish(PullArgs a) {
 // L2 norms and normalised copies of the rows of a table, in the lane layout / operation order pull_finish_row uses
 template <int G, int NV>
 __global__ __launch_bounds__(kBlock) void k_row_norms(const float* __restrict__ tab, int64_t rows, int d, float* __restrict__ out,
-                                                      float* __restrict__ hat, unsigned hat_row_bytes) {
+                                                      float* __restrict__ inv_out, float* __restrict__ hat, unsigned hat_row_bytes) {
     constexpr int GPB = kBlock / G;
     const int gl = threadIdx.x % G;
     const int64_t r = (int64_t)blockIdx.x * GPB + threadIdx.x / G;
@@ -726,9 +733,12 @@ __global__ __launch_bounds__(kBlock) void k_row_norms(const float* __restrict__ 
     for (int v = 0; v < NV; ++v) { n2 = fmaf(X[v].x, X[v].x, n2); n2 = fmaf(X[v].y, X[v].y, n2); n2 = fmaf(X[v].z, X[v].z, n2); n2 = fmaf(X[v].w, X[v].w, n2); }
     n2 = gsum<G>(n2);
     const float nn = sqrtf(n2);
-    if (gl == 0) out[r] = nn;
+    const float inn = 1.0f / fmaxf(nn, kEpsNormalize);
+    if (gl == 0) {
+        out[r] = nn;
+        if (inv_out) inv_out[r] = inn;   // (the hat-less evaluation's scale: what pull_finish_row<..., HATLESS> stores)
+    }
     if (hat) {   // rows of hat_row_bytes: padded to 4 * G * NV floats, or compact (d floats)
-        const float inn = 1.0f / fmaxf(nn, kEpsNormalize);
         float4* const hrow = reinterpret_cast<float4*>(reinterpret_cast<char*>(hat) + r * (int64_t)hat_row_bytes);
         const int hvec = (int)(hat_row_bytes >> 4);
 #pragma unroll
@@ -866,7 +876,8 @@ int pull_hat_stride(int dim) { const PullGeo g = pull_geo(dim); return g.G ? (in
 int pull_groups_per_block(int dim) { const PullGeo g = pull_geo(dim); return g.G ? kBlock / g.G : 0; }
 
 int launch_pull_step(const kge_model_desc* m, float* const tables_out[2], const float* const hat_in[2], float* const hat_out[2],
-                     const float* norm_in, float* norm_out, float* const state1[2], float* const state2[2], const int32_t* pairs,
+                     const float* norm_in, float* norm_out, const float* inv_norm_in, float* inv_norm_out, float* const state1[2],
+                     float* const state2[2], const int32_t* pairs,
                      const kge_pull_lists* lists, const int32_t* items, int64_t n_items, const uint32_t* dense_skip, const int32_t* inc, float* partials,
                      const int32_t* multi, int64_t n_multi, float margin, int optimizer, float lr, int64_t step,
                      const float* dev_hyper, int reset_lists, const int32_t* next_pairs, const int32_t* next_inv, int64_t next_n, const float* bern,
@@ -895,6 +906,7 @@ int launch_pull_step(const kge_model_desc* m, float* const tables_out[2], const 
     }
     a.hat_row_bytes = hat_row_bytes(geo, m->dim);
     a.norm_in = norm_in; a.norm_out = norm_out;
+    a.inv_norm_in = inv_norm_in; a.inv_norm_out = inv_norm_out;
     a.pairs = (const int4*)pairs; a.lists = to_lists(lists);
     a.items = (const int4*)items; a.inc = inc; a.partials = partials; a.multi = (const int4*)multi;
     a.n_items = n_items; a.n_multi = n_multi; a.sample_blocks = 0;
@@ -914,6 +926,10 @@ int launch_pull_step(const kge_model_desc* m, float* const tables_out[2], const 
     a.n_pairs = two_phase ? dir->n_pairs : 0;
     a.wt = write_through_mask();
     a.hatless = two_phase && optimizer != KGE_OPT_GRADIENT && pull_hatless() ? 1u : 0u;
+    if (a.hatless && (!inv_norm_in || !inv_norm_out || inv_norm_in == inv_norm_out)) {
+        set_error("kge_pull_step: the hat-less two-phase step reads inv_norm_in and writes inv_norm_out (two buffers of E + R floats)");
+        return -1;
+    }
     PullSampleArgs sa = make_sample_args(next_pairs, next_inv, next_pairs && next_lists ? next_n : 0, m->tot_entity, bern, slots,
                                          n_slots, seed, next_offset, nullptr, next_lists);
     sa.no_desc = two_phase && dir->lists_without_descriptors ? 1 : 0;
@@ -928,14 +944,14 @@ int launch_pull_step(const kge_model_desc* m, float* const tables_out[2], const 
     return -1;
 }
 
-int launch_row_norms(const float* table, int64_t rows, int dim, float* out, float* hat, hipStream_t s) {
+int launch_row_norms(const float* table, int64_t rows, int dim, float* out, float* inv_out, float* hat, hipStream_t s) {
     const PullGeo g = pull_geo(dim);
     if (!g.G) { set_error("kge_row_norms: row length %d must be a multiple of 4 and at most 1024", dim); return -1; }
     if (rows == 0) return 0;
 #define KGE_RN(G_, NV_)                                                                                               \
     if (g.G == G_ && g.NV == NV_) {                                                                                    \
         hipLaunchKernelGGL((k_row_norms<G_, NV_>), dim3((unsigned)((rows + kBlock / G_ - 1) / (kBlock / G_))), dim3(kBlock), 0, s, \
-                           table, rows, dim, out, hat, hat_row_bytes(g, dim));                                         \
+                           table, rows, dim, out, inv_out, hat, hat_row_bytes(g, dim));                                         \
         return check_launch("k_row_norms");                                                                            \
     }
     KGE_RN(16, 1) KGE_RN(16, 2) KGE_RN(32, 1) KGE_RN(32, 2) KGE_RN(32, 4) KGE_RN(32, 8)

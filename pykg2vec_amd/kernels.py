@@ -1384,12 +1384,13 @@ def _ptr_pair(tensors):
     return arr
 
 
-def row_norms(table, out, hat=None):
-    """out[r] = ||table[r]||_2 and hat[r] = table[r] / max(norm, 1e-12), in the lane layout / operation order the pull
-    step uses for the rows it writes."""
-    L.check(L.load().kge_row_norms(_dev(table, torch.float32, "table"), table.shape[0], table.shape[1],
-                                   _dev(out, torch.float32, "norms"),
-                                   _dev(hat, torch.float32, "normalised") if hat is not None else None, _stream()),
+def row_norms(table, out, hat=None, inv=None):
+    """out[r] = ||table[r]||_2, inv[r] = 1 / max(norm, 1e-12) and hat[r] = table[r] * inv[r], in the lane layout / operation order the
+    pull step uses for the rows it writes."""
+    L.check(L.load().kge_row_norms_inv(_dev(table, torch.float32, "table"), table.shape[0], table.shape[1],
+                                       _dev(out, torch.float32, "norms"),
+                                       _dev(inv, torch.float32, "inverse norms") if inv is not None else None,
+                                       _dev(hat, torch.float32, "normalised") if hat is not None else None, _stream()),
             "kge_row_norms")
 
 
@@ -1492,17 +1493,22 @@ def pull_step(desc_in, tables_out, hat_in, hat_out, norm_in, norm_out, state1, s
               dense_skip=None, prepare_only=False, direction=None):
     """One whole training step (scoring, hinge, backward, dense optimiser) without atomics: see csrc/kge_pull.hip.
     desc_in: descriptor over the tables READ; tables_out: [ent, rel] of the other half of the double buffer; hat_in /
-    hat_out: the row-normalised copies of both halves.
+    hat_out: the row-normalised copies of both halves.  The hat-less two-phase step (pull_hatless()) also needs the inverse norms of both
+    halves: they are taken from `norm_in.inv` / `norm_out.inv`, the companions state.PullState hangs on its norm tensors; without them
+    the library refuses that step.
     sample_next = (next_pairs, next_inv, bern_prob, slots, seed, next_offset, next_lists): the sampler of the next batch rides
     in this launch and fills `next_lists` (a cleared second PullListSet)."""
     to, s1, s2, hi, ho = _ptr_pair(tables_out), _ptr_pair(state1), _ptr_pair(state2), _ptr_pair(hat_in), _ptr_pair(hat_out)
     # run_finish=False (timing only): the owners still write their partial sums, the finishing launch is skipped
     n_multi = multi.shape[0] if (multi is not None and run_finish) else 0
     nx = _next_sampler_args(sample_next)
+    inv_in, inv_out = getattr(norm_in, "inv", None), getattr(norm_out, "inv", None)
     args = (
         ctypes.byref(desc_in), ctypes.addressof(to), ctypes.addressof(hi), ctypes.addressof(ho) if hat_out is not None else None,
         _dev(norm_in, torch.float32, "norm_in"),
         _dev(norm_out, torch.float32, "norm_out") if norm_out is not None else None,
+        _dev(inv_in, torch.float32, "norm_in.inv") if inv_in is not None else None,
+        _dev(inv_out, torch.float32, "norm_out.inv") if inv_out is not None else None,
         ctypes.addressof(s1) if state1 is not None else None,
         ctypes.addressof(s2) if state2 is not None else None, _i32(pairs, "pairs"), ctypes.byref(lists.c),
         _i32(items, "items"), items.shape[0], _i32(dense_skip, "dense_skip") if dense_skip is not None else None,
@@ -1510,11 +1516,11 @@ def pull_step(desc_in, tables_out, hat_in, hat_out, norm_in, norm_out, state1, s
         _i32(multi, "multi") if n_multi else None, n_multi, float(margin), OPTIMIZER_IDS[optimizer], float(lr), int(step),
         _dev(dev_hyper, torch.float32, "dev_hyper") if dev_hyper is not None else None, 1 if reset_lists else 0,
         *nx, _dev(loss_buf, torch.float32, "loss"), ctypes.byref(direction.c) if direction is not None else None)
-    keep = (desc_in, to, hi, ho, s1, s2, tables_out, hat_in, hat_out, norm_in, norm_out, state1, state2, pairs, lists, items, inc,
+    keep = (desc_in, to, hi, ho, s1, s2, tables_out, hat_in, hat_out, norm_in, norm_out, inv_in, inv_out, state1, state2, pairs, lists, items, inc,
             partials, multi, loss_buf, dense_skip, sample_next, direction)
     if prepare_only:   # (a data-parallel step runs this launch between two collectives: host time per step matters there)
-        return _prepared(L.load().kge_pull_step, "kge_pull_step", args, len(args) - 4, keep)
-    L.check(L.load().kge_pull_step(*args, _stream()), "kge_pull_step")
+        return _prepared(L.load().kge_pull_step_inv, "kge_pull_step", args, len(args) - 4, keep)
+    L.check(L.load().kge_pull_step_inv(*args, _stream()), "kge_pull_step")
 
 
 def pull_index_build(triples, perm, batch_stride, slice_lo, n_pairs, n_batches, tot_entity, tot_relation, segment,
@@ -1610,6 +1616,7 @@ class PullPlan:
         for half in (0, 1):
             c.model[half] = make_desc(model_name, tables[half], None, tot_entity=tot_entity, tot_relation=tot_relation, **desc_kwargs)
             c.norm[half] = norms[half].data_ptr()
+            c.inv_norm[half] = norms[half].inv.data_ptr()   # (state.PullState: the inverse norms ride on the norm tensors)
             for t in (0, 1):
                 c.hat[half][t] = hats[half][t].data_ptr()
         for t in (0, 1):

@@ -223,6 +223,11 @@ class PullState(OwnerRunState):
         E, R, d = shapes[0][0], shapes[1][0], shapes[0][1]
         self.E, self.R = E, R
         self.norms = [torch.empty(E + R, dtype=torch.float32, device=dev) for _ in range(2)]
+        # 1 / max(norm, eps) of the same rows: what the hat-less evaluation scales by.  Each rides on its norm tensor as `.inv`, so whoever
+        # is handed norms[half] (kernels.pull_step, kernels.PullPlan) has both
+        self.inv_norms = [torch.empty(E + R, dtype=torch.float32, device=dev) for _ in range(2)]
+        for n, i in zip(self.norms, self.inv_norms):
+            n.inv = i
         self.batch_size = batch_size
         super().__init__([K.PullListSet(batch_size, E, dev) for _ in range(2)])
         self.calls = {}   # prepared kge_pull_step calls of the data-parallel gradient step
@@ -234,6 +239,9 @@ class PullState(OwnerRunState):
         # hat-less two-phase steps (K.pull_hatless()) neither read nor write the hat tables: after them hats[cur] no longer describes
         # tables[cur], and whoever reads hats asks fresh_hats() first
         self.hats_stale = False
+        # ... and only they write the inverse norms: after any other optimiser step inv_norms[cur] no longer describes tables[cur], and a
+        # hat-less run asks fresh_inv_norms() first
+        self.inv_stale = False
 
     def run_steps(self, gen, index, n_steps, flat, run):
         """As OwnerRunState.run_steps; `run` also takes, after n_steps, the table half the first step reads (the halves alternate)."""
@@ -246,10 +254,12 @@ class PullState(OwnerRunState):
         if n_steps <= 0:
             return
         hatless = self.plan_two_phase and K.pull_hatless()   # (once per run: the native loop asks nothing of Python)
-        if not hatless:
+        if hatless:
+            self.fresh_inv_norms()
+        else:
             self.fresh_hats()
         self.run_steps(gen, index, n_steps, flat, self.plan.run)
-        self.hats_stale = hatless
+        self.hats_stale, self.inv_stale = hatless, not hatless
 
     def fresh_hats(self):
         """Before a launch that reads hats[cur]: rebuild them from the current tables if hat-less steps left them behind."""
@@ -258,6 +268,13 @@ class PullState(OwnerRunState):
                 K.row_norms(self.tables[self.cur][t], self.norms[self.cur][lo:hi], self.hats[self.cur][t])
             self.hats_stale = False
 
+    def fresh_inv_norms(self):
+        """Before a hat-less launch, which reads inv_norms[cur]: rebuild them if hat-carrying steps left them behind."""
+        if self.inv_stale:
+            for t, (lo, hi) in enumerate(((0, self.E), (self.E, self.E + self.R))):
+                K.row_norms(self.tables[self.cur][t], self.norms[self.cur][lo:hi], inv=self.inv_norms[self.cur][lo:hi])
+            self.inv_stale = False
+
     def sync_in(self):
         """(Re)derive the row norms from the tables the model currently holds (they may have been set from outside)."""
         if self.grad_only:
@@ -265,9 +282,9 @@ class PullState(OwnerRunState):
             self.refresh_norms()
             return
         self.sync_out()
-        K.row_norms(self.tables[0][0], self.norms[0][:self.E], self.hats[0][0])
-        K.row_norms(self.tables[0][1], self.norms[0][self.E:], self.hats[0][1])
-        self.hats_stale = False
+        K.row_norms(self.tables[0][0], self.norms[0][:self.E], self.hats[0][0], self.inv_norms[0][:self.E])
+        K.row_norms(self.tables[0][1], self.norms[0][self.E:], self.hats[0][1], self.inv_norms[0][self.E:])
+        self.hats_stale = self.inv_stale = False
 
     def refresh_norms(self):
         """Row norms / normalised copies of the current parameter tables (after the all-gather of a data-parallel step)."""
@@ -284,6 +301,8 @@ class PullState(OwnerRunState):
         if self.cur == 1 and not self.grad_only:
             self.flat.param.copy_(self.alt)
             self.norms[0].copy_(self.norms[1])
+            if not self.inv_stale:
+                self.inv_norms[0].copy_(self.inv_norms[1])
             if not self.hats_stale:   # (stale hats stay stale in either half: nothing to carry over)
                 for t in (0, 1):
                     self.hats[0][t].copy_(self.hats[1][t])

@@ -471,6 +471,7 @@ class Trainer:
                     ps.partials, multi, self.config.margin, self.config.optimizer, self.config.learning_rate,
                     self.flat.step, self.loss_buf, dense_skip=skip, direction=ps.direction)
         ps.hats_stale = ps.direction is not None and K.pull_hatless()
+        ps.inv_stale = not ps.hats_stale
         ps.cur = 1
         ps.sync_out()
 
