@@ -206,6 +206,61 @@ int kge_tsne_run(float* Y, float* Y_tmp, float* update, float* gains, int64_t n,
                  const float* val, int64_t nnz, int64_t it0, int64_t it1, float exaggeration, float momentum, float learning_rate,
                  int32_t record_every, double* trace, int64_t n_records, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- k-means clustering of embedding rows (kge_kmeans.hip): Lloyd's iteration and the k-means++ seeding as exact functions of
+ * their inputs.  No [n, k] distance block is written, no float atomic is used, every sum runs in a fixed order: results are
+ * bit-identical from run to run.  Every buffer is the caller's and lives on the device.  rows float32 [n, row_stride], centroids
+ * float32 [k, centroid_stride]; the first dim elements of a row count.
+ *
+ * kge_kmeans_assign: out_label[i] is the centroid first in the total order of kge_topk_rows over the float32 keys
+ * |c|^2 - 2 x_i.c (lower key first, lower centroid id among equal keys, -0.0 equals +0.0, a NaN key after every number); |c|^2 is
+ * summed per centroid in a fixed order.  out_dist2[i] = sum_j (x_ij - c_j)^2 to the winner, recomputed directly in float32 in a
+ * fixed order: a row on its centroid is at exactly 0 and no returned value carries the expansion's cancellation.  A row with a NaN
+ * entry gets label -1 and a NaN out_dist2: it belongs to no cluster.
+ *
+ * kge_kmeans_update: the members of cluster c (label == c) in ascending row id are cut into chunks of KGE_KMEANS_CHUNK; a chunk is
+ * summed per column in float32 in member order; the chunk sums are added in chunk order in float64, divided by the count in float64
+ * (under unit_centroids: then by the float64 norm of that mean -- spherical k-means --) and rounded to float32 once.  centroids in:
+ * the previous ones, out: the new ones; out_count int32 [k].  An empty cluster keeps its previous centroid and gets out_count 0; so
+ * does, under unit_centroids, a cluster whose mean has norm zero: out_count 0 marks a centroid that was not updated.
+ *
+ * kge_kmeans_run: at most max_iter iterations of [assign, count the labels that changed, update] in one C loop without a host read.
+ * label int32 [n] in: the previous labels (-2 everywhere: none), out: those of the last assign, as are out_dist2 and out_inertia
+ * (float64 [1]: the sum of out_dist2 over the rows with a label, in a fixed order); centroids and out_count are those after the last
+ * update.  state int32 [4]: done, iterations that did work, labels changed in the last one, rows with a NaN (label -1); zeros start
+ * a run.  An iteration in which no label changed sets done; the launches of later iterations (and calls) return at once and write
+ * nothing.  There is no tolerance-based stop.  All of a run's state is in centroids, label and state: a run cut into several calls
+ * leaves the bits of one call.
+ *
+ * kge_kmeans_seed: k-means++ (Arthur and Vassilvitskii 2007) as a function of (rows, u), u float64 [k] in [0, 1): centre 0 is the first
+ * row without a NaN entry from row floor(u[0] n) on, cyclically (that row itself when every row holds a NaN); for j >= 1, d_i is the
+ * squared distance (computed as out_dist2 is) of row i to its nearest chosen centre, 0 for a row with a NaN; P the inclusive prefix sum
+ * of d in row order in float64, T its last element; centre j is the smallest i with P_i > u[j] T, or, when T is not positive, the
+ * lowest row id not chosen yet.  A row with a NaN (d = 0) is never chosen while T > 0.  The grouping of the prefix is
+ * part of the contract: with nb = ceil(n / 64) blocks of 64 rows and runs of L = ceil(nb / 1024) consecutive blocks,
+ * P_i = O_r + (B + s_i), where s_i is the sum of d over the rows of i's block up to i, added one by one; B the sum of the whole blocks
+ * of i's run in front of i's block, block sums added one by one; O_r the sum of the runs in front of i's run, run sums added one
+ * by one.  On float32 terms in float64 this differs from the one-by-one prefix below 2^-53 relative per addition; on data whose sums
+ * are exact (integers) not at all.  out_ids int32 [k], out_centroids float32 [k, dim] (contiguous): copies of the chosen rows.  Two
+ * launches per centre.
+ *
+ * workspace: kge_kmeans_workspace_bytes of the same n, dim and k, for every call (0 for refused arguments).  Refused before any GPU call,
+ * kge_last_error() naming the argument: n < 1, dim < 1, k outside 1..min(n, KGE_KMEANS_MAX_K), a stride below dim, max_iter < 0, a null
+ * pointer, a workspace that is too small. */
+#define KGE_KMEANS_MAX_K 4096
+#define KGE_KMEANS_CHUNK 128   /* members per float32 partial sum of the update: part of the contract, it fixes the summation order */
+size_t kge_kmeans_workspace_bytes(int64_t n, int64_t dim, int32_t k);
+int kge_kmeans_assign(const float* rows, int64_t n, int64_t dim, int64_t row_stride, const float* centroids, int32_t k,
+                      int64_t centroid_stride, void* workspace, size_t workspace_bytes, int32_t* out_label, float* out_dist2,
+                      void* stream);
+int kge_kmeans_update(const float* rows, int64_t n, int64_t dim, int64_t row_stride, const int32_t* label, int32_t k,
+                      int32_t unit_centroids, float* centroids, int64_t centroid_stride, int32_t* out_count, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int kge_kmeans_run(const float* rows, int64_t n, int64_t dim, int64_t row_stride, float* centroids, int32_t k, int64_t centroid_stride,
+                   int32_t unit_centroids, int32_t max_iter, int32_t* label, float* out_dist2, int32_t* out_count, double* out_inertia,
+                   int32_t* state, void* workspace, size_t workspace_bytes, void* stream);
+int kge_kmeans_seed(const float* rows, int64_t n, int64_t dim, int64_t row_stride, int32_t k, const double* u, void* workspace,
+                    size_t workspace_bytes, int32_t* out_ids, float* out_centroids, void* stream);
+
 /* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
  * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).
  * triples int64 [n, 3].  side 0 ranks tails (the candidates replace column 2), side 1 ranks heads (column 0); the true entity

@@ -126,6 +126,8 @@ TOPK_MAX = 1024   # KGE_TOPK_MAX: the most candidates kge_topk_rows returns per 
 KNN_MAX = 128     # KGE_KNN_MAX: the most neighbours kge_knn_rows returns per query
 KNN_METRICS = {"dot": 0, "cosine": 1, "l2": 2}   # KGE_KNN_DOT / _COSINE / _L2
 TSNE_TILE = 256   # KGE_TSNE_TILE: points per tile of the t-SNE repulsion sweep
+KMEANS_MAX_K = 4096   # KGE_KMEANS_MAX_K: the most clusters of kge_kmeans_*
+KMEANS_CHUNK = 128    # KGE_KMEANS_CHUNK: members per float32 partial sum of kge_kmeans_update
 CAND_CHUNK = 64   # KGE_CAND_CHUNK: list entries per work item of kge_rank_candidates
 REL_CHUNK = 64    # KGE_REL_CHUNK: relation ids per work item of kge_rank_relations
 TYPED_ATTEMPTS = 16           # KGE_TYPED_ATTEMPTS: typed draws of kge_corrupt_typed before it falls back
@@ -368,6 +370,17 @@ _SIGNATURES = {
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_kmeans_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "kge_kmeans_assign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kge_kmeans_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_void_p]),
+    "kge_kmeans_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                      ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 6
+                       + [ctypes.c_size_t, ctypes.c_void_p]),
+    "kge_kmeans_seed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_rank_candidates_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "kge_rank_candidates": (ctypes.c_int, [ctypes.POINTER(ModelDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,

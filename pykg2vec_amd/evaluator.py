@@ -476,6 +476,78 @@ class Evaluator:
             raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
         return self._project(X.contiguous(), **kw)
 
+    # --- k-means clustering of embedding rows (kge_kmeans_*): entity typing, relation groups, the colours of a projection
+    last_clustering = None
+
+    def _cluster(self, X, n_clusters, metric="l2", init="k-means++", n_init=1, max_iter=100, seed=0):
+        n, k = int(X.shape[0]), int(n_clusters)
+        if metric not in ("l2", "cosine"):
+            raise ValueError("metric = %r (\"l2\" or \"cosine\")" % (metric,))
+        if not 1 <= k <= min(n, K.KMEANS_MAX_K):
+            raise ValueError("n_clusters = %d outside 1..min(n = %d, KGE_KMEANS_MAX_K = %d)" % (k, n, K.KMEANS_MAX_K))
+        if int(max_iter) < 1 or int(n_init) < 1:   # (without an iteration there are no labels to return)
+            raise ValueError("max_iter = %d, n_init = %d (at least 1 each)" % (max_iter, n_init))
+        unit = metric == "cosine"
+
+        def normalised(M):   # rows of norm 1; zero rows stay zero
+            norm = M.norm(dim=1, keepdim=True)
+            return torch.where(norm > 0, M / torch.where(norm > 0, norm, torch.ones_like(norm)), M).contiguous()
+
+        given = isinstance(init, (torch.Tensor, np.ndarray))
+        with torch.no_grad():   # (X may be the parameter itself: no graph over the table)
+            X = normalised(X) if unit else X.detach()
+            if given:
+                start = torch.as_tensor(init).detach().to(device=X.device, dtype=torch.float32)
+                if tuple(start.shape) != (k, int(X.shape[1])):
+                    raise ValueError("init must be [%d, %d] (got %s)" % (k, X.shape[1], list(start.shape)))
+                start = normalised(start) if unit else start
+        if not given and init != "k-means++":
+            raise ValueError("init = %r (\"k-means++\" or a [k, D] tensor)" % (init,))
+        best = None
+        for run in range(1 if given else int(n_init)):
+            if given:
+                cent = start.clone().contiguous()
+            else:
+                gen = torch.Generator(device="cpu")
+                gen.manual_seed(int(seed) + run)
+                _, cent = self.K.kmeans_seed(X, k, torch.rand(k, generator=gen, dtype=torch.float64).to(X.device))
+            res = self.K.kmeans_run(X, cent, int(max_iter), unit_centroids=unit)
+            inertia = float(res.inertia.item())   # the one host read of a run, at its end
+            if best is None or inertia < best[0]:
+                best = (inertia, res)
+        inertia, res = best
+        state = res.state.tolist()
+        self.last_clustering = {"inertia": inertia, "iterations": state[1], "counts": res.count, "invalid_rows": state[3],
+                                "converged": bool(state[0])}
+        return res.label.to(torch.int64), res.centroids
+
+    def _cluster_rows(self, kind, n_clusters, ids, tables, kw):
+        table = self._knn_matrix(kind, tables)
+        if ids is not None:
+            table = table[self._ids_arg(ids, "ids").to(table.device)]
+        return self._cluster(table, n_clusters, **kw)
+
+    def cluster_entities(self, n_clusters, ids=None, tables=None, **kw):
+        """(labels int64 [n], centroids float32 [n_clusters, D]) on the device: k-means over the entities `ids` (None: every entity),
+        rows from Model.entity_matrix(tables).  metric="l2", or "cosine": spherical k-means -- the rows are normalised once (zero rows
+        stay zero) and so is every centroid.  init="k-means++" (draws from a CPU generator seeded with seed + run) or a [k, D] tensor;
+        n_init=1 runs, of which the one of lowest inertia is kept; max_iter=100 Lloyd iterations at most (at least 1), stopped when no label moves
+        (there is no tolerance); seed=0.  A row with a NaN gets label -1.  Results are the same bits on every run (kge_kmeans_run);
+        last_clustering holds inertia, iterations, counts, invalid_rows and converged."""
+        return self._cluster_rows("entity", n_clusters, ids, tables, kw)
+
+    def cluster_relations(self, n_clusters, ids=None, tables=None, **kw):
+        """cluster_entities over Model.relation_matrix(tables)."""
+        return self._cluster_rows("relation", n_clusters, ids, tables, kw)
+
+    def cluster_vectors(self, X, n_clusters, **kw):
+        """cluster_entities for rows that are no table rows: X float32 [n, D]."""
+        X = X.detach() if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X))
+        X = X.to(device=self.config.device, dtype=torch.float32)
+        if X.dim() != 2:
+            raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
+        return self._cluster(X.contiguous(), n_clusters, **kw)
+
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))
         if self.config.debug:

@@ -1148,6 +1148,102 @@ def tsne_run(csr, Y, n_iter, it0=0, exaggeration=1.0, momentum=0.8, learning_rat
     return Y, trace
 
 
+# --- k-means clustering of embedding rows (csrc/kge_kmeans.hip): fused MFMA assign, ordered update, the Lloyd loop, k-means++
+KMEANS_MAX_K = L.KMEANS_MAX_K
+KMEANS_CHUNK = L.KMEANS_CHUNK
+
+KMeansResult = collections.namedtuple("KMeansResult", "centroids label dist2 count inertia state")
+KMeansResult.__doc__ = """What kmeans_run leaves on the device: centroids float32 [k, dim] after the last update, count int32 [k]; label
+int32 [n] (-1: a row with a NaN), dist2 float32 [n] and inertia float64 [1] of the last assign; state int32 [4] = (done, iterations
+that did work, labels changed in the last one, rows with a NaN)."""
+
+
+def _kmeans_args(rows, centroids=None, k=None):
+    """(lib, n, dim, row_stride, k, centroid_stride, workspace) of a k-means call over float32 device rows."""
+    stride = _knn_rows_arg(rows, "rows")
+    n, dim = (int(x) for x in rows.shape)
+    cstride = dim
+    if centroids is not None:
+        cstride = _knn_rows_arg(centroids, "centroids")
+        if centroids.device != rows.device:
+            raise ValueError("rows and centroids live on different devices")
+        if int(centroids.shape[1]) != dim:
+            raise ValueError("centroids have %d columns, the rows %d" % (centroids.shape[1], dim))
+        k = int(centroids.shape[0])
+    k = int(k)
+    if not 1 <= k <= min(n, KMEANS_MAX_K):
+        raise ValueError("k = %d outside 1..min(n = %d, KGE_KMEANS_MAX_K = %d)" % (k, n, KMEANS_MAX_K))
+    lib = L.load()
+    nbytes = lib.kge_kmeans_workspace_bytes(n, dim, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=rows.device)
+    return lib, n, dim, stride, k, cstride, ws
+
+
+def kmeans_assign(rows, centroids):
+    """(label int32 [n], dist2 float32 [n]): every row's first centroid in the total order of the keys |c|^2 - 2 x.c (lower key, then
+    lower id; NaN last) and its directly recomputed squared distance to it; a row with a NaN entry gets -1 and NaN
+    (kge_kmeans_assign: the argmin runs inside the matrix-core sweep, no [n, k] block is written)."""
+    lib, n, dim, stride, k, cstride, ws = _kmeans_args(rows, centroids)
+    label = torch.empty(n, dtype=torch.int32, device=rows.device)
+    dist2 = torch.empty(n, dtype=torch.float32, device=rows.device)
+    L.check(lib.kge_kmeans_assign(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, ctypes.c_void_p(centroids.data_ptr()), k, cstride,
+                                  ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(label.data_ptr()),
+                                  ctypes.c_void_p(dist2.data_ptr()), _stream()), "kge_kmeans_assign")
+    return label, dist2
+
+
+def kmeans_update(rows, label, centroids, unit_centroids=False):
+    """(centroids, count int32 [k]): the mean of every cluster's rows (label int32 [n]; negative: in no cluster), summed in ascending row
+    id in chunks of KMEANS_CHUNK -- float32 inside a chunk, float64 across chunks, one rounding -- and, under unit_centroids, divided by
+    its float64 norm.  `centroids` is updated IN PLACE; a cluster that is empty (or whose mean has no direction) keeps its row and
+    gets count 0 (kge_kmeans_update)."""
+    lib, n, dim, stride, k, cstride, ws = _kmeans_args(rows, centroids)
+    if tuple(label.shape) != (n,):
+        raise ValueError("label must hold one id per row (%d, got %s)" % (n, list(label.shape)))
+    count = torch.empty(k, dtype=torch.int32, device=rows.device)
+    L.check(lib.kge_kmeans_update(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, _dev(label, torch.int32, "label"), k,
+                                  1 if unit_centroids else 0, ctypes.c_void_p(centroids.data_ptr()), cstride,
+                                  ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+            "kge_kmeans_update")
+    return centroids, count
+
+
+def kmeans_run(rows, centroids, max_iter, unit_centroids=False, resume=None):
+    """At most max_iter Lloyd iterations in one C loop (kge_kmeans_run): no Python per iteration, no host read; the iterations behind
+    the one in which no label moved return at once.  `centroids` float32 [k, dim] is updated IN PLACE.  resume: the KMeansResult of an
+    earlier call over the same rows and centroids, whose tensors are carried on in place -- a run cut into several calls leaves the
+    bits of one.  -> KMeansResult."""
+    lib, n, dim, stride, k, cstride, ws = _kmeans_args(rows, centroids)
+    dev = rows.device
+    if resume is None:
+        resume = KMeansResult(centroids, torch.full((n,), -2, dtype=torch.int32, device=dev),
+                              torch.full((n,), float("nan"), dtype=torch.float32, device=dev), torch.zeros(k, dtype=torch.int32, device=dev),
+                              torch.full((1,), float("nan"), dtype=torch.float64, device=dev), torch.zeros(4, dtype=torch.int32, device=dev))
+    elif tuple(resume.label.shape) != (n,) or tuple(resume.count.shape) != (k,):
+        raise ValueError("resume belongs to a run of another shape")
+    L.check(lib.kge_kmeans_run(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, ctypes.c_void_p(centroids.data_ptr()), k, cstride,
+                               1 if unit_centroids else 0, int(max_iter), _dev(resume.label, torch.int32, "label"),
+                               _dev(resume.dist2, torch.float32, "dist2"), _dev(resume.count, torch.int32, "count"),
+                               _dev(resume.inertia, torch.float64, "inertia"), _dev(resume.state, torch.int32, "state"),
+                               ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()), "kge_kmeans_run")
+    return resume._replace(centroids=centroids)
+
+
+def kmeans_seed(rows, k, u):
+    """(ids int32 [k], centroids float32 [k, dim]): the k-means++ centres of the rows as a function of u (float64 [k] in [0, 1), one
+    draw per centre): row floor(u[0] n), then the first row whose float64 prefix of squared distances to the nearest chosen centre
+    passes u[j] times their sum (kge_kmeans_seed: two launches per centre, nothing read on the host)."""
+    lib, n, dim, stride, k, _, ws = _kmeans_args(rows, None, k)
+    if tuple(u.shape) != (k,):
+        raise ValueError("u must hold one draw per centre (%d, got %s)" % (k, list(u.shape)))
+    ids = torch.empty(k, dtype=torch.int32, device=rows.device)
+    cent = torch.empty((k, dim), dtype=torch.float32, device=rows.device)
+    L.check(lib.kge_kmeans_seed(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, k, _dev(u, torch.float64, "u"),
+                                ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(ids.data_ptr()),
+                                ctypes.c_void_p(cent.data_ptr()), _stream()), "kge_kmeans_seed")
+    return ids, cent
+
+
 CAND_CHUNK = L.CAND_CHUNK
 
 
