@@ -100,7 +100,7 @@ const char* kge_last_error(void);
  * kge_eval_ranks / _grouped / kge_eval_sweep_scores (and _side), kge_rank_from_scores. */
 int kge_set_debug(int32_t check_ids);
 /* A/B switches of the dispatch rules: RESCAL_UNFUSED, RESCAL_ROWS, RESCAL_G, RESCAL_G2, TRANSR_ROWS, TRANSR_G,
- * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT, KNN_SPLIT, TSNE_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an
+ * EVAL_GEMM, HEAD_TILE, NTN_BIG, OPT_NT, PULL_G, ROTATE_SPLIT, KNN_SPLIT, TSNE_SPLIT, SIL_SPLIT.  value >= 0 forces it, -1 hands the decision back to the environment variable KGE_<name> (an
  * integer; "0" off, "1" on) or, if that is unset, to the built-in rule.  Same meaning on both sides of the boundary. */
 int kge_set_switch(const char* name, int32_t value);
 int kge_get_debug(void);
@@ -260,6 +260,45 @@ int kge_kmeans_run(const float* rows, int64_t n, int64_t dim, int64_t row_stride
                    int32_t* state, void* workspace, size_t workspace_bytes, void* stream);
 int kge_kmeans_seed(const float* rows, int64_t n, int64_t dim, int64_t row_stride, int32_t k, const double* u, void* workspace,
                     size_t workspace_bytes, int32_t* out_ids, float* out_centroids, void* stream);
+
+/* ---- silhouette scores of labelled embedding rows (kge_silhouette.hip; Rousseeuw 1987): how well does row i sit in its cluster?  An
+ * all-pairs quantity computed in one matrix-core sweep: no [n, n] distance block exists, no float atomic is used, every sum runs in a
+ * fixed order -- the same bits on every run.  Every buffer is the caller's and lives on the device.  rows float32 [n, row_stride], the
+ * first dim elements of a row count; label int32 [n] in -1..k-1, k in 2..KGE_KMEANS_MAX_K.  Label -1 is what kge_kmeans_* gives a row
+ * with a NaN entry: the row belongs to no cluster and enters no sum.  A row with a NaN entry under a label >= 0 (and a row whose label
+ * is outside -1..k-1) is treated the same way: its out_s, out_a and out_b are NaN, its out_neighbor is -1, it is not counted.
+ * Only NaN is looked for: keeping +-Inf out of the rows is the caller's part.  A row with an Inf entry stays a member of its cluster,
+ * its distances are Inf or NaN, and every sum they enter -- so the outputs of any row -- may be Inf, NaN or wrong (a NaN own-cluster sum
+ * reads as 0); nothing is read or written out of bounds.
+ *
+ * metric KGE_SIL_L2: d(i, j) = sqrt(max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j, 0)), the float32 expansion of the other sweeps, |x|^2 summed per
+ * row in a fixed order, the square root correctly rounded.  KGE_SIL_COSINE: d(i, j) = max(1 - x_i.x_j, 0) on rows the caller has
+ * normalised; a zero row stays zero and is at distance 1 from everything.  d(i, i) is excluded by index, never by value.
+ *
+ * With S_c(i) the sum of d(i, j) over the members j of cluster c, n_c their number and c_i the row's own cluster:
+ *   a = S_{c_i}(i) / (n_{c_i} - 1)   (0 when n_{c_i} = 1),
+ *   b = min over c != c_i with n_c > 0 of S_c(i) / n_c; out_neighbor[i] is that c, the lower id among equal means, -1 (and b NaN)
+ *       when there is no other non-empty cluster,
+ *   s = (b - a) / max(a, b), and s = 0 when n_{c_i} = 1, when max(a, b) = 0, or when there is no other non-empty cluster.
+ * The divisions, the minimum and s are in float64, each of out_s, out_a, out_b rounded to float32 once.  out_count int32 [k] = n_c.
+ * out_score float64 [1]: the mean of the float32 out_s over the counted rows (NaN if none is counted).
+ *
+ * The summation order: the members of a cluster in ascending row id are cut into tiles of 32; inside a tile, with p the member's
+ * place in it, lane half h = (p >> 2) & 1 adds its 16 distances in float32 in ascending p; the two half sums are added in float32;
+ * the tile sums are added in tile order in float64.  The score: thread t of 1024 adds out_s of the counted rows t, t + 1024, ... in
+ * float64; a pairwise tree (stride 512, 256, ..., 1) adds the threads; one division by the count.  The column range is cut into S slabs
+ * at cluster boundaries, S a function of n alone (the switch SIL_SPLIT forces it): a cluster lies in one slab, a row's partials are at
+ * most one own-cluster sum and a minimum under the total order (mean, id), so the result does not depend on S.
+ *
+ * workspace: kge_silhouette_workspace_bytes of the same n, dim and k (0 for refused arguments), asked for under the same switches as the call.
+ * Refused before any GPU call, kge_last_error() naming the argument: n < 2, dim < 1, k outside 2..KGE_KMEANS_MAX_K, a stride below
+ * dim, an unknown metric, a null pointer, a workspace that is too small.  Seven launches, whatever n and k are. */
+#define KGE_SIL_L2 0
+#define KGE_SIL_COSINE 1
+size_t kge_silhouette_workspace_bytes(int64_t n, int64_t dim, int32_t k);
+int kge_silhouette(const float* rows, int64_t n, int64_t dim, int64_t row_stride, const int32_t* label, int32_t k, int metric,
+                   void* workspace, size_t workspace_bytes, float* out_s, float* out_a, float* out_b, int32_t* out_neighbor,
+                   int32_t* out_count, double* out_score, void* stream);
 
 /* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
  * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).

@@ -479,6 +479,11 @@ class Evaluator:
     # --- k-means clustering of embedding rows (kge_kmeans_*): entity typing, relation groups, the colours of a projection
     last_clustering = None
 
+    @staticmethod
+    def _unit_rows(M):   # rows of norm 1; zero rows stay zero
+        norm = M.norm(dim=1, keepdim=True)
+        return torch.where(norm > 0, M / torch.where(norm > 0, norm, torch.ones_like(norm)), M).contiguous()
+
     def _cluster(self, X, n_clusters, metric="l2", init="k-means++", n_init=1, max_iter=100, seed=0):
         n, k = int(X.shape[0]), int(n_clusters)
         if metric not in ("l2", "cosine"):
@@ -489,9 +494,7 @@ class Evaluator:
             raise ValueError("max_iter = %d, n_init = %d (at least 1 each)" % (max_iter, n_init))
         unit = metric == "cosine"
 
-        def normalised(M):   # rows of norm 1; zero rows stay zero
-            norm = M.norm(dim=1, keepdim=True)
-            return torch.where(norm > 0, M / torch.where(norm > 0, norm, torch.ones_like(norm)), M).contiguous()
+        normalised = self._unit_rows
 
         given = isinstance(init, (torch.Tensor, np.ndarray))
         with torch.no_grad():   # (X may be the parameter itself: no graph over the table)
@@ -547,6 +550,80 @@ class Evaluator:
         if X.dim() != 2:
             raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
         return self._cluster(X.contiguous(), n_clusters, **kw)
+
+    # --- silhouette scores of a clustering (kge_silhouette): how many clusters, and which rows sit badly in theirs
+    last_silhouette = None
+
+    def _silhouette(self, X, labels, metric="l2"):
+        n = int(X.shape[0])
+        if metric not in ("l2", "cosine"):
+            raise ValueError("metric = %r (\"l2\" or \"cosine\")" % (metric,))
+        labels = labels.detach() if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+        if labels.dim() != 1 or int(labels.shape[0]) != n or labels.dtype.is_floating_point:
+            raise ValueError("labels must hold one integer per row (%d, got %s %s)" % (n, labels.dtype, list(labels.shape)))
+        if n < 2:
+            raise ValueError("a silhouette needs at least 2 rows (got %d)" % n)
+        lo, hi = torch.stack([labels.min(), labels.max()]).tolist()   # the one host read before the call
+        k = int(hi) + 1
+        if lo < -1 or not 2 <= k <= K.KMEANS_MAX_K:
+            raise ValueError("labels span %d..%d: outside -1..n_clusters - 1 with n_clusters in 2..KGE_KMEANS_MAX_K = %d"
+                             % (lo, hi, K.KMEANS_MAX_K))
+        with torch.no_grad():
+            X = self._unit_rows(X) if metric == "cosine" else X.detach()
+        res = self.K.silhouette(X, labels.to(device=X.device, dtype=torch.int32).contiguous(), k, metric)
+        self.last_silhouette = {"a": res.a, "b": res.b, "neighbor": res.neighbor, "counts": res.count,
+                                "invalid_rows": n - res.count.sum()}
+        return float(res.score.item()), res.s
+
+    def _silhouette_rows(self, kind, labels, ids, tables, metric):
+        table = self._knn_matrix(kind, tables)
+        if ids is not None:
+            table = table[self._ids_arg(ids, "ids").to(table.device)]
+        return self._silhouette(table, labels, metric)
+
+    def silhouette_entities(self, labels, ids=None, tables=None, metric="l2"):
+        """(score: float, samples float32 [n] on the device): the mean silhouette and every row's own (sklearn's silhouette_score and
+        silhouette_samples) of the entities `ids` (None: every entity; the subset cluster_entities(ids=...) clustered) under `labels`
+        (one integer per row in -1..n_clusters - 1, n_clusters = labels.max() + 1; -1: in no cluster, as is a row with a NaN, whose
+        sample is NaN).  metric="l2", or "cosine" on rows normalised as cluster_entities normalises them.  One fused all-pairs sweep
+        (kge_silhouette): no [n, n] block, the same bits on every run.  last_silhouette holds a, b, neighbor (the nearest other
+        cluster), counts and invalid_rows."""
+        return self._silhouette_rows("entity", labels, ids, tables, metric)
+
+    def silhouette_relations(self, labels, ids=None, tables=None, metric="l2"):
+        """silhouette_entities over Model.relation_matrix(tables)."""
+        return self._silhouette_rows("relation", labels, ids, tables, metric)
+
+    def silhouette_vectors(self, X, labels, metric="l2"):
+        """silhouette_entities for rows that are no table rows: X float32 [n, D]."""
+        X = X.detach() if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X))
+        X = X.to(device=self.config.device, dtype=torch.float32)
+        if X.dim() != 2:
+            raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
+        return self._silhouette(X.contiguous(), labels, metric)
+
+    def choose_n_clusters(self, candidates, kind="entity", ids=None, tables=None, **cluster_kw):
+        """(best n_clusters, {n_clusters: score}): cluster the rows (kind "entity" or "relation", the subset `ids` of them) at every
+        candidate count with cluster_kw (cluster_entities' keywords) and score each clustering by its mean silhouette under the same
+        metric.  The best is the highest score, the lower count on a tie.  One clustering and one silhouette per candidate."""
+        counts = sorted(set(int(c) for c in candidates))
+        if not counts or counts[0] < 2:
+            raise ValueError("candidates must be cluster counts of at least 2 (got %s)" % (list(candidates),))
+        if kind not in ("entity", "relation"):
+            raise ValueError("kind = %r (\"entity\" or \"relation\")" % (kind,))
+        X = self._knn_matrix(kind, tables)
+        if ids is not None:
+            X = X[self._ids_arg(ids, "ids").to(X.device)]
+        metric = cluster_kw.get("metric", "l2")
+        with torch.no_grad():   # the rows the silhouette sees: normalised once, as _cluster normalises them
+            rows = (self._unit_rows(X) if metric == "cosine" else X.detach()).contiguous()
+        scores = {}
+        for c in counts:
+            labels, _ = self._cluster(X, c, **cluster_kw)
+            res = self.K.silhouette(rows, labels.to(torch.int32), c, metric)
+            scores[c] = float(res.score.item())
+        best = max(counts, key=lambda c: (scores[c], -c) if scores[c] == scores[c] else (float("-inf"), -c))
+        return best, scores
 
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))

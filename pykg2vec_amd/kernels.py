@@ -1244,6 +1244,49 @@ def kmeans_seed(rows, k, u):
     return ids, cent
 
 
+# --- silhouette scores of labelled embedding rows (csrc/kge_silhouette.hip): one fused all-pairs MFMA sweep, no [n, n] block
+SilhouetteResult = collections.namedtuple("SilhouetteResult", "s a b neighbor count score")
+SilhouetteResult.__doc__ = """What silhouette leaves on the device: s, a, b float32 [n] (the silhouette, the mean distance inside the
+row's cluster, the least mean distance to another cluster), neighbor int32 [n] (that cluster; -1: none), count int32 [k], score
+float64 [1] (the mean of s over the counted rows).  A row with a NaN entry or label -1 has NaN s, a, b and neighbor -1."""
+
+
+def sil_metric(metric):
+    if metric not in L.SIL_METRICS:
+        raise ValueError("metric = %r (one of %s)" % (metric, ", ".join(sorted(L.SIL_METRICS))))
+    return L.SIL_METRICS[metric]
+
+
+def silhouette(rows, label, k, metric="l2"):
+    """Silhouette of every row (float32 [n, dim], unit inner stride) under the labels int32 [n] in -1..k-1 (kge_silhouette): no
+    [n, n] distance block is written, the bits repeat from run to run.  "cosine" expects normalised rows.  -> SilhouetteResult."""
+    code = sil_metric(metric)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise TypeError("rows must be a 2-D tensor")
+    n, dim = (int(x) for x in rows.shape)
+    k = int(k)
+    if n < 2:
+        raise ValueError("a silhouette needs at least 2 rows (got %d)" % n)
+    if not 2 <= k <= KMEANS_MAX_K:
+        raise ValueError("k = %d outside 2..KGE_KMEANS_MAX_K = %d" % (k, KMEANS_MAX_K))
+    if not isinstance(label, torch.Tensor) or tuple(label.shape) != (n,):
+        raise ValueError("label must hold one id per row (%d)" % n)
+    if label.device != rows.device:
+        raise ValueError("rows and label live on different devices")
+    stride = _knn_rows_arg(rows, "rows")
+    lib, dev = L.load(), rows.device
+    ws = torch.empty(lib.kge_silhouette_workspace_bytes(n, dim, k), dtype=torch.uint8, device=dev)
+    s, a, b = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+    neighbor = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(k, dtype=torch.int32, device=dev)
+    score = torch.empty(1, dtype=torch.float64, device=dev)
+    L.check(lib.kge_silhouette(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, _dev(label, torch.int32, "label"), k, code,
+                               ctypes.c_void_p(ws.data_ptr()), ws.numel(), *(ctypes.c_void_p(t.data_ptr()) for t in
+                                                                             (s, a, b, neighbor, count, score)), _stream()),
+            "kge_silhouette")
+    return SilhouetteResult(s, a, b, neighbor, count, score)
+
+
 CAND_CHUNK = L.CAND_CHUNK
 
 
