@@ -300,6 +300,41 @@ int kge_silhouette(const float* rows, int64_t n, int64_t dim, int64_t row_stride
                    void* workspace, size_t workspace_bytes, float* out_s, float* out_a, float* out_b, int32_t* out_neighbor,
                    int32_t* out_count, double* out_score, void* stream);
 
+/* ---- DBSCAN of embedding rows (kge_dbscan.hip; Ester et al. 1996): density clusters without a cluster count; rows in sparse regions
+ * are noise, label -1 -- the label kge_silhouette already reads as "in no cluster".  Three kinds of all-pairs matrix-core sweeps; no
+ * [n, n] block of any kind (bits included) exists, no float atomic is used.  Every output is an integer and a unique function of the
+ * eps-graph: the same on every run and under every split.  Every buffer is the caller's and lives on the device.  rows float32
+ * [n, row_stride], the first dim elements of a row count.
+ *
+ * The pair test.  KGE_DBS_L2: j is a neighbour of i iff max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j, 0) <= eps2, the float32 expansion of the
+ * other sweeps: |x|^2 summed per row in a fixed order, the two norms added to each other first, the dot product one chain in ascending
+ * k on mfma_f32_32x32x2f32; eps2 = eps * eps formed in float64 and rounded to float32 once.  KGE_DBS_COSINE: max(1 - x_i.x_j, 0) <= eps
+ * on rows the caller has normalised; a zero row stays zero and is at distance 1 from everything.  The test is symmetric: (i, j) and
+ * (j, i) give the same bit.  Row i is its own neighbour by index, never by value.  A row with a NaN entry is nobody's neighbour, not
+ * even its own: count 0, core 0, label -1.  Only NaN is looked for: keeping +-Inf out of the rows is the caller's part.
+ *
+ * out_count int32 [n]: the row's neighbours, itself included.  out_core uint8 [n]: 1 where out_count >= min_samples.  Clusters are the
+ * connected components of the neighbour graph restricted to core rows, numbered 0, 1, ... in ascending order of their lowest core id
+ * (not their lowest member id); out_n_clusters int32 [1] is their number.  out_label int32 [n]: a core row's cluster; for a row that is
+ * no core but has core neighbours (a border row) the lowest cluster number among them; -1 for every other row.  That is what a scan in
+ * row order that grows each cluster to completion produces (sklearn's dbscan_inner).
+ *
+ * Components are labelled by rounds of min-id propagation with pointer jumping; after every round the host reads one int32, the
+ * round's change flag, from the stream (the call synchronises: it cannot be captured into a graph).  out_rounds int32 [1]: the rounds
+ * run, the last of which changed nothing: at most 1 + the largest hop distance from a component's lowest core to another core of it,
+ * never more than max(1, number of cores).  Seven launches and two per round.  The column range of a sweep is cut into S slabs, S a function
+ * of n alone (the switch DBS_SPLIT forces it); partials are integers, so the result does not depend on S.
+ *
+ * workspace: kge_dbscan_workspace_bytes of the same n and dim (0 for refused arguments), asked for under the same switches as the call:
+ * O(n S) bytes, S <= 64.  Refused before any GPU call, kge_last_error() naming the argument: n < 1, dim < 1, a stride below dim, eps
+ * negative or not finite, min_samples < 1, an unknown metric, a null pointer, a workspace that is too small. */
+#define KGE_DBS_L2 0
+#define KGE_DBS_COSINE 1
+size_t kge_dbscan_workspace_bytes(int64_t n, int64_t dim);
+int kge_dbscan(const float* rows, int64_t n, int64_t dim, int64_t row_stride, float eps, int32_t min_samples, int metric,
+               void* workspace, size_t workspace_bytes, int32_t* out_label, uint8_t* out_core, int32_t* out_count,
+               int32_t* out_n_clusters, int32_t* out_rounds, void* stream);
+
 /* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
  * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).
  * triples int64 [n, 3].  side 0 ranks tails (the candidates replace column 2), side 1 ranks heads (column 0); the true entity

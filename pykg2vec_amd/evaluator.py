@@ -16,6 +16,7 @@ the pair (h, t) left out (kernels.rank_relations): MR / MRR / Hits@k of relation
 thresholds fitted on labelled validation triples, then accuracy, per-relation accuracy and AUC (kernels.classification_fit /
 classification_apply / corrupt_typed).
 """
+import math
 import os
 import timeit
 
@@ -624,6 +625,78 @@ class Evaluator:
             scores[c] = float(res.score.item())
         best = max(counts, key=lambda c: (scores[c], -c) if scores[c] == scores[c] else (float("-inf"), -c))
         return best, scores
+
+    # --- DBSCAN of embedding rows (kge_dbscan): clusters without a cluster count, the long tail of rows left as noise (-1)
+    last_dbscan = None
+
+    def _dbscan(self, X, eps, min_samples=5, metric="l2"):
+        if metric not in ("l2", "cosine"):
+            raise ValueError("metric = %r (\"l2\" or \"cosine\")" % (metric,))
+        eps, min_samples = float(eps), int(min_samples)
+        if not (math.isfinite(eps) and eps >= 0) or min_samples < 1:
+            raise ValueError("eps = %r, min_samples = %d (a finite distance >= 0, at least 1)" % (eps, min_samples))
+        if int(X.shape[0]) < 1:
+            raise ValueError("dbscan needs at least one row")
+        with torch.no_grad():
+            X = self._unit_rows(X) if metric == "cosine" else X.detach()
+        res = self.K.dbscan(X, eps, min_samples, metric)
+        self.last_dbscan = {"n_clusters": int(res.n_clusters.item()), "core": res.core.bool(), "neighbor_counts": res.count,
+                            "noise_rows": (res.label < 0).sum(), "rounds": int(res.rounds.item())}
+        return res.label.to(torch.int64)
+
+    def _dbscan_rows(self, kind, eps, min_samples, ids, tables, metric):
+        table = self._knn_matrix(kind, tables)
+        if ids is not None:
+            table = table[self._ids_arg(ids, "ids").to(table.device)]
+        return self._dbscan(table, eps, min_samples, metric)
+
+    def dbscan_entities(self, eps, min_samples=5, ids=None, tables=None, metric="l2"):
+        """labels int64 [n] on the device: DBSCAN (sklearn.cluster.DBSCAN's labels_) over the entities `ids` (None: every entity), rows
+        from Model.entity_matrix(tables).  Two rows are neighbours when their distance is <= eps -- Euclidean for metric="l2"; for
+        "cosine" 1 - cos on rows normalised as cluster_entities normalises them.  A row with at least min_samples neighbours, itself
+        included, is a core; clusters are the connected cores, numbered by their lowest core id; a row that is no core joins the
+        lowest-numbered cluster among its core neighbours; every other row, and a row with a NaN, is noise: -1, the label
+        silhouette_entities reads as "in no cluster".  Fused all-pairs sweeps (kge_dbscan): no [n, n] block, the same result on every
+        run.  last_dbscan holds n_clusters, core (bool [n]), neighbor_counts (int32 [n]), noise_rows and rounds.  suggest_eps proposes
+        an eps."""
+        return self._dbscan_rows("entity", eps, min_samples, ids, tables, metric)
+
+    def dbscan_relations(self, eps, min_samples=5, ids=None, tables=None, metric="l2"):
+        """dbscan_entities over Model.relation_matrix(tables)."""
+        return self._dbscan_rows("relation", eps, min_samples, ids, tables, metric)
+
+    def dbscan_vectors(self, X, eps, min_samples=5, metric="l2"):
+        """dbscan_entities for rows that are no table rows: X float32 [n, D]."""
+        X = X.detach() if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X))
+        X = X.to(device=self.config.device, dtype=torch.float32)
+        if X.dim() != 2:
+            raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
+        return self._dbscan(X.contiguous(), eps, min_samples, metric)
+
+    def suggest_eps(self, min_samples=5, kind="entity", ids=None, tables=None, metric="l2", quantile=0.9):
+        """float: the k-distance heuristic for dbscan_*'s eps -- the given quantile (linear between order statistics) of every row's
+        distance to its (min_samples - 1)-th nearest other row, read from nearest_entities' search (2 <= min_samples <= KGE_KNN_MAX +
+        1).  For "cosine" the distance is 1 - similarity.  Rows with fewer live neighbours are left out."""
+        k, q = int(min_samples) - 1, float(quantile)
+        if metric not in ("l2", "cosine"):
+            raise ValueError("metric = %r (\"l2\" or \"cosine\")" % (metric,))
+        if not 1 <= k <= K.KNN_MAX or not 0.0 <= q <= 1.0:
+            raise ValueError("min_samples = %d outside 2..%d (KGE_KNN_MAX + 1) or quantile = %g outside [0, 1]" % (k + 1, K.KNN_MAX + 1, q))
+        table = self._knn_matrix(kind, tables)
+        if ids is not None:
+            table = table[self._ids_arg(ids, "ids").to(table.device)].contiguous()
+        n = int(table.shape[0])
+        own = torch.arange(n, dtype=torch.int64, device=table.device)
+        _, vals = self._knn_chunks(table, n, k, metric, lambda a, b: table[a:b], own)
+        d = vals[:, k - 1].double()
+        d = torch.sort(d[d == d]).values
+        if d.numel() == 0:
+            raise ValueError("no row has %d other live rows" % k)
+        d = d if metric == "l2" else (1.0 - d).clamp_min(0.0).flip(0)
+        at = q * (d.numel() - 1)
+        lo = int(at)
+        hi = min(lo + 1, d.numel() - 1)
+        return float((d[lo] + (d[hi] - d[lo]) * (at - lo)).item())
 
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))

@@ -1287,6 +1287,44 @@ def silhouette(rows, label, k, metric="l2"):
     return SilhouetteResult(s, a, b, neighbor, count, score)
 
 
+# --- DBSCAN of embedding rows (csrc/kge_dbscan.hip): neighbour counts, core components and labels by fused all-pairs MFMA sweeps
+DbscanResult = collections.namedtuple("DbscanResult", "label core count n_clusters rounds")
+DbscanResult.__doc__ = """What dbscan leaves on the device: label int32 [n] (the cluster, numbered by lowest core id; -1: noise), core
+uint8 [n], count int32 [n] (the neighbours within eps, the row included), n_clusters int32 [1], rounds int32 [1] (labelling rounds
+run).  A row with a NaN entry has label -1, core 0 and count 0 and is counted by nobody."""
+
+
+def dbscan(rows, eps, min_samples, metric="l2"):
+    """DBSCAN of the rows (float32 [n, dim], unit inner stride): j is a neighbour of i iff their L2 distance is <= eps ("cosine": 1 -
+    x_i.x_j <= eps on normalised rows); a row with at least min_samples neighbours, itself included, is a core; clusters are the
+    components of the core graph, border rows join the lowest-numbered cluster among their core neighbours (kge_dbscan).  No [n, n]
+    block is written; every output is an integer and the same on every run.  The call reads one int32 per labelling round from the
+    stream.  -> DbscanResult."""
+    if metric not in L.DBS_METRICS:
+        raise ValueError("metric = %r (one of %s)" % (metric, ", ".join(sorted(L.DBS_METRICS))))
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise TypeError("rows must be a 2-D tensor")
+    n, dim = (int(x) for x in rows.shape)
+    eps, min_samples = float(eps), int(min_samples)
+    if n < 1 or dim < 1:
+        raise ValueError("dbscan needs at least one row and one column (got %s)" % (list(rows.shape),))
+    if not (math.isfinite(eps) and eps >= 0):
+        raise ValueError("eps = %r is not a finite distance >= 0" % (eps,))
+    if min_samples < 1:
+        raise ValueError("min_samples = %d below 1" % min_samples)
+    stride = _knn_rows_arg(rows, "rows")
+    lib, dev = L.load(), rows.device
+    ws = torch.empty(lib.kge_dbscan_workspace_bytes(n, dim), dtype=torch.uint8, device=dev)
+    label, count = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    core = torch.empty(n, dtype=torch.uint8, device=dev)
+    n_clusters, rounds = (torch.empty(1, dtype=torch.int32, device=dev) for _ in range(2))
+    L.check(lib.kge_dbscan(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, eps, min_samples, L.DBS_METRICS[metric],
+                           ctypes.c_void_p(ws.data_ptr()), ws.numel(), *(ctypes.c_void_p(t.data_ptr()) for t in
+                                                                         (label, core, count, n_clusters, rounds)), _stream()),
+            "kge_dbscan")
+    return DbscanResult(label, core, count, n_clusters, rounds)
+
+
 CAND_CHUNK = L.CAND_CHUNK
 
 

@@ -1252,6 +1252,15 @@ class Trainer:
         which = range(len(labels)) if ids is None else [int(i) for i in self.evaluator._ids_arg(ids, "ids").tolist()]
         return labels, {i: idx2ent[i] for i in which}
 
+    def dbscan_entities(self, eps, min_samples=5, ids=None, **kw):
+        """(labels numpy int64 [n], {entity id: name}): the DBSCAN cluster (-1: noise) of the entities `ids` (None: every entity)
+        through Evaluator.dbscan_entities, whose keywords it takes."""
+        self.sync_model()
+        idx2ent = self.config.knowledge_graph.read_cache_data('idx2entity')
+        labels = self.evaluator.dbscan_entities(eps, min_samples, ids, **kw).cpu().numpy()
+        which = range(len(labels)) if ids is None else [int(i) for i in self.evaluator._ids_arg(ids, "ids").tolist()]
+        return labels, {i: idx2ent[i] for i in which}
+
     def display(self):
         """utils/trainer.py:421-437: the embedding plots when config.plot_embedding is set (entities; relations and entities with
         relations too unless config.plot_entity_only).  The loss-curve and result-table plots of the two other flags are not built."""
