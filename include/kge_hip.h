@@ -335,6 +335,37 @@ int kge_dbscan(const float* rows, int64_t n, int64_t dim, int64_t row_stride, fl
                void* workspace, size_t workspace_bytes, int32_t* out_label, uint8_t* out_core, int32_t* out_count,
                int32_t* out_n_clusters, int32_t* out_rounds, void* stream);
 
+/* ---- principal component analysis of embedding rows (kge_pca.hip): mean, sample covariance, its eigenvalues and unit axes in float64,
+ * and the projection of rows -- the fitted ones or others -- on the leading axes.  The centred Gram matrix runs on the float64 matrix
+ * cores (v_mfma_f64_16x16x4_f64), the eigensolver is a cyclic Jacobi iteration in one workgroup.  No [n, dim] centred copy or larger
+ * temporary exists, no float atomic is used: for a given split the bits repeat from run to run.  Every buffer is the caller's and lives
+ * on the device.  rows float32 [n, row_stride], the first dim elements of a row count, dim in 1..KGE_PCA_MAX_DIM.
+ *
+ * kge_pca_fit.  A row with a non-finite entry (NaN, +-Inf) enters neither the mean nor the covariance.  count int32 [1]: the rows used.
+ * mean float64 [dim]: chunks of 64 rows summed in row order, the chunk sums added in chunk order, divided by count (0 when count is 0).
+ * cov float64 [dim, dim]: sum over the used rows of (x - mean)(x - mean)^T, float32 entries centred in float64, divided by
+ * max(count - 1, 1); symmetric bit for bit.  The rows are cut into S contiguous slabs whose partial sums are added in slab order; S is
+ * a function of n and dim (the switch PCA_SPLIT forces it).  eigenvalue float64 [dim]: the eigenvalues of cov, descending (equal values
+ * in the order of their Jacobi index), clamped at 0 from below.  components float64 [dim, dim]: row c is the unit axis of eigenvalue[c];
+ * its sign makes its component of largest magnitude positive, the lowest index on a tie.  With count < 2 cov and eigenvalue are 0 and
+ * components is the identity.  sweeps int32 [1]: the Jacobi sweeps run; the solver stops after a sweep in which no rotation was needed
+ * (a rotation is skipped when |a_pq| <= 2^-53 sqrt(|a_pp a_qq|)), at the latest after 60.
+ *
+ * kge_pca_transform.  out float32 [n, n_components], contiguous: (x - mean) . components[c] accumulated in float64 on the matrix cores
+ * and rounded once; with whiten != 0 divided by sqrt(eigenvalue[c]) before the rounding, a component with eigenvalue 0 gives 0.  A row
+ * with a non-finite entry gives NaN in every component.  mean, components and eigenvalue are kge_pca_fit's (or any of the same shapes).
+ *
+ * workspace: kge_pca_workspace_bytes of the same n and dim (0 for refused arguments), asked for under the same switches as the call:
+ * n + n dim / 8 + 32768 S pairs + 16 dim^2 bytes at the most, pairs = T (T + 1) / 2 for T = ceil(dim / 64), S <= 64.  Refused before any
+ * GPU call, kge_last_error() naming the argument: n < 1, dim outside 1..KGE_PCA_MAX_DIM, a stride below dim, n_components outside
+ * 1..dim, a null pointer, a workspace that is too small. */
+#define KGE_PCA_MAX_DIM 512
+size_t kge_pca_workspace_bytes(int64_t n, int64_t dim);
+int kge_pca_fit(const float* rows, int64_t n, int64_t dim, int64_t row_stride, void* workspace, size_t workspace_bytes, double* out_mean,
+                double* out_cov, double* out_eigenvalue, double* out_components, int32_t* out_count, int32_t* out_sweeps, void* stream);
+int kge_pca_transform(const float* rows, int64_t n, int64_t dim, int64_t row_stride, const double* mean, const double* components,
+                      const double* eigenvalue, int32_t n_components, int whiten, float* out, void* stream);
+
 /* ---- ranking against given candidates (kge_candidates.hip): where does the true entity of query i stand among the ids of its
  * list L(i)?  The cost scales with the lists, not with tot_entity (fixed negatives per test triple, type-constrained ranking).
  * triples int64 [n, 3].  side 0 ranks tails (the candidates replace column 2), side 1 ranks heads (column 0); the true entity

@@ -130,6 +130,7 @@ KMEANS_MAX_K = 4096   # KGE_KMEANS_MAX_K: the most clusters of kge_kmeans_*
 KMEANS_CHUNK = 128    # KGE_KMEANS_CHUNK: members per float32 partial sum of kge_kmeans_update
 SIL_METRICS = {"l2": 0, "cosine": 1}   # KGE_SIL_L2 / _COSINE
 DBS_METRICS = {"l2": 0, "cosine": 1}   # KGE_DBS_L2 / _COSINE
+PCA_MAX_DIM = 512     # KGE_PCA_MAX_DIM: the most columns of kge_pca_*
 CAND_CHUNK = 64   # KGE_CAND_CHUNK: list entries per work item of kge_rank_candidates
 REL_CHUNK = 64    # KGE_REL_CHUNK: relation ids per work item of kge_rank_relations
 TYPED_ATTEMPTS = 16           # KGE_TYPED_ATTEMPTS: typed draws of kge_corrupt_typed before it falls back
@@ -389,6 +390,11 @@ _SIGNATURES = {
     "kge_dbscan_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
     "kge_dbscan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_int32,
                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 6),
+    "kge_pca_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "kge_pca_fit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t] +
+                    [ctypes.c_void_p] * 7),
+    "kge_pca_transform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "kge_rank_candidates_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "kge_rank_candidates": (ctypes.c_int, [ctypes.POINTER(ModelDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,

@@ -19,6 +19,7 @@ classification_apply / corrupt_typed).
 import math
 import os
 import timeit
+import types
 
 import numpy as np
 import torch
@@ -697,6 +698,61 @@ class Evaluator:
         lo = int(at)
         hi = min(lo + 1, d.numel() - 1)
         return float((d[lo] + (d[hi] - d[lo]) * (at - lo)).item())
+
+    # --- PCA of embedding rows (kge_pca_*): a linear map, the explained-variance spectrum, whitened rows for the clusterings
+    last_pca = None
+
+    def _pca(self, X, n_components=2, whiten=False):
+        n_components = int(n_components)
+        if int(X.shape[0]) < 2:
+            raise ValueError("a PCA needs at least 2 rows (got %d)" % int(X.shape[0]))
+        if not 1 <= n_components <= int(X.shape[1]):
+            raise ValueError("n_components = %d outside 1..D = %d" % (n_components, int(X.shape[1])))
+        X = X.detach()
+        fit = self.K.pca_fit(X)
+        total = fit.explained_variance.sum()
+        ratio = torch.where(total > 0, fit.explained_variance / torch.where(total > 0, total, torch.ones_like(total)),
+                            torch.zeros_like(fit.explained_variance))
+        self.last_pca = types.SimpleNamespace(explained_variance_ratio=ratio, **fit._asdict())
+        return self.K.pca_transform(X, fit, n_components, whiten)
+
+    def _pca_rows(self, kind, n_components, ids, tables, whiten):
+        table = self._knn_matrix(kind, tables)
+        if ids is not None:
+            table = table[self._ids_arg(ids, "ids").to(table.device)]
+        return self._pca(table, n_components, whiten)
+
+    def pca_entities(self, n_components=2, ids=None, tables=None, whiten=False):
+        """float32 [n, n_components] on the device: the entities `ids` (None: every entity), rows from Model.entity_matrix(tables),
+        projected on their leading principal axes (sklearn.decomposition.PCA's fit_transform; whiten divides every component by its
+        standard deviation, e.g. before cluster_* / dbscan_*).  Mean, covariance, eigenvalues and axes are float64 (kge_pca_fit: the
+        covariance on the float64 matrix cores, a Jacobi eigensolver); a row with a non-finite entry enters nothing and projects to
+        NaN.  No [n, D] temporary, the same bits on every run.  last_pca holds the fit: mean, cov, explained_variance,
+        explained_variance_ratio (all zeros for rows without variance), components (row c: the axis, its largest component positive),
+        count, sweeps; pca_transform_vectors projects other rows on it.  project_entities' own init="pca" stays its float64 torch
+        composition; to start a t-SNE from this PCA pass init=1e-4 * Y / Y[:, 0].std() of the [n, 2] result Y."""
+        return self._pca_rows("entity", n_components, ids, tables, whiten)
+
+    def pca_relations(self, n_components=2, ids=None, tables=None, whiten=False):
+        """pca_entities over Model.relation_matrix(tables)."""
+        return self._pca_rows("relation", n_components, ids, tables, whiten)
+
+    def _pca_vectors_arg(self, X):
+        X = X.detach() if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X))
+        X = X.to(device=self.config.device, dtype=torch.float32)
+        if X.dim() != 2:
+            raise ValueError("vectors must be [n, D] (got %s)" % (list(X.shape),))
+        return X.contiguous()
+
+    def pca_vectors(self, X, n_components=2, whiten=False):
+        """pca_entities for rows that are no table rows: X float32 [n, D]."""
+        return self._pca(self._pca_vectors_arg(X), n_components, whiten)
+
+    def pca_transform_vectors(self, X, n_components=2, whiten=False):
+        """float32 [n, n_components]: the rows X [n, D], which need not have been in the fit, projected on last_pca."""
+        if self.last_pca is None:
+            raise ValueError("no fit yet: pca_entities / pca_relations / pca_vectors leave one in last_pca")
+        return self.K.pca_transform(self._pca_vectors_arg(X), self.last_pca, n_components, whiten)
 
     def mini_test(self, epoch=None):
         n = len(self.eval_data) if self.config.test_num == 0 else min(self.config.test_num, len(self.eval_data))

@@ -1325,6 +1325,74 @@ def dbscan(rows, eps, min_samples, metric="l2"):
     return DbscanResult(label, core, count, n_clusters, rounds)
 
 
+# --- PCA of embedding rows (csrc/kge_pca.hip): float64 MFMA covariance, a one-workgroup Jacobi eigensolver, MFMA projection
+PCA_MAX_DIM = L.PCA_MAX_DIM
+PcaResult = collections.namedtuple("PcaResult", "mean cov explained_variance components count sweeps")
+PcaResult.__doc__ = """What pca_fit leaves on the device: mean float64 [dim], cov float64 [dim, dim] (divisor max(count - 1, 1)),
+explained_variance float64 [dim] (the eigenvalues of cov, descending, clamped at 0), components float64 [dim, dim] (row c: the unit
+axis of explained_variance[c], its component of largest magnitude positive), count int32 [1] (the rows without a non-finite entry),
+sweeps int32 [1] (Jacobi sweeps run)."""
+
+
+def _pca_rows(rows, what):
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise TypeError("%s must be a 2-D tensor" % what)
+    n, dim = (int(x) for x in rows.shape)
+    if not 1 <= dim <= PCA_MAX_DIM:
+        raise ValueError("dim = %d outside 1..KGE_PCA_MAX_DIM = %d" % (dim, PCA_MAX_DIM))
+    return n, dim
+
+
+def pca_workspace_bytes(n, dim):
+    """Bytes of pca_fit's workspace under the switches now in force (0 for refused shapes): no [n, dim] term."""
+    return int(L.load().kge_pca_workspace_bytes(int(n), int(dim)))
+
+
+def pca_fit(rows):
+    """PCA of the rows (float32 [n, dim], unit inner stride, n >= 2, dim <= PCA_MAX_DIM): mean, sample covariance, eigenvalues and
+    axes in float64 (kge_pca_fit).  A row with a non-finite entry enters nothing.  No [n, dim] temporary is written; for a given
+    PCA_SPLIT the bits repeat from run to run.  -> PcaResult."""
+    n, dim = _pca_rows(rows, "rows")
+    if n < 2:
+        raise ValueError("pca_fit needs at least 2 rows (got %d)" % n)
+    stride = _knn_rows_arg(rows, "rows")
+    lib, dev = L.load(), rows.device
+    ws = torch.empty(lib.kge_pca_workspace_bytes(n, dim), dtype=torch.uint8, device=dev)
+    mean, eigenvalue = (torch.empty(dim, dtype=torch.float64, device=dev) for _ in range(2))
+    cov, components = (torch.empty((dim, dim), dtype=torch.float64, device=dev) for _ in range(2))
+    count, sweeps = (torch.empty(1, dtype=torch.int32, device=dev) for _ in range(2))
+    L.check(lib.kge_pca_fit(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                            *(ctypes.c_void_p(t.data_ptr()) for t in (mean, cov, eigenvalue, components, count, sweeps)), _stream()),
+            "kge_pca_fit")
+    return PcaResult(mean, cov, eigenvalue, components, count, sweeps)
+
+
+def pca_transform(rows, fit, n_components, whiten=False):
+    """float32 [n, n_components]: (x - fit.mean) . fit.components[c], divided by sqrt(fit.explained_variance[c]) with whiten (a
+    component without variance gives 0), accumulated in float64 and rounded once (kge_pca_transform).  The rows need not be the
+    fitted ones; a row with a non-finite entry gives NaN.  fit: a PcaResult, or anything with its mean, components and
+    explained_variance."""
+    n, dim = _pca_rows(rows, "rows")
+    n_components = int(n_components)
+    if n < 1:
+        raise ValueError("pca_transform needs at least one row")
+    if tuple(fit.components.shape) != (dim, dim) or tuple(fit.mean.shape) != (dim,) or tuple(fit.explained_variance.shape) != (dim,):
+        raise ValueError("a fit of %d columns against rows of %d" % (int(fit.mean.shape[0]), dim))
+    if not 1 <= n_components <= dim:
+        raise ValueError("n_components = %d outside 1..dim = %d" % (n_components, dim))
+    parts = (fit.mean, fit.components, fit.explained_variance)
+    if any(t.device != rows.device for t in parts):
+        raise ValueError("rows on %s, the fit on %s" % (rows.device, ", ".join(str(t.device) for t in parts)))
+    if any(t.dtype != torch.float64 or not t.is_contiguous() for t in parts):
+        raise TypeError("the fit's mean, components and explained_variance must be contiguous float64 tensors")
+    stride = _knn_rows_arg(rows, "rows")
+    out = torch.empty((n, n_components), dtype=torch.float32, device=rows.device)
+    L.check(L.load().kge_pca_transform(ctypes.c_void_p(rows.data_ptr()), n, dim, stride, *(ctypes.c_void_p(t.data_ptr()) for t in parts),
+                                       n_components, 1 if whiten else 0, ctypes.c_void_p(out.data_ptr()), _stream()),
+            "kge_pca_transform")
+    return out
+
+
 CAND_CHUNK = L.CAND_CHUNK
 
 

@@ -1261,6 +1261,15 @@ class Trainer:
         which = range(len(labels)) if ids is None else [int(i) for i in self.evaluator._ids_arg(ids, "ids").tolist()]
         return labels, {i: idx2ent[i] for i in which}
 
+    def pca_entities(self, n_components=2, ids=None, **kw):
+        """(coordinates numpy float32 [n, n_components], {entity id: name}): the entities `ids` (None: every entity) on their leading
+        principal axes through Evaluator.pca_entities, whose keywords it takes; the fit stays in evaluator.last_pca."""
+        self.sync_model()
+        idx2ent = self.config.knowledge_graph.read_cache_data('idx2entity')
+        Y = self.evaluator.pca_entities(n_components, ids, **kw).cpu().numpy()
+        which = range(len(Y)) if ids is None else [int(i) for i in self.evaluator._ids_arg(ids, "ids").tolist()]
+        return Y, {i: idx2ent[i] for i in which}
+
     def display(self):
         """utils/trainer.py:421-437: the embedding plots when config.plot_embedding is set (entities; relations and entities with
         relations too unless config.plot_entity_only).  The loss-curve and result-table plots of the two other flags are not built."""
